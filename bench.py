@@ -2,8 +2,9 @@
 """bench.py -- headline benchmark of the MI355X batched DSP backend.
 
 Contract (see DESIGN.md "Measurement"):
-  python bench.py --gpus N --steps K --warmup W
-prints ONE JSON line on rank 0.
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+prints ONE JSON line on rank 0; exactly K steps are timed and ms_per_step is their mean wall time.  --dump-outputs: the outputs of
+the last timed step as DIR/*.npy (dump_outputs), for comparing two builds output for output.
 
 Workload: the north_star hot path, chained on the device, per call leg and
 10 ms tick (src/base/msticker.c:46): MSResample 16k->48k -> MSSpeexEC (48 kHz,
@@ -88,7 +89,24 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
                     help="where the full record goes (everything the short stdout line leaves out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed: DIR/mixed.npy, float32, the conference "
+                         "mix every one of the first 8192 legs hears")
     return ap.parse_args()
+
+
+DUMP_LEGS = 8192  # 256 whole conferences: 15 MB of float32
+
+
+def dump_outputs(rig, out_dir):
+    """The conference mix the last timed step handed every one of the first min(legs, DUMP_LEGS) legs: DIR/mixed.npy, float32
+    [legs][480], the int16 samples exactly.  Those legs play the same scenes, conferences, re-framing leads and number of
+    ticks whatever leg count the capacity sweep settles on, so the same arguments give the same inputs from run to run."""
+    k = min(rig.n, DUMP_LEGS)
+    mixed = rig.mixed[:k].cpu().numpy().astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "mixed.npy"), mixed)
+    print(f"bench.py: outputs of the last timed step written to {out_dir} (mixed {list(mixed.shape)})", file=sys.stderr, flush=True)
 
 
 def synth_pcm_batch(nstreams, n, rate, seed0=0x5EED, sigma=3000.0):
@@ -1863,6 +1881,8 @@ def main():
     ev_ms = head.run(steps)
     sync_local()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:  # (untimed, and before finish_period() ticks on over the last step's outputs)
+        dump_outputs(rig, a.dump_outputs)
     barrier()
     head.finish_period(steps)
     dt = reduce_scalar(dt, "MAX")

@@ -97,6 +97,7 @@ class Rig:
         self.n = self.nconf * self.MEMBERS + nsplit * self.mloc
         self.cost_ms = self.n / LEGS_PER_MS * float(os.environ.get(f"DOUBLE_SLOW_RANK{rank}", "1"))
         self.rank = rank
+        self.mixed = torch.zeros((self.n, 480), dtype=torch.int16)  # what every leg hears: here, which tick wrote it last
         if nsplit:
             g = torch.Generator().manual_seed(1234 + rank)
             self.feed = [torch.randint(-12000, 12000, (nsplit, self.mloc, 480), generator=g, dtype=torch.int16) for _ in range(self.RING)]
@@ -106,6 +107,7 @@ class Rig:
 
     def _tick(self, t):
         Clock.now_ms += self.cost_ms
+        self.mixed[:, 0] = t % self.RING
         if self.nsplit:
             self.split_in.copy_(self.feed[t % self.RING])
             self.d_sum.copy_(self.split_in.to(self.torch.int32).sum(1))

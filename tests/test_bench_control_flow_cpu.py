@@ -81,6 +81,22 @@ def test_one_rank_sweep_settles_on_the_doubles_capacity():
     assert "split_conferences" not in d["config"]
 
 
+def test_dump_outputs_holds_what_the_last_timed_step_computed():
+    """--dump-outputs DIR: exactly --steps steps are timed, and DIR/mixed.npy is what the LAST of them wrote (tick 20 % 16 - 1 = 3 of
+    the scene period), not the untimed ticks that complete the period after it; float32, one row per leg of the sample, under 64 MB"""
+    import numpy as np
+    with tempfile.TemporaryDirectory() as d:
+        r = run(1, args=("--steps", "20", "--dump-outputs", d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = the_line(r)
+        assert line["steps"] == 20 and line["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["mixed.npy"]
+        m = np.load(os.path.join(d, "mixed.npy"))
+        assert m.dtype == np.float32 and m.shape == (min(line["value"], 8192), 480), (m.dtype, m.shape)
+        assert m.nbytes <= 64 << 20
+        assert (m[:, 0] == 3).all(), np.unique(m[:, 0])
+
+
 def test_final_line_is_short():
     """The line the driver parses carries numbers and short identifiers only -- also when every optional section is as large as a
     real run makes it: bench.short_line() over round 4's full 26.5 KB record (profiles/r04_bench_final.json) stays under 6 000

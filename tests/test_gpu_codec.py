@@ -1,8 +1,10 @@
 """G.711 / L16 / channel adapter / audio flow controller through the C ABI vs the oracle.
 
 All integer work: bit-exact.  The oracle's four G.711 conversions are themselves pinned against the reference's
-own g711.c (tests/test_oracle_cpu.py::test_g711_matches_the_reference_build), and the GPU kernels are compared with
-that build directly here when oracle/_ref travelled with the snapshot."""
+own g711.c (tests/test_oracle_codec_cpu.py::test_g711_matches_the_reference_build), and the GPU kernels are compared
+with that build's stored outputs (tests/golden/g711.npz) directly here."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -10,6 +12,7 @@ import torch
 import mediastreamer2_amd as ms
 
 pytestmark = pytest.mark.gpu
+G711 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g711.npz")
 
 
 def dev(x):
@@ -30,10 +33,9 @@ def test_g711_decode_every_code_word(ctx, oracle, law):
     torch.cuda.synchronize()
     got = host(ctx, ms.g711_decode(ctx, law, dev(codes), pcm))
     np.testing.assert_array_equal(got, oracle.g711_decode(law, codes))
-    R = oracle.g711_ref()
-    if R is not None:  # the reference's own g711.c
-        fn = R.Snack_Alaw2Lin if law == ms.MI_LAW_PCMA else R.Snack_Mulaw2Lin
-        np.testing.assert_array_equal(got[0], np.array([fn(int(c)) for c in range(256)], np.int16))
+    # the reference's own g711.c, code words 0..255
+    want = np.load(G711)["alaw_decode" if law == ms.MI_LAW_PCMA else "ulaw_decode"]
+    np.testing.assert_array_equal(got[0], want)
 
 
 @pytest.mark.parametrize("law", [ms.MI_LAW_PCMA, ms.MI_LAW_PCMU])
@@ -43,11 +45,9 @@ def test_g711_encode_every_pcm_value(ctx, oracle, law):
     torch.cuda.synchronize()
     got = host(ctx, ms.g711_encode(ctx, law, dev(pcm), codes))
     np.testing.assert_array_equal(got, oracle.g711_encode(law, pcm))
-    R = oracle.g711_ref()
-    if R is not None:
-        fn = R.Snack_Lin2Alaw if law == ms.MI_LAW_PCMA else R.Snack_Lin2Mulaw
-        want = np.array([fn(int(v)) for v in pcm.ravel()], np.uint8).reshape(pcm.shape)
-        np.testing.assert_array_equal(got, want)
+    # the reference's own g711.c, PCM values -32768..32767 (the order of `pcm` above)
+    want = np.load(G711)["alaw_encode" if law == ms.MI_LAW_PCMA else "ulaw_encode"].reshape(pcm.shape)
+    np.testing.assert_array_equal(got, want)
 
 
 @pytest.mark.parametrize("law", [ms.MI_LAW_PCMA, ms.MI_LAW_PCMU])
