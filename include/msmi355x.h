@@ -321,6 +321,10 @@ int mi_equalizer_process_masked(mi_equalizer *e, int16_t *d_samples, int nsample
 typedef struct mi_aec mi_aec;
 /* speex_ec_preprocess sizing, speexec.c:171-180,:194-203 */
 int mi_aec_framesize(int framesize_at_8000, int sample_rate);
+/* frame_size: 64, 128, 256 or 512 -- what mi_aec_framesize gives with the default setting (framesize_at_8000 = 64) at
+ * 8 kHz (64), 16 kHz (128), 32-48 kHz (256) and 96 kHz (512); with MS_ECHO_CANCELLER_SET_FRAMESIZE 86 to 170 (e.g. 128)
+ * a 48 kHz canceller runs 512-sample frames.  Anything else (1024 and up) is MI_ENOTSUP.  At most 64 filter blocks:
+ * filter_length <= 64 * frame_size (682 ms at 48 kHz with 512-sample frames, 341 ms at 96 kHz). */
 int mi_aec_create(mi_ctx *ctx, int nstreams, int sample_rate, int frame_size, int filter_length,
                   mi_aec **out);
 void mi_aec_destroy(mi_aec *a);

@@ -145,14 +145,18 @@ __device__ __forceinline__ float2 cmulf(float2 a, float2 b) {
 
 // kiss_fft factorisation (4s first, then 2), stages listed deepest first:
 // F=256: radix 4,4,4,4 with m = 1,4,16,64;  F=128: radix 2 (m=1) then 4,4,4 with m = 2,8,32;
-// F=64 (8 kHz): radix 4,4,4 with m = 1,4,16.
-__host__ __device__ constexpr int plan_n(int F) { return F == 64 ? 3 : 4; }
-__host__ __device__ constexpr int plan_p(int F, int s) { return (F == 128 && s == 0) ? 2 : 4; }
+// F=64 (8 kHz): radix 4,4,4 with m = 1,4,16;  F=512: radix 2 (m=1) then 4,4,4,4 with m = 2,8,32,128.
+__host__ __device__ constexpr int plan_n(int F) { return F == 64 ? 3 : (F == 512 ? 5 : 4); }
+__host__ __device__ constexpr int plan_p(int F, int s) { return ((F == 128 || F == 512) && s == 0) ? 2 : 4; }
 __host__ __device__ constexpr int plan_m(int F, int s) {
-	return F == 128 ? (s == 0 ? 1 : (s == 1 ? 2 : (s == 2 ? 8 : 32))) : (s == 0 ? 1 : (s == 1 ? 4 : (s == 2 ? 16 : 64)));
+	return F == 512   ? (s == 0 ? 1 : (s == 1 ? 2 : (s == 2 ? 8 : (s == 3 ? 32 : 128))))
+	       : F == 128 ? (s == 0 ? 1 : (s == 1 ? 2 : (s == 2 ? 8 : 32)))
+	                  : (s == 0 ? 1 : (s == 1 ? 4 : (s == 2 ? 16 : 64)));
 }
 __host__ __device__ constexpr int plan_fs(int F, int s) {
-	return F == 64 ? (s == 0 ? 16 : (s == 1 ? 4 : 1)) : (s == 0 ? 64 : (s == 1 ? 16 : (s == 2 ? 4 : 1)));
+	return F == 512  ? (s == 0 ? 256 : (s == 1 ? 64 : (s == 2 ? 16 : (s == 3 ? 4 : 1))))
+	       : F == 64 ? (s == 0 ? 16 : (s == 1 ? 4 : 1))
+	                 : (s == 0 ? 64 : (s == 1 ? 16 : (s == 2 ? 4 : 1)));
 }
 
 __device__ __forceinline__ float rdlane(float v, int l) {
@@ -535,9 +539,9 @@ static bool aec_group_form_on();
 int mi_aec_create(mi_ctx *ctx, int nstreams, int sample_rate, int frame_size, int filter_length, mi_aec **out) {
 	MI_CHECK_ARG(ctx && out && nstreams > 0 && sample_rate > 0 && filter_length > 0);
 	*out = nullptr;
-	if (frame_size != 64 && frame_size != 128 && frame_size != 256) {
-		mi::set_error("frame size %d not supported: the filter's 2^k sizing (speexec.c:171-180) gives 64 at 8 kHz, "
-		              "128 at 16 kHz and 256 at 32-48 kHz",
+	if (frame_size != 64 && frame_size != 128 && frame_size != 256 && frame_size != 512) {
+		mi::set_error("frame size %d not supported: the kernels are built for 64, 128, 256 and 512 (the filter's 2^k sizing, "
+		              "speexec.c:171-180, gives 512 at 48 kHz with a frame-size setting of 86 to 170 and at 96 kHz with the default)",
 		              frame_size);
 		return MI_ENOTSUP;
 	}
@@ -625,6 +629,7 @@ int mi_aec_reset(mi_aec *a, int first, int count) {
 	MI_CHECK_ARG(a && first >= 0 && count >= 0 && first + count <= a->nstreams);
 	if (count == 0) return MI_OK;
 	if (a->ctx->activate() != MI_OK) return MI_ENODEV;
+	if (a->F == 512) return init_state<512>(a, first, count);
 	return a->F == 256 ? init_state<256>(a, first, count) : (a->F == 128 ? init_state<128>(a, first, count) : init_state<64>(a, first, count));
 }
 
@@ -722,7 +727,7 @@ static int aec_launch(mi_aec *a, const int16_t *d_mic, const int16_t *d_ref, int
 	// (its lanes take their four samples of a row as one 8-byte access: rows that start off that grid stay on the tick form)
 	const bool rows8 = !fifo && (stride & 3) == 0 &&
 	                   ((reinterpret_cast<uintptr_t>(d_mic) | reinterpret_cast<uintptr_t>(d_ref) | reinterpret_cast<uintptr_t>(d_out)) & 7) == 0;
-	if (rows8 && a->F != 256 && g_group_form.load(std::memory_order_relaxed) > 0) {
+	if (rows8 && a->F < 256 && g_group_form.load(std::memory_order_relaxed) > 0) {
 		for (int frame = 0; frame < max_frames; ++frame) {
 			if (a->F == 128) hipLaunchKernelGGL(aec_group_kernel<128>, dim3((a->nstreams + 1) / 2), dim3(64), 0, a->ctx->stream, g, frame);
 			else hipLaunchKernelGGL(aec_group_kernel<64>, dim3((a->nstreams + 3) / 4), dim3(64), 0, a->ctx->stream, g, frame);
@@ -736,7 +741,8 @@ static int aec_launch(mi_aec *a, const int16_t *d_mic, const int16_t *d_ref, int
 		else if (mode == TICK_FIFO) hipLaunchKernelGGL((aec_tick_kernel<FR, TICK_FIFO>), grid, dim3(64), 0, a->ctx->stream, g);  \
 		else hipLaunchKernelGGL((aec_tick_kernel<FR, TICK_ROWS>), grid, dim3(64), 0, a->ctx->stream, g);                        \
 	} while (0)
-	if (a->F == 256) MI_TICK_LAUNCH(256);
+	if (a->F == 512) MI_TICK_LAUNCH(512); // (one wave per SIMD: no several-legs-per-wavefront form at this size)
+	else if (a->F == 256) MI_TICK_LAUNCH(256);
 	else if (a->F == 128) MI_TICK_LAUNCH(128);
 	else MI_TICK_LAUNCH(64);
 #undef MI_TICK_LAUNCH
@@ -1077,7 +1083,7 @@ int mi_aec_copy_state(mi_aec *dst, int dst_first, const mi_aec *src, int src_fir
 int mi_debug_fft(mi_aec *a, const float *d_in, float *d_out, int nframes, int inverse) {
 	MI_CHECK_ARG(a && d_in && d_out && nframes > 0);
 	if (a->ctx->activate() != MI_OK) return MI_ENODEV;
-	if ((inverse & 2) && a->F != 256) { // bit 1: the several-legs-per-wavefront transforms
+	if ((inverse & 2) && a->F < 256) { // bit 1: the several-legs-per-wavefront transforms
 		if (a->F == 64) hipLaunchKernelGGL(fft_debug_group_kernel<64>, dim3((nframes + 3) / 4), dim3(64), 0, a->ctx->stream, d_in, d_out, inverse & 1, nframes, a->t);
 		else hipLaunchKernelGGL(fft_debug_group_kernel<128>, dim3((nframes + 1) / 2), dim3(64), 0, a->ctx->stream, d_in, d_out, inverse & 1, nframes, a->t);
 		MI_LAUNCH_CHECK();
@@ -1086,6 +1092,8 @@ int mi_debug_fft(mi_aec *a, const float *d_in, float *d_out, int nframes, int in
 	inverse &= 1;
 	if (a->F == 64)
 		hipLaunchKernelGGL(fft_debug_kernel<64>, dim3(nframes), dim3(64), 0, a->ctx->stream, d_in, d_out, inverse, a->t);
+	else if (a->F == 512)
+		hipLaunchKernelGGL(fft_debug_kernel<512>, dim3(nframes), dim3(64), 0, a->ctx->stream, d_in, d_out, inverse, a->t);
 	else if (a->F == 256)
 		hipLaunchKernelGGL(fft_debug_kernel<256>, dim3(nframes), dim3(64), 0, a->ctx->stream, d_in, d_out, inverse, a->t);
 	else

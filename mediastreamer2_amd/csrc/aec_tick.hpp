@@ -122,6 +122,10 @@ __device__ __forceinline__ void bload_vec(rsrc_t r, unsigned voff, unsigned soff
 	} else if constexpr (K == 2) {
 		const u2v t = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
 		v[0] = u2f(t.x), v[1] = u2f(t.y);
+	} else if constexpr (K == 8) {
+		const u4v t = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0), u = __builtin_amdgcn_raw_buffer_load_b128(r, voff + 16, soff, 0);
+		v[0] = u2f(t.x), v[1] = u2f(t.y), v[2] = u2f(t.z), v[3] = u2f(t.w);
+		v[4] = u2f(u.x), v[5] = u2f(u.y), v[6] = u2f(u.z), v[7] = u2f(u.w);
 	} else {
 		v[0] = u2f(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 	}
@@ -134,6 +138,10 @@ __device__ __forceinline__ void bstore_vec(rsrc_t r, unsigned voff, unsigned sof
 	} else if constexpr (K == 2) {
 		u2v t = {f2u(v[0]), f2u(v[1])};
 		__builtin_amdgcn_raw_buffer_store_b64(t, r, voff, soff, 0);
+	} else if constexpr (K == 8) {
+		u4v t = {f2u(v[0]), f2u(v[1]), f2u(v[2]), f2u(v[3])}, u = {f2u(v[4]), f2u(v[5]), f2u(v[6]), f2u(v[7])};
+		__builtin_amdgcn_raw_buffer_store_b128(t, r, voff, soff, 0);
+		__builtin_amdgcn_raw_buffer_store_b128(u, r, voff + 16, soff, 0);
 	} else {
 		__builtin_amdgcn_raw_buffer_store_b32(f2u(v[0]), r, voff, soff, 0);
 	}
@@ -195,7 +203,7 @@ enum { TICK_ROWS = 0, TICK_FIFO = 1, TICK_FIFO_RS = 2 };
 // 2's pass: bit-equal and 2.9x slower, two wavefronts per CU where this form runs eight.  profiles/r05_w_in_lds.txt holds the
 // measurement; the form is no longer in the source.)
 template <int F, int MODE>
-__global__ __launch_bounds__(64, F == 256 ? 2 : (F == 128 ? 3 : 4)) void aec_tick_kernel(AecArgs a) {
+__global__ __launch_bounds__(64, F == 512 ? 1 : (F == 256 ? 2 : (F == 128 ? 3 : 4))) void aec_tick_kernel(AecArgs a) {
 	__shared__ TLds<F> L;
 	using SL = TickLayout<F>;
 	constexpr int N = 2 * F, K = F / 64;
@@ -696,6 +704,18 @@ __global__ __launch_bounds__(64, F == 256 ? 2 : (F == 128 ? 3 : 4)) void aec_tic
 				cmac_bins<K>(ybgs, xa, w, e0);
 				norm_of(w, j);
 			};
+			if constexpr (F == 512) {
+				// one block per iteration (64 bytes per lane and block, twice the 256-sample form's): a second copy of `block` would
+				// take the form past the instruction cache
+				for (int j = 0; j < M; ++j) {
+					v2f xa[K], wa[K]; // the next block's: X(j+4), W(j+2) (clamped at the end: dropped)
+					bload_bins<K>(rX, vb8, xclamp(j + 4), xa);
+					bload_bins<K>(rWF, vb8, wsrc + wclamp(j + 2), wa);
+					block(j, wl, xj, xn, xn2);
+#pragma unroll
+					for (int k = 0; k < K; ++k) xj[k] = xn[k], xn[k] = xn2[k], xn2[k] = xn3[k], xn3[k] = xa[k], wl[k] = wl2[k], wl2[k] = wa[k];
+				}
+			} else {
 			for (int j = 0; j < M; j += 2) { // an odd block count: the last round serves one block (no third copy of `block` in the code)
 				v2f xa[K], xb[K], wa[K], wb[K]; // the next pair: X(j+3), X(j+4), W(j+2), W(j+3) (clamped at the end: dropped)
 				bload_bins<K>(rX, vb8, xclamp(j + 4), xa);
@@ -706,6 +726,7 @@ __global__ __launch_bounds__(64, F == 256 ? 2 : (F == 128 ? 3 : 4)) void aec_tic
 				if (j + 1 < M) block(j + 1, wl2, xn, xn2, xn3);
 #pragma unroll
 				for (int k = 0; k < K; ++k) xj[k] = xn2[k], xn[k] = xn3[k], xn2[k] = xa[k], xn3[k] = xb[k], wl[k] = wa[k], wl2[k] = wb[k];
+			}
 			}
 #pragma unroll
 			for (int k = 0; k < K; ++k) yfg[k] = spec2[k];

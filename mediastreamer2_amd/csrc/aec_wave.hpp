@@ -74,16 +74,63 @@ __device__ void w_cfft(LT &L, const AecTables &T, const float2 *src, bool invers
 			}
 		}
 	}
+	// F = 512 (K = 8): the lane's 8 values are four whole radix-2 butterflies of the deepest stage (m = 1) and then the two
+	// radix-4 butterflies (j = 0, 1) of the next one (m = 2: elements j, j + 2, j + 4, j + 6): both stages run in registers,
+	// same expressions and twiddles as the LDS stages below
+	constexpr bool kRegStage01 = (K == 8 && plan_p(F, 0) == 2 && plan_m(F, 1) == 2);
+	if constexpr (kRegStage01) {
+		float2 w0 = L.tw[0];
+		if (inverse) w0.y = -w0.y;
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			const float2 t = cmulf(val[2 * q + 1], w0);
+			const float2 a = val[2 * q];
+			val[2 * q + 1] = make_float2(a.x - t.x, a.y - t.y);
+			val[2 * q] = make_float2(a.x + t.x, a.y + t.y);
+		}
+		constexpr int fs1 = plan_fs(F, 1);
+#pragma unroll
+		for (int j = 0; j < 2; ++j) {
+			float2 w1 = L.tw[j * fs1], w2 = L.tw[j * fs1 * 2], w3 = L.tw[j * fs1 * 3];
+			if (inverse) {
+				w1.y = -w1.y;
+				w2.y = -w2.y;
+				w3.y = -w3.y;
+			}
+			const float2 s0 = cmulf(val[j + 2], w1);
+			const float2 s1 = cmulf(val[j + 4], w2);
+			const float2 s2 = cmulf(val[j + 6], w3);
+			float2 f0 = val[j];
+			const float2 s5 = make_float2(f0.x - s1.x, f0.y - s1.y);
+			f0.x += s1.x;
+			f0.y += s1.y;
+			const float2 s3 = make_float2(s0.x + s2.x, s0.y + s2.y);
+			const float2 s4 = make_float2(s0.x - s2.x, s0.y - s2.y);
+			val[j + 4] = make_float2(f0.x - s3.x, f0.y - s3.y);
+			f0.x += s3.x;
+			f0.y += s3.y;
+			val[j] = f0;
+			if (inverse) {
+				val[j + 2] = make_float2(s5.x - s4.y, s5.y + s4.x);
+				val[j + 6] = make_float2(s5.x + s4.y, s5.y - s4.x);
+			} else {
+				val[j + 2] = make_float2(s5.x + s4.y, s5.y - s4.x);
+				val[j + 6] = make_float2(s5.x - s4.y, s5.y + s4.x);
+			}
+		}
+	}
+	constexpr int kFirstLdsStage = kRegStage0 ? 1 : (kRegStage01 ? 2 : 0);
 	WSYNC();
 #pragma unroll
 	for (int k = 0; k < K; ++k) L.zbuf[lane * K + k] = val[k];
 	WSYNC();
 #pragma unroll
-	for (int s = kRegStage0 ? 1 : 0; s < plan_n(F); ++s) {
+	for (int s = kFirstLdsStage; s < plan_n(F); ++s) {
 		constexpr int FF = F;
 		const int p = plan_p(FF, s), m = plan_m(FF, s), fs = plan_fs(FF, s);
-		if (lane < F / p) {
-			const int i = lane / m, j = lane - i * m;
+		// butterfly bf of the stage (F / p of them: at most 64 up to F = 256, one per lane; F = 512: two per lane)
+		auto butterfly = [&](int bf) {
+			const int i = bf / m, j = bf - i * m;
 			float2 *Fo = L.zbuf + i * (p * m) + j;
 			if (p == 2) {
 				float2 w = L.tw[j * fs];
@@ -120,20 +167,27 @@ __device__ void w_cfft(LT &L, const AecTables &T, const float2 *src, bool invers
 					Fo[3 * m] = make_float2(s5.x - s4.y, s5.y + s4.x);
 				}
 			}
+		};
+		if constexpr (F > 256) {
+#pragma unroll 1
+			for (int bf = lane; bf < F / p; bf += 64) butterfly(bf);
+		} else {
+			if (lane < F / p) butterfly(lane);
 		}
 		WSYNC();
 	}
 }
 
-// L.tbuf (2F time samples) -> this lane's K bins, scaled 1/N.  Bin 0 = (DC, Nyquist).
-// src: the 2F time samples -- L.tbuf (the default) or L.zbuf, where the inverse transform leaves its result
+template <int K>
+__device__ __forceinline__ void load_bins(const float2 *p, float2 (&v)[K]);
+template <int K>
+__device__ __forceinline__ void store_bins(float2 *p, const float2 (&v)[K]);
+
+// the real transform's last pass: the complex transform's result in L.zbuf -> this lane's K bins
 template <int F, typename LT>
-__device__ void w_rfft_forward(LT &L, const AecTables &T, float2 (&out)[F / 64], const float *src = nullptr) {
-	if (src == nullptr) src = L.tbuf;
+__device__ __forceinline__ void w_rfft_forward_bins(LT &L, float2 (&out)[F / 64]) {
 	constexpr int K = F / 64;
 	const int lane = threadIdx.x;
-	WSYNC();
-	w_cfft<F>(L, T, reinterpret_cast<const float2 *>(src), false);
 	const float scale = 1.f / (2 * F);
 #pragma unroll
 	for (int k = 0; k < K; ++k) {
@@ -161,21 +215,42 @@ __device__ void w_rfft_forward(LT &L, const AecTables &T, float2 (&out)[F / 64],
 			out[k] = make_float2(r.x, r.y);
 		}
 	}
+}
+// F = 512: each transform is ONE copy in the code, called (sixteen inlined copies took the canceller's forms past the
+// instruction cache).  The bins travel through L.zbuf (lane l's at l K ..): no register array crosses the call.
+template <int F, typename LT>
+__device__ __attribute__((noinline)) void w_rfft_forward_lds(LT &L, const AecTables &T, const float *src) {
+	constexpr int K = F / 64;
+	w_cfft<F>(L, T, reinterpret_cast<const float2 *>(src), false);
+	float2 r[K];
+	w_rfft_forward_bins<F>(L, r);
+	WSYNC();
+	store_bins<K>(L.zbuf + threadIdx.x * K, r);
+}
+
+// L.tbuf (2F time samples) -> this lane's K bins, scaled 1/N.  Bin 0 = (DC, Nyquist).
+// src: the 2F time samples -- L.tbuf (the default) or L.zbuf, where the inverse transform leaves its result
+template <int F, typename LT>
+__device__ void w_rfft_forward(LT &L, const AecTables &T, float2 (&out)[F / 64], const float *src = nullptr) {
+	if (src == nullptr) src = L.tbuf;
+	constexpr int K = F / 64;
+	WSYNC();
+	if constexpr (F == 512) {
+		w_rfft_forward_lds<F>(L, T, src);
+		load_bins<K>(L.zbuf + threadIdx.x * K, out);
+	} else {
+		w_cfft<F>(L, T, reinterpret_cast<const float2 *>(src), false);
+		w_rfft_forward_bins<F>(L, out);
+	}
 	WSYNC();
 }
 
-// this lane's K bins -> 2F time samples in w_time(L), unscaled
+// the inverse real transform after its input bins are in L.spec: the split into one complex half-size spectrum, then the
+// complex transform
 template <int F, typename LT>
-__device__ void w_rfft_inverse(LT &L, const AecTables &T, const float2 (&in)[F / 64]) {
+__device__ __forceinline__ void w_rfft_inverse_tail(LT &L, const AecTables &T) {
 	constexpr int K = F / 64;
 	const int lane = threadIdx.x;
-	WSYNC();
-#pragma unroll
-	for (int k = 0; k < K; ++k) {
-		L.spec[2 * (lane * K + k)] = in[k].x;
-		L.spec[2 * (lane * K + k) + 1] = in[k].y;
-	}
-	WSYNC();
 	float2 *tmp = reinterpret_cast<float2 *>(L.tbuf);
 	float2 t[K];
 #pragma unroll
@@ -212,6 +287,26 @@ __device__ void w_rfft_inverse(LT &L, const AecTables &T, const float2 (&in)[F /
 	for (int k = 0; k < K; ++k) tmp[lane * K + k] = t[k];
 	WSYNC();
 	w_cfft<F>(L, T, tmp, true); // ends with an LDS fence: the 2F time samples are in L.zbuf (see w_time)
+}
+template <int F, typename LT>
+__device__ __attribute__((noinline)) void w_rfft_inverse_lds(LT &L, const AecTables &T) { // F = 512: one copy, called
+	w_rfft_inverse_tail<F>(L, T);
+}
+
+// this lane's K bins -> 2F time samples in w_time(L), unscaled
+template <int F, typename LT>
+__device__ void w_rfft_inverse(LT &L, const AecTables &T, const float2 (&in)[F / 64]) {
+	constexpr int K = F / 64;
+	const int lane = threadIdx.x;
+	WSYNC();
+#pragma unroll
+	for (int k = 0; k < K; ++k) {
+		L.spec[2 * (lane * K + k)] = in[k].x;
+		L.spec[2 * (lane * K + k) + 1] = in[k].y;
+	}
+	WSYNC();
+	if constexpr (F == 512) w_rfft_inverse_lds<F>(L, T);
+	else w_rfft_inverse_tail<F>(L, T);
 }
 
 
@@ -391,6 +486,9 @@ __device__ __forceinline__ void load_vec(const float *p, float (&v)[K]) {
 	} else if constexpr (K == 2) {
 		const float2 t = *reinterpret_cast<const float2 *>(p);
 		v[0] = t.x, v[1] = t.y;
+	} else if constexpr (K == 8) {
+		const float4 t = *reinterpret_cast<const float4 *>(p), u = *reinterpret_cast<const float4 *>(p + 4);
+		v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w, v[4] = u.x, v[5] = u.y, v[6] = u.z, v[7] = u.w;
 	} else {
 		v[0] = *p;
 	}
@@ -399,7 +497,10 @@ template <int K>
 __device__ __forceinline__ void store_vec(float *p, const float (&v)[K]) {
 	if constexpr (K == 4) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
 	else if constexpr (K == 2) *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1]);
-	else *p = v[0];
+	else if constexpr (K == 8) {
+		*reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
+		*reinterpret_cast<float4 *>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+	} else *p = v[0];
 }
 template <int K>
 __device__ __forceinline__ void load_bins(const float2 *p, float2 (&v)[K]) {

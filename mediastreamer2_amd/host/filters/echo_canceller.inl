@@ -242,15 +242,17 @@ void ec_prepare(MSFilter *f) { // (the hub locked by the caller where the filter
 	__atomic_store_n(&s->bypass_live, s->bypass_mode, __ATOMIC_RELAXED);
 	s->filterlength = (s->tail_length_ms * s->samplerate) / 1000;
 	s->framesize = mi_aec_framesize(s->framesize_at_8000, s->samplerate);
-	if (s->framesize != 64 && s->framesize != 128 && s->framesize != 256) {
-		// e.g. 96 kHz would need 512-sample frames: audio keeps flowing uncancelled rather than the process dying
-		ms_error("mi355x echo canceller: frame size %d (rate %d) is not built; the filter forwards both pins untouched",
+	if (s->framesize != 64 && s->framesize != 128 && s->framesize != 256 && s->framesize != 512) {
+		// 1024 samples or more (e.g. 48 kHz with a frame-size setting of 171 or more): audio keeps flowing uncancelled rather
+		// than the process dying
+		ms_error("mi355x echo canceller: frame size %d (rate %d) is not built (64, 128, 256 and 512 are); the filter forwards "
+		         "both pins untouched",
 		         s->framesize, s->samplerate);
 		s->unsupported = TRUE; // internal: the user's MS_ECHO_CANCELLER_SET_BYPASS_MODE value stays what it was
 		return;
 	}
 	s->unsupported = FALSE;
-	if (s->filterlength > 64 * s->framesize) { // the kernels hold at most 64 filter blocks (341 ms at 48 kHz, 512 ms at 8/16 kHz)
+	if (s->filterlength > 64 * s->framesize) { // the kernels hold at most 64 filter blocks (341 ms at 48 kHz, 512 ms at 8/16 kHz; 682 ms at 48 kHz with 512-sample frames)
 		ms_warning("mi355x echo canceller: tail of %d ms shortened to %d ms (64 blocks of %d samples)", s->tail_length_ms,
 		           64 * s->framesize * 1000 / s->samplerate, s->framesize);
 		s->filterlength = 64 * s->framesize;
