@@ -677,7 +677,6 @@ void server_disqualify(ServerLeg *leg);
 bool server_wants_out(ServerLeg *leg);
 Pool *server_pool(ServerLeg *leg);
 Pool *server_pool_of(ServerBank *b);
-void server_conf_walked(ServerBank *b, int c);
 void server_unfuse(MSFilter *mixer, bool keep_running);
 
 // the receiving side of an AudioStream as one batch (filters/recv_leg.inl): what the decoders, MSGenericPLC and MSAudioFlowControl need to know of it
@@ -704,6 +703,7 @@ void recv_flow_config(RecvLeg *leg, const MSAudioFlowControlConfig *cfg);
 #include "filters/mixer.inl"
 #include "filters/echo_canceller.inl"
 #include "filters/codec.inl"
+#include "filters/conf_bank.inl"
 #include "filters/leg_chain.inl"
 #include "filters/video.inl"
 #include "filters/server_leg.inl"

@@ -43,7 +43,6 @@
 
 constexpr int kLegRefOver = 3; // far-end ticks beyond the first that one flush carries per leg (a burst after a network hiccup)
 constexpr int kLegLightRounds = 8; // frames MSVolume (no AGC) can meter in one enqueue: kMaxRounds blocks of 10 ms in frames
-constexpr int kLegMeterRounds = 8; // rounds before the last of a flush whose meter state is read back (kLegLightRounds, kLegMaxChunks fit)
 // 10 ms chunks a conference member's result queue is sized for BESIDES a tick's bursts (LegBank::out_cap).  A running batch keeps one or two;
 // what a re-plumbed conference brings back (take_remainders) grows by up to one with every detach + attach -- the reference's mixer skips
 // the walk in which none of its pins delivers (audiomixer.c:244-286: a restarted canceller's first frame may not complete a chunk) and its
@@ -136,11 +135,9 @@ void bufferizer_put_samples(MSBufferizer *bz, const int16_t *x, int n) {
 }
 
 struct LegBank;
-struct FusedLeg {
+struct FusedLeg : ConfMember {
 	LegBank *bank;
-	int slot, pin;
-	uint32_t lv_from = 0; // MSMI355X_CHECK_LEVELS: the first read-back of the queues' levels (LegBank::lv_seq) that is this leg's -- an earlier one shows the slot before it was taken
-	MSFilter *rs, *ec, *vol, *mixer;
+	MSFilter *rs, *ec;
 	void *rs_data = nullptr, *ec_data = nullptr, *vol_data = nullptr; // the facades' states (f->data), known here so that a prefetch needs no cold load
 	int staged_mic = 0;  // 10 ms blocks staged since the last flush (launch rounds)
 	int framed_mic = 0;  // ... of which the framing below has already counted (a leg headed by MSSpeexEC frames as it stages)
@@ -153,10 +150,7 @@ struct FusedLeg {
 	int chan_chunks = 0; // the mixer channel's bufferizer: whole chunks waiting (f_out holds vol_rem + chan_chunks * ns)
 	int newchunks = 0;   // chunks MSVolume would have put on the mixer's queue in this flush
 	// MSVolume WITHOUT AGC (LegBank::light): the canceller's frames pass it one by one, the mixer channel holds samples
-	int lt_frames = 0;    // frames MSVolume meters in this enqueue
-	int new_samples = 0;  // samples it put on the mixer's queue since the mixer last looked
-	int chan_samples = 0; // the mixer channel's bufferizer, samples (what f_chan holds)
-	bool metered = false;
+	int lt_frames = 0;    // frames MSVolume meters in this enqueue (ConfMember::new_samples, chan_samples: what it put on the mixer's queue)
 	// MSVolume's echo limiter (msvolume.c:201-238): volsend reads the energy of its peer, volrecv -- which this leg METERS beside its
 	// chain (LegBank::vol_peer): the peer facade hands its blocks on untouched in the walk and stages a copy of each for the meter
 	MSFilter *eq = nullptr; // mic_equalizer between the leg's MSResample and MSSpeexEC (audiostream.c:1801): runs in the bank (LegBank::eq)
@@ -169,19 +163,14 @@ struct FusedLeg {
 	bool peer_metered = false;
 	std::atomic<bool> unfuse_wanted{false}; // (a leg without a mixer: set by a method on any thread under the hub's lock, honoured by the head's next process())
 	uint32_t far_tick = 0;      // ticker tick in which the far end was last taken (a bank without mixers leaves early on these)
+	inline bool delivered() const; // (below: a bank with AGC counts chunks, one without counts samples)
+	bool has_staged() const { return staged_mic > 0 || staged_ref > 0 || inject > 0 || pre_frames > 0; }
+	static void prefetch_meters(FusedLeg *const *legs, size_t s, size_t n) { // eight legs ahead: the leg; four: its MSVolume's state
+		if (!leg_prefetch_on()) return;
+		if (s + 8 < n) pf2(legs[s + 8], sizeof(FusedLeg));
+		if (s + 4 < n && legs[s + 4]) pf2(legs[s + 4]->vol_data, sizeof(VolumeData));
+	}
 };
-
-struct MixSlab { // one flush's conference mixes in pinned memory, referenced by the blocks handed downstream
-	std::atomic<int> state{0}; // 0 free, 1 a data block is alive on it, 2 its bank is gone (freed when the block goes)
-	size_t bytes = 0;
-	uint8_t *payload() { return reinterpret_cast<uint8_t *>(this) + 64; }
-	static MixSlab *of(void *payload) { return reinterpret_cast<MixSlab *>(static_cast<uint8_t *>(payload) - 64); }
-};
-static_assert(sizeof(MixSlab) <= 64, "slab header");
-void mix_slab_release(void *payload) { // db_freefn of the slab's data block (the last dupb of a flush was freed)
-	MixSlab *s = MixSlab::of(payload);
-	if (s->state.exchange(0, std::memory_order_acq_rel) == 2) mi_host_free(nullptr, s);
-}
 
 // MSSpeexEC's speaker-pin frames of one flush (one frame per microphone frame, speexec.c:261-284): cut from ONE host buffer per
 // bank and flush -- esballoc for the buffer, a dupb per frame pointing at its piece -- instead of an allocb per frame (two
@@ -198,39 +187,27 @@ void spk_slab_release(void *payload) {
 	if (s->state.exchange(0, std::memory_order_acq_rel) == 2) free(s);
 }
 
-int channel_flow_control_level(Channel *chan, int level, int threshold, uint64_t now); // mixer.inl
 void enc_take_codes(MSFilter *e, const uint8_t *codes, int n); // server_leg.inl
 bool is_g711_enc(const MSFilterDesc *d);
 bool is_forwarding_mixer(MSFilter *g, MSTicker *ticker); // recv_leg.inl
 void leg_speaker_frame(MSFilter *f, SpeexECState *s, FusedLeg *leg, size_t nbytes, bool immediate);
 void conf_unfuse(MSFilter *mixer, bool keep_running);
-void leg_conf_walked(LegBank *b, int c);
 void leg_far_walked(LegBank *b, FusedLeg *leg);
 
-struct LegBank : Pool {
+struct LegBank : ConfBank<FusedLeg> {
 	uint32_t in_rate, rate;
-	int F, flen, delay, mm, ns, in_len, den, nlegs;
+	int F, flen, delay, in_len, den;
 	int mic_cap, ref_cap, out_cap;
 	mi_resampler *rs = nullptr;
 	mi_aec *aec = nullptr;
 	mi_fifo *f_mic = nullptr, *f_ref = nullptr, *f_out = nullptr;
-	mi_volume *vol = nullptr;
-	mi_mixer *mix = nullptr;
 	int16_t *h_mic, *d_mic;     // [kMaxRounds][nlegs][in_len] / [nlegs][in_len]
 	uint8_t *h_gate, *d_gate;   // [kMaxRounds][nlegs] / [nlegs]
 	int16_t *h_ref, *d_ref;     // [nlegs][ns]: the first tick of far end a leg staged
 	int16_t *h_refx, *d_refx;   // [nlegs][kLegRefOver * ns]: what came beyond it (rare)
 	int32_t *h_cnt, *d_cnt;     // [3][nlegs]: far-end samples in h_ref, in h_refx, silence injected behind them
 	int32_t *d_zero;            // [nlegs] zeros: the canceller's launch appends no far end of its own
-	int16_t *d_mix, *d_scratch; // [capacity][mm][ns]; [nlegs][ns]
 	int32_t *h_lv, *d_lv;       // MSMI355X_CHECK_LEVELS: [3][nlegs]
-	mi_volume_state *h_vstate;  // pinned [nlegs]
-	// MSVolume records EVERY chunk's energy in its extrema (update_energy, msvolume.c:405-406): when a flush levels more than one
-	// chunk of a leg, the state behind each round but the last comes back too (kLegMeterRounds rows of [nlegs]; vhas: the leg had a
-	// chunk in that round)
-	mi_volume_state *h_vround = nullptr;
-	std::vector<uint8_t> vhas;
-	int vrounds = 0;
 	// the legs' echo-limiter peers (FusedLeg::peer), metered block by block as volrecv without AGC meters (msvolume.c:505-513) BEFORE the
 	// chain's MSVolume runs in the same enqueue -- volsend reads what volrecv's process() of the same tick left, as in the reference,
 	// where volrecv stands upstream of the canceller (audiostream.c:1812-1826).  Created when the first such leg joins.
@@ -251,42 +228,11 @@ struct LegBank : Pool {
 	std::vector<mi_volume_state> pstate;        // the peers' running state as of the last flush
 	int prounds = 0;                 // rounds of the launch that is out
 	int npeers = 0;
-	int16_t *h_copy;            // the mixes when every slab is still held downstream: emitted by copy
-	std::vector<MixSlab *> slabs;
-	MixSlab *cur = nullptr;     // the slab this flush downloads into (null: h_copy)
-	mblk_t *root = nullptr;     // its data block, alive from finish() to emitted()
-	std::vector<FusedLeg *> legs;
-	std::vector<uint8_t> conf_ready;
-	std::vector<int> lone; // the single contributor's pin of a conference that ticked with one, else -1
-	std::vector<uint8_t> flags;
-	std::vector<float> gains;
-	bool ctl_dirty = true;
-	// what a method set while the last walk's blocks were still waiting for the coming flush (Pool::work_waiting): live when that flush is
-	// through (flushed()).  vp_dirty / vs_dirty: 1 = goes to the device with the next enqueue, 2 = waits for flushed() first
-	std::vector<uint8_t> next_flags, next_conf;
-	std::vector<float> next_gains;
-	bool next_any = false;
-	std::vector<mi_volume_params> vparams;
-	std::vector<mi_volume_state> vstate;
-	std::vector<uint8_t> vp_dirty, vs_dirty;
 	// ... and in a conference with AGC the chunks MSVolume has already handed to the mixer's channel are levelled here only when the
 	// mixer takes them (volmix_kernel pops, meters and mixes): what a method sets must pass those by -- v_delay: chunks of the leg
 	// that were produced before the call and are still to be taken; the change goes to the device when it is down to zero
 	std::vector<int> v_delay;
-	bool v_dirty = false;
 	std::vector<std::pair<int, int>> drops; // (leg slot, chunks) the mixer channels' flow control discards this flush
-	std::vector<uint64_t> conf_time;        // ticker time of a conference's last tick (one per tick, whoever enqueues)
-	std::vector<uint32_t> walk_tick;        // ticker tick in which a conference's mixer was last walked
-	uint32_t walk_epoch = 0;
-	uint8_t *h_run, *d_run;                 // [capacity]: conferences that tick in this launch of the volume + mix kernel
-	bool staged_since = false;              // something was staged (or a conference joined) since the last enqueue
-	bool outstanding = false;               // an enqueue has not been waited for yet
-	// The staging rows and the mixes' slab are pinned host memory the device addresses itself: by default the launches read
-	// and write them where they lie (a few hundred bytes per leg, once) and the tick path makes no copy at all -- four
-	// launches and the meters' read-back.  MSMI355X_ZERO_COPY=0: staged through device buffers by copy launches (A/B).
-	bool zero_copy = true;
-	bool mixed = false, check_levels = false, lv_fresh = false;
-	uint32_t lv_seq = 0; // read-backs of the levels so far (FusedLeg::lv_from)
 	double trace_ms = 0;          // MSMI355X_TRACE_SLOW_MS: an enqueue that takes longer says where (stderr)
 	uint64_t tr[8] = {0};
 	std::vector<std::pair<const char *, uint64_t>> trc; // ... and call by call inside the device's half
@@ -301,14 +247,10 @@ struct LegBank : Pool {
 	void step(const char *what) {
 		if (trace_ms > 0) trc.emplace_back(what, trace_now());
 	}
-	uint64_t launches = 0;
 	std::vector<std::pair<MSQueue *, mblk_t *>> spk; // speaker-pin frames of this flush (MSSpeexEC pin 0: host audio), handed on in finish()
 	std::vector<SpkSlab *> spk_slabs;                // ... cut from one of these (a ring: a slab returns when its last frame is freed downstream)
 	SpkSlab *spk_cur = nullptr;
 	mblk_t *spk_root = nullptr;
-	int walked = 0;                                  // conferences whose mixer has run in this tick's graph walk
-	bool early = false, early_any = false;           // this tick's work was enqueued at the end of the walk (leg_conf_walked)
-	bool no_early = false;
 	// A bank WITHOUT mixers (plain): legs  MSResample -> MSSpeexEC -> MSVolume -> any other filter  -- the sending side of an
 	// AudioStream (audiostream.c:1798-1810) whose streams share a ticker.  One slot = one leg (mm = 1), owned by its MSVolume,
 	// which hands the levelled 10 ms chunks on as they come out of mi_volume_process_fifo_flags (up to kLegMaxChunks a flush).
@@ -324,18 +266,9 @@ struct LegBank : Pool {
 	uint8_t *h_codes = nullptr, *d_codes = nullptr; // [kLegMaxChunks][nlegs][chunk]: the encoded chunks of this flush
 	int32_t *h_elen = nullptr, *d_elen = nullptr;   // [kLegMaxChunks][nlegs]: chunk where the leg has a chunk in that round, else 0
 	int chunk = 0;                 // samples of a block MSVolume hands on: 10 ms with AGC, a canceller frame without
-	mi_volume *vol_id = nullptr;   // identity batch (gain 1, nothing enabled): volmix_kernel's volume half for the levelled queue
-	mi_fifo *f_chan = nullptr;     // the mixer channels' bufferizers
 	int16_t *d_lev = nullptr;      // [nlegs][F] a round's levelled frames
 	int32_t *h_fcnt = nullptr, *d_fcnt = nullptr; // [kLegLightRounds][nlegs]: F where the leg has a frame in that round, else 0
-	uint8_t *h_dgate = nullptr, *d_dgate = nullptr; // [nlegs]: the leg the channels' flow control drops samples of (rare)
-	std::vector<std::pair<int, int>> sdrops;      // (leg slot, samples) of those drops
 	std::vector<int> nout, nready; // chunks a leg's MSVolume completes in this flush / has ready to hand on
-	struct GainPatch {
-		float gain, target;
-		bool also_target;
-	};
-	std::vector<GainPatch> vpatch; // MS_VOLUME_SET_GAIN & co. on a fused leg: the two fields, set on the state as the device holds it
 	// A leg that joins the bank costs NO device call when its slot has never been used: every batch object is created with every
 	// stream at its start state (mi_aec_create / mi_fifo_create / mi_resampler_create / mi_volume_create end in their own reset), so
 	// only a slot that HAD a leg is reset; MSVolume's parameters and start state go up with the next enqueue, neighbours in one call,
@@ -350,7 +283,7 @@ struct LegBank : Pool {
 	static int out_cap_for(int ns, int F) { return frames_up(kLegHeldChunks * ns + kMaxRounds * 2 * F, F); }
 	LegBank(int cap_conf, uint32_t ir, uint32_t r, int frame, int filter_length, int delay_samples, int members, bool no_mixer = false, bool no_agc = false,
 	        bool with_eq = false, int law = -1)
-	    : in_rate(ir), rate(r), F(frame), flen(filter_length), delay(delay_samples), mm(members), plain(no_mixer), light(no_agc), enc_law(law) {
+	    : ConfBank(members), in_rate(ir), rate(r), F(frame), flen(filter_length), delay(delay_samples), plain(no_mixer), light(no_agc), enc_law(law) {
 		Building b(this, cap_conf);
 		ns = (int)rate / 100;
 		chunk = light ? F : ns;
@@ -406,39 +339,19 @@ struct LegBank : Pool {
 		d_lv = devmem<int32_t>(4 * L);
 		h_vstate = pinned<mi_volume_state>(L);
 		h_vround = pinned<mi_volume_state>((size_t)kLegMeterRounds * L);
-		vhas.assign((size_t)kLegMeterRounds * L, 0);
 		h_copy = pinned<int16_t>((plain ? kLegMaxChunks : 1) * L * ns);
 		nout.assign(L, 0);
 		nready.assign(L, 0);
 		h_run = pinned<uint8_t>((size_t)capacity);
 		d_run = devmem<uint8_t>((size_t)capacity);
-		conf_time.assign((size_t)capacity, (uint64_t)-1);
-		walk_tick.assign((size_t)capacity, 0);
 		if (!failed) MI_MUST(mi_memset(hub->ctx, d_zero, 0, L * 4));
-		legs.assign(L, nullptr);
-		conf_ready.assign((size_t)capacity, 0);
-		lone.assign((size_t)capacity, -1);
-		flags.assign(L, 0);
-		gains.assign(L, 1.0f);
-		next_flags.assign(L, 0);
-		next_gains.assign(L, 1.0f);
-		next_conf.assign((size_t)capacity, 0);
-		mi_volume_params p;
-		mi_volume_default_params(&p);
-		vparams.assign(L, p);
-		vstate.resize(L);
-		vp_dirty.assign(L, 0);
-		vs_dirty.assign(L, 0);
+		init_conf();
 		v_delay.assign(L, 0);
-		vpatch.assign(L, GainPatch{1.f, 1.f, false});
 		used.assign(L, 0);
-		vparams0 = p;
+		vparams0 = vparams[0];
 		memset(&vstate0, 0, sizeof(vstate0));
 		if (!failed) MI_MUST(mi_volume_get_state(vol, 0, 1, &vstate0));
-		check_levels = getenv("MSMI355X_CHECK_LEVELS") != nullptr;
 		if (const char *e = getenv("MSMI355X_TRACE_SLOW_MS")) trace_ms = atof(e);
-		zero_copy = zero_copy_rows();
-		no_early = getenv("MSMI355X_NO_EARLY_LAUNCH") != nullptr; // A/B switch: everything leaves at the flush
 		// the first ticks' slabs are made here (the attaching thread opens the bank), not by those ticks: two of each -- a flush's blocks
 		// are still held downstream when the next flush needs its slab
 		for (int i = 0; i < 2 && !failed && enc_law < 0; ++i) {
@@ -449,12 +362,10 @@ struct LegBank : Pool {
 		for (int i = 0; i < 2 && !failed; ++i) (void)new_spk_slab();
 	}
 	~LegBank() override {
-		if (root) freeb(root);
 		for (auto &qm : spk) freemsg(qm.second);
 		if (spk_root) freeb(spk_root);
 		for (SpkSlab *s : spk_slabs)
 			if (s->state.exchange(2, std::memory_order_acq_rel) == 0) free(s);
-		for (FusedLeg *l : legs) delete l;
 		if (hub->ctx) mi_ctx_sync(hub->ctx);
 		if (mix) mi_mixer_destroy(mix);
 		if (vol) mi_volume_destroy(vol);
@@ -466,8 +377,6 @@ struct LegBank : Pool {
 			if (f) mi_fifo_destroy(f);
 		if (aec) mi_aec_destroy(aec);
 		if (rs) mi_resampler_destroy(rs);
-		for (MixSlab *s : slabs) // a slab whose blocks are still held downstream outlives the bank: its last block frees it
-			if (s->state.exchange(2, std::memory_order_acq_rel) == 0) mi_host_free(hub->ctx, s);
 	}
 	// a frame of `nbytes` for the speaker pin: a piece of this flush's slab (NULL: no slab to be had, the caller allocates)
 	mblk_t *spk_frame(size_t nbytes) {
@@ -505,18 +414,7 @@ struct LegBank : Pool {
 		spk_root = nullptr;
 		spk_cur = nullptr;
 	}
-	MixSlab *free_slab() {
-		for (MixSlab *s : slabs)
-			if (s->state.load(std::memory_order_acquire) == 0) return s;
-		if (slabs.size() >= 4 || failed) return nullptr;
-		const size_t bytes = (size_t)(plain ? kLegMaxChunks : 1) * nlegs * ns * 2;
-		void *p = mi_host_alloc(hub->ctx, 64 + bytes);
-		if (!p) return nullptr;
-		MixSlab *s = new (p) MixSlab();
-		s->bytes = bytes;
-		slabs.push_back(s);
-		return s;
-	}
+	size_t slab_bytes() const override { return (size_t)(plain ? kLegMaxChunks : 1) * nlegs * ns * 2; }
 
 	// legs [s0, s0 + count) are about to be taken: their per-slot objects at the start state (see `used`)
 	bool start_slots(int s0, int count) {
@@ -555,51 +453,13 @@ struct LegBank : Pool {
 		return nfr;
 	}
 
-	// ---- one tick of a conference on counts: mixer_process (audiomixer.c:288-346) with the census of mixer_check_bypass
-	// (:244-286) and the channels' flow control (:92-111), deciding from what MSVolume would have put on the pins' queues
-	void conf_tick(int c, uint64_t now) {
-		MSFilter *mx = owner[(size_t)c];
-		MixerState *s = (MixerState *)mx->data;
-		conf_ready[(size_t)c] = 0;
-		lone[(size_t)c] = -1;
-		int count = 0, who = -1;
+	// the channels' half of a conference's tick with AGC: whole 10 ms chunks wait in the result queue and are levelled when the mixer
+	// takes them (without AGC the shared, sample-counted step)
+	void channels_tick(int c, MixerState *s, uint64_t now) override {
+		if (light) return ConfBank::channels_tick(c, s, now);
 		for (int pin = 0; pin < mm; ++pin) {
 			FusedLeg *leg = legs[(size_t)(c * mm + pin)];
 			if (!leg) continue;
-			uint64_t &seen = s->channels[pin].last_activity;
-			bool contributes;
-			if (light ? leg->new_samples > 0 : leg->newchunks > 0) {
-				seen = now;
-				contributes = true;
-			} else if (seen == (uint64_t)-1) {
-				seen = now; // first look at a silent pin only starts its clock
-				contributes = false;
-			} else {
-				contributes = now - seen < BYPASS_MODE_TIMEOUT;
-			}
-			if (contributes) ++count, who = pin;
-		}
-		if (count == 0) return; // nobody has delivered for a second: nothing leaves (and nothing was queued)
-		if ((count == 1) != (s->bypass_mode != FALSE))
-			ms_message("mi355x mixer %p: %s", (void *)mx, count == 1 ? "a single contributor (mixed on the device all the same)" : "two or more contributors");
-		s->bypass_mode = count == 1;
-		for (int pin = 0; pin < mm; ++pin) {
-			FusedLeg *leg = legs[(size_t)(c * mm + pin)];
-			if (!leg) continue;
-			Channel *chan = &s->channels[pin];
-			if (light) { // the channel's bufferizer holds the levelled frames, the tick reads 10 ms of them or nothing (:78-90)
-				leg->chan_samples += leg->new_samples;
-				leg->new_samples = 0;
-				if (leg->chan_samples >= ns) leg->chan_samples -= ns;
-				const int skip = channel_flow_control_level(chan, leg->chan_samples * 2, s->skip_threshold, now);
-				if (skip > 0) {
-					const int k = std::min(leg->chan_samples, skip / 2);
-					ms_warning("mi355x mixer: pin %i kept more than two ticks queued for 5 s; %i samples discarded", pin, k);
-					leg->chan_samples -= k;
-					if (k > 0) sdrops.push_back({leg->slot, k});
-				}
-				continue;
-			}
 			leg->chan_chunks += leg->newchunks; // ms_bufferizer_put_from_queue, channel_process_in :78-90
 			leg->newchunks = 0;
 			if (leg->chan_chunks > 0) { // ... and the read of one tick (the device pops it: the queue holds a whole chunk)
@@ -607,7 +467,7 @@ struct LegBank : Pool {
 				leg->metered = true;
 				if (v_delay[(size_t)leg->slot] > 0) --v_delay[(size_t)leg->slot];
 			}
-			const int skip = channel_flow_control_level(chan, leg->chan_chunks * ns * 2, s->skip_threshold, now);
+			const int skip = channel_flow_control_level(&s->channels[pin], leg->chan_chunks * ns * 2, s->skip_threshold, now);
 			if (skip > 0) {
 				const int k = std::min(leg->chan_chunks, skip / (ns * 2));
 				ms_warning("mi355x mixer: pin %i kept more than two ticks queued for 5 s; %i ms discarded", pin, k * 10);
@@ -615,8 +475,6 @@ struct LegBank : Pool {
 				if (k > 0) drops.push_back({leg->slot, k});
 			}
 		}
-		conf_ready[(size_t)c] = 1;
-		lone[(size_t)c] = count == 1 ? who : -1;
 	}
 
 	// the device's half up to the cleaned frames, in the order the reference's process() works: far end queued, then the frames
@@ -780,35 +638,6 @@ struct LegBank : Pool {
 		return d_takegate;
 	}
 	uint8_t *d_takegate = nullptr;
-	// A slot's owner leaves while the bank's work for the coming tick is already out (it left at the end of the last graph walk):
-	// the reference's filters would have handed that tick's audio on in the walk itself, so it goes out now -- the speaker frames
-	// of every leg (LegBank::finish), the owner's own mix or chunks; the others' follow with the hub's flush as usual.
-	// A conference with a SINGLE contributor is in the reference's bypass mode (audiomixer.c:219-286): that pin's blocks go to the other
-	// outputs AS THEY ARE -- no input gain, no regard for MS_AUDIO_MIXER_SET_ACTIVE (mixer_dispatch_output never looks at the channel).
-	// The batch mixes such a conference all the same, with that pin's controls set to "active, gain 1" for as long as it is alone:
-	// the sum of one is the block itself (but for a sample of -32768, which the sum saturates to -32767: the stated exception).
-	std::vector<int> lone_ctl;           // per conference: the pin whose controls are overridden right now, -1 = none
-	std::vector<uint8_t> eff_flags;
-	std::vector<float> eff_gains;
-	void push_controls() {
-		if (!mix) return;
-		bool moved = false;
-		if (lone_ctl.size() != lone.size()) lone_ctl.assign(lone.size(), -1), moved = true;
-		for (size_t c = 0; c < lone.size(); ++c) {
-			if (!owner[c] && lone_ctl[c] >= 0) lone_ctl[c] = -1, moved = true; // (the slot was given up)
-			if (owner[c] && conf_ready[c] && lone_ctl[c] != lone[c]) lone_ctl[c] = lone[c], moved = true; // (a conference that does not tick keeps what it had)
-		}
-		if (!ctl_dirty && !moved) return;
-		eff_flags = flags, eff_gains = gains;
-		for (size_t c = 0; c < lone_ctl.size(); ++c)
-			if (lone_ctl[c] >= 0) {
-				const size_t at = c * (size_t)mm + (size_t)lone_ctl[c];
-				eff_flags[at] |= MI_MIX_ACTIVE;
-				eff_gains[at] = 1.0f;
-			}
-		MI_MUST(mi_mixer_set_controls(mix, eff_flags.data(), eff_gains.data()));
-		ctl_dirty = false;
-	}
 	bool want_peers() { // (hub locked) the meter batch and its rows, on first use
 		if (vol_peer) return true;
 		if (failed) return false;
@@ -878,22 +707,11 @@ struct LegBank : Pool {
 		}
 		prounds = 0;
 	}
-	// a graph is being detached between two ticks (deliver_*_in_scope): rows staged in the last walk whose launches have not left --
-	// a bank without early launch, a conference that joined the bank mid-walk -- leave now, as the coming flush would send them
-	// (the walks are over and the ticker's clock reads what that flush would read): the tick in flight includes them
-	void launch_staged() {
-		if (failed || !staged_since || !hub->ticker) return;
-		const bool more = enqueue_at(hub_time(hub));
-		early_any = early ? (early_any || more) : more;
-		early = true;
-	}
-	void deliver_in_flight(MSFilter *owner_filter, int slot) {
-		if (failed || (!outstanding && !early)) return;
-		sync_stream();
-		if (failed) return;
-		outstanding = false;
-		// (this may be the APPLICATION's thread -- a postprocess, msticker.c:221 -- while the ticker walks the bank's other graphs: only the
-		// owner's graph is handed anything here, the other legs' speaker frames follow with the ticker's own flush; TickerHub::scope)
+	// The two banks differ here, since when is unknown: this one narrows the hub's scope to the owner's graph, ServerBank does not.
+	// (This may be the APPLICATION's thread -- a postprocess, msticker.c:221 -- while the ticker walks the bank's other graphs: only the
+	// owner's graph is handed anything here -- its mix or chunks, its legs' speaker frames (finish) --, the other legs' speaker frames
+	// follow with the ticker's own flush; TickerHub::scope)
+	void deliver_now(MSFilter *owner_filter, int slot) override {
 		const std::unordered_set<MSFilter *> *outer = hub->scope;
 		std::unordered_set<MSFilter *> own;
 		if (!outer) {
@@ -904,22 +722,8 @@ struct LegBank : Pool {
 		emit(owner_filter, slot);
 		hub->scope = outer;
 	}
-	// vstate as the device holds it NOW (a leg is about to leave with its MSVolume's running state): launches that are out and not
-	// waited for yet are waited for, their read-back taken
-	void settle_meters() {
-		if (!outstanding && !early) return;
-		if (failed) return;
-		sync_stream();
-		if (failed || !mixed) return;
-		for (size_t s = 0; s < (size_t)nlegs; ++s)
-			if (legs[s] && !vs_dirty[s]) vstate[s] = h_vstate[s];
-	}
-	// the meters behind a levelling round that is not the flush's last (read back with the round's results: finish() records them)
-	void meter_round(size_t UL) {
-		if (vrounds >= kLegMeterRounds || failed) return;
-		MI_MUST(mi_volume_get_state_async(vol, 0, (int)UL, h_vround + (size_t)vrounds * nlegs));
-		++vrounds;
-	}
+	// The two banks differ here, since when is unknown: this one takes the read-back only when a launch levelled something, ServerBank always.
+	bool meters_came_back() const override { return mixed; }
 	bool enqueue_plain(bool any_ref, bool any_refx, bool any_inj, int rounds) {
 		mi_ctx *ctx = hub->ctx;
 		const size_t L = (size_t)nlegs, UL = (size_t)hi;
@@ -975,19 +779,7 @@ struct LegBank : Pool {
 		return any;
 	}
 
-	bool enqueue() override {
-		bool any = false;
-		const bool was_early = early;
-		if (early) { // already out since the end of the last graph walk
-			early = false;
-			any = early_any;
-		}
-		// (what was staged after an early enqueue -- a conference that joined the bank later in that walk -- goes out now)
-		if (!was_early || staged_since) any |= enqueue_at(hub_time(hub));
-		outstanding = false; // the hub waits for the stream right behind this
-		return any;
-	}
-	bool enqueue_at(uint64_t now) {
+	bool enqueue_at(uint64_t now) override {
 		mi_ctx *ctx = hub->ctx;
 		const size_t L = (size_t)nlegs, UL = (size_t)hi * mm; // legs of the conference slots ever handed out
 		mark(0);
@@ -1112,14 +904,7 @@ struct LegBank : Pool {
 			if (!zero_copy) MI_MUST(mi_copy_h2d_pinned(ctx, d_run, h_run, (size_t)capacity));
 			MI_MUST(mi_mixer_process_volume_fifo_flags(mix, light ? vol_id : vol, 0, light ? f_chan : f_out, zero_copy ? host_rows : d_mix, MI_VOLMIX_DRY_SKIPS,
 			                                           zero_copy ? h_run : d_run));
-			for (const auto &dk : sdrops) { // samples the channels' flow control discards (rare: a pin that kept two ticks queued for 5 s)
-				memset(h_dgate, 0, L);
-				h_dgate[(size_t)dk.first] = 1;
-				if (!zero_copy) MI_MUST(mi_copy_h2d_pinned(ctx, d_dgate, h_dgate, L));
-				for (int left = dk.second; left > 0; left -= std::min(left, ns))
-					MI_MUST(mi_fifo_pop(f_chan, std::min(left, ns), d_scratch, ns, nullptr, zero_copy ? h_dgate : d_dgate, 0));
-				sync_stream(); // (the gate row is rewritten for the next one)
-			}
+			discard_sdrops();
 			mark(4);
 			++launches;
 			for (const auto &dk : drops) // chunks the channels' flow control discards: metered (MSVolume saw them), never mixed
@@ -1196,31 +981,8 @@ struct LegBank : Pool {
 		finish_peers();
 		check_overflows();
 		if (mixed) {
-			const bool pfon = leg_prefetch_on();
-			for (size_t s = 0; s < UL; ++s) {
-				FusedLeg *leg = legs[s];
-				if (pfon && s + 8 < UL) pf2(legs[s + 8], sizeof(FusedLeg));
-				if (pfon && s + 4 < UL && legs[s + 4]) pf2(legs[s + 4]->vol_data, sizeof(VolumeData));
-				if (!leg) continue;
-				vstate[s] = h_vstate[s];
-				if (leg->metered && hub->ticker) { // update_energy's extremum records, msvolume.c:405-406: one per chunk, in order
-					VolumeData *vd = (VolumeData *)leg->vol->data;
-					for (int r = 0; r < vrounds; ++r)
-						if (vhas[(size_t)r * L + s]) {
-							vd->max.record_max(hub_time(hub), h_vround[(size_t)r * L + s].energy);
-							vd->min.record_min(hub_time(hub), h_vround[(size_t)r * L + s].energy);
-						}
-					vd->max.record_max(hub_time(hub), vstate[s].energy);
-					vd->min.record_min(hub_time(hub), vstate[s].energy);
-				}
-				leg->metered = false;
-			}
-			std::fill(vhas.begin(), vhas.end(), 0);
-			vrounds = 0;
-			if (cur) {
-				cur->state.store(1, std::memory_order_release);
-				root = esballoc(cur->payload(), cur->bytes, 0, mix_slab_release);
-			}
+			read_meters();
+			if (cur) slab_out();
 			mixed = false;
 			if (plain)
 				for (size_t s = 0; s < UL; ++s) nready[s] = nout[s], nout[s] = 0;
@@ -1252,19 +1014,8 @@ struct LegBank : Pool {
 			return;
 		}
 		if (plain) { // the leg's MSVolume hands its levelled chunks on (volume_process :500-502)
-			const uint8_t *base = root ? cur->payload() : reinterpret_cast<const uint8_t *>(h_copy);
 			for (int r = 0; r < nready[(size_t)c]; ++r) {
-				uint8_t *row = const_cast<uint8_t *>(base) + (((size_t)r * nlegs + (size_t)c) * chunk) * 2;
-				mblk_t *om;
-				if (root) {
-					om = dupb(root);
-					om->b_rptr = row;
-					om->b_wptr = row + (size_t)chunk * 2;
-				} else {
-					om = allocb((size_t)chunk * 2, 0);
-					memcpy(om->b_wptr, row, (size_t)chunk * 2);
-					om->b_wptr += chunk * 2;
-				}
+				mblk_t *om = row_block(((size_t)r * nlegs + (size_t)c) * chunk, chunk);
 				if (f->outputs[0]) ms_queue_put(f->outputs[0], om);
 				else freemsg(om);
 			}
@@ -1274,28 +1025,11 @@ struct LegBank : Pool {
 		if (!conf_ready[(size_t)c]) return;
 		conf_ready[(size_t)c] = 0;
 		MixerState *s = (MixerState *)f->data;
-		const uint8_t *base = root ? cur->payload() : reinterpret_cast<const uint8_t *>(h_copy);
 		for (int pin = 0; pin < mm && pin < MIXER_MAX_CHANNELS; ++pin) {
 			MSQueue *q = f->outputs[pin];
 			if (!q || !s->channels[pin].output_enabled || pin == lone[(size_t)c]) continue;
-			uint8_t *row = const_cast<uint8_t *>(base) + ((size_t)(c * mm + pin) * ns) * 2;
-			mblk_t *om;
-			if (root) { // the row as it lies in the slab
-				om = dupb(root);
-				om->b_rptr = row;
-				om->b_wptr = row + (size_t)ns * 2;
-			} else {
-				om = allocb((size_t)ns * 2, 0);
-				memcpy(om->b_wptr, row, (size_t)ns * 2);
-				om->b_wptr += ns * 2;
-			}
-			ms_queue_put(q, om);
+			ms_queue_put(q, row_block((size_t)(c * mm + pin) * ns, ns));
 		}
-	}
-	void emitted() override { // the flush's own reference: the slab returns to the ring when the last block downstream is freed
-		if (root) freeb(root);
-		root = nullptr;
-		cur = nullptr;
 	}
 	void flushed() override { // the coming flush is through: what the methods set while its blocks were waiting goes live
 		const size_t UL = (size_t)hi * mm;
@@ -1311,16 +1045,7 @@ struct LegBank : Pool {
 			v_delay[s] = chunks_waiting(s);
 			v_dirty = true;
 		}
-		if (!next_any) return;
-		for (int c = 0; c < hi; ++c) {
-			if (!next_conf[(size_t)c]) continue;
-			const size_t at = (size_t)c * mm;
-			std::copy(next_flags.begin() + at, next_flags.begin() + at + mm, flags.begin() + at);
-			std::copy(next_gains.begin() + at, next_gains.begin() + at + mm, gains.begin() + at);
-			next_conf[(size_t)c] = 0;
-			ctl_dirty = true;
-		}
-		next_any = false;
+		controls_flushed();
 	}
 	// chunks leg s's MSVolume has produced that the mixer has not taken yet (a conference with AGC: they are levelled when taken)
 	int chunks_waiting(size_t s) const {
@@ -1328,6 +1053,7 @@ struct LegBank : Pool {
 		return (leg && !plain && !light) ? leg->chan_chunks + leg->newchunks : 0;
 	}
 };
+inline bool FusedLeg::delivered() const { return bank->light ? new_samples > 0 : newchunks > 0; }
 
 // one speaker frame per microphone frame, on counts: ec_emit_speaker_frame with the delay line on the device
 void leg_speaker_frame(MSFilter *f, SpeexECState *s, FusedLeg *leg, size_t nbytes, bool immediate) {
@@ -1374,58 +1100,19 @@ void leg_speaker_frame(MSFilter *f, SpeexECState *s, FusedLeg *leg, size_t nbyte
 	hand_on(m);
 }
 
-// A graph is being detached (facade_detached, filters.cpp): its fused conferences' and legs' tick in flight is waited for and handed
-// on -- speaker frames, mixes / chunks -- before any of its facades lets go (the scoped flush then carries those blocks on through
-// whatever facades of the graph sit behind: an encoder, a resampler)
-void deliver_fused_in_scope(TickerHub &h) {
-	for (Pool *p : h.pools) {
-		if (p->key.compare(0, 3, "leg") != 0) continue;
-		LegBank *b = static_cast<LegBank *>(p);
-		// (a launch is the whole bank's: it leaves from here -- possibly the application's thread, in the middle of the ticker's walk of the bank's
-		// OTHER graphs, with only part of them staged -- only when the detaching graph itself staged something that has not left; between two ticks
-		// its work is out already and there is nothing to launch)
-		bool ours = false;
-		for (int s = 0; s < b->hi && !ours; ++s) {
-			if (!b->owner[(size_t)s] || !h.scope->count(b->owner[(size_t)s])) continue;
-			for (int pin = 0; pin < b->mm && !ours; ++pin)
-				if (const FusedLeg *leg = b->legs[(size_t)(s * b->mm + pin)]) ours = leg->staged_mic > 0 || leg->staged_ref > 0 || leg->inject > 0 || leg->pre_frames > 0;
-		}
-		if (ours) b->launch_staged();
-		for (int s = 0; s < b->hi; ++s)
-			if (b->owner[(size_t)s] && h.scope->count(b->owner[(size_t)s])) b->deliver_in_flight(b->owner[(size_t)s], s);
-	}
-}
+void deliver_fused_in_scope(TickerHub &h) { deliver_banks_in_scope<LegBank>(h, "leg"); }
 
-// Every conference of the bank has been walked in this tick (its mixer runs behind all of its legs in the ticker's
-// depth-first order, msticker.c:261-282, so everything the tick will stage IS staged): the bank's uploads and launches go
-// out NOW, at the end of the graph walk, instead of at the start of the next tick -- the device works through the idle
-// part of the interval and the next tick's flush finds the results waiting.  Same results, same one tick of latency; the
-// launches just leave the tick's critical path.  (A tick in which some mixer did not run falls back to the flush.)
 double leg_trace_ms(LegBank *b) { return b->trace_ms; }
 uint64_t leg_trace_now() { return LegBank::trace_now(); }
-void leg_conf_walked(LegBank *b, int c) {
-	if (b->no_early || b->failed || b->early || !b->hub->ticker) return;
-	const uint32_t tick = b->hub->ticker->ticks;
-	if (b->walk_epoch != tick) b->walk_epoch = tick, b->walked = 0;
-	if (b->walk_tick[(size_t)c] == tick) return;
-	b->walk_tick[(size_t)c] = tick;
-	if (++b->walked < b->in_use) return;
-	b->early_any = b->enqueue_at(hub_time(b->hub) + (uint64_t)b->hub->ticker->interval); // the mixers' clock reads what the flush would
-	b->early = true;
-}
+void conf_walked(LegBank *b, int c) { b->conf_walked(c); } // (mixer.inl, which knows the banks by name only)
 
 // A bank without mixers has no filter that is walked behind all of a leg's facades; its legs' cancellers are (MSSpeexEC runs
 // when both the resampler and the far end have, msticker.c:230-242): once every leg of the bank has taken its far end in this
 // tick the bank's work leaves, as above.  (A tick in which some far end is late falls back to the flush.)
 void leg_far_walked(LegBank *b, FusedLeg *leg) {
-	if (b->no_early || b->failed || b->early || !b->hub->ticker) return;
-	const uint32_t tick = b->hub->ticker->ticks;
-	if (b->walk_epoch != tick) b->walk_epoch = tick, b->walked = 0;
-	if (leg->far_tick == tick) return;
-	leg->far_tick = tick;
-	if (++b->walked < b->in_use) return;
-	b->early_any = b->enqueue_at(hub_time(b->hub) + (uint64_t)b->hub->ticker->interval);
-	b->early = true;
+	if (!b->walk_begins() || leg->far_tick == b->hub->ticker->ticks) return;
+	leg->far_tick = b->hub->ticker->ticks;
+	b->walk_counted();
 }
 
 // ---- the facades' fused halves -----------------------------------------------------------------------------------------
@@ -2302,39 +1989,14 @@ bool leg_has_resampler(FusedLeg *leg) { return leg && leg->rs != nullptr; }
 
 Pool *leg_pool(FusedLeg *leg) { return leg->bank; }
 Pool *leg_pool_of(LegBank *b) { return b; }
-// MS_AUDIO_MIXER_SET_INPUT_GAIN / SET_ACTIVE / ENABLE_OUTPUT on a fused conference (hub locked): the bank's control rows
-void leg_push_mixer_controls(MSFilter *f, MixerState *s, bool from_method) {
-	LegBank *b = s->fbank;
-	const bool later = from_method && b->work_waiting();
-	std::vector<uint8_t> &fl_row = later ? b->next_flags : b->flags;
-	std::vector<float> &g_row = later ? b->next_gains : b->gains;
-	for (int pin = 0; pin < b->mm; ++pin) {
-		const size_t at = (size_t)(s->fconf * b->mm + pin);
-		uint8_t fl = 0;
-		if (f->inputs[pin] && b->legs[at]) fl |= MI_MIX_LINKED;
-		if (s->channels[pin].active) fl |= MI_MIX_ACTIVE;
-		if (f->outputs[pin] && s->channels[pin].output_enabled) fl |= MI_MIX_OUTPUT;
-		fl_row[at] = fl;
-		g_row[at] = s->channels[pin].gain;
-	}
-	if (later) b->next_conf[(size_t)s->fconf] = 1, b->next_any = true;
-	else b->next_conf[(size_t)s->fconf] = 0, b->ctl_dirty = true;
-}
+void conf_push_mixer_controls(LegBank *b, MSFilter *f, MixerState *s, bool from_method) { b->push_mixer_controls(f, s, s->fconf, from_method); }
 mi_volume_state *leg_vstate(FusedLeg *leg) { return &leg->bank->vstate[(size_t)leg->slot]; }
 // MS_VOLUME_* methods on a fused leg's MSVolume (hub locked): parameters / running state for the next flush
 void leg_push_volume(FusedLeg *leg, const mi_volume_params *p, const float *gain, const float *target) {
 	LegBank *b = leg->bank;
 	const size_t s = (size_t)leg->slot;
-	const uint8_t when = b->work_waiting() ? 2 : 1; // (2: behind the coming flush, LegBank::flushed)
-	if (when == 1) b->v_delay[s] = b->chunks_waiting(s);
-	b->vparams[s] = *p;
-	b->vparams[s].peer = leg->peer ? MI_VOLUME_PEER_EXTERNAL : -1;
-	b->vp_dirty[s] = when;
-	if (gain) {
-		b->vpatch[s] = {*gain, target ? *target : 0.f, target != nullptr};
-		b->vs_dirty[s] = when;
-	}
-	b->v_dirty = true;
+	// (a change that goes with the next enqueue passes the chunks produced before the call by: v_delay; one behind the coming flush: LegBank::flushed)
+	if (b->push_volume(s, p, leg->peer ? MI_VOLUME_PEER_EXTERNAL : -1, gain, target) == 1) b->v_delay[s] = b->chunks_waiting(s);
 }
 mi_aec *leg_canceller(FusedLeg *leg, int *slot) {
 	*slot = leg->slot;

@@ -5,7 +5,6 @@
 // ======================================================================= mixer
 constexpr int MIXER_MAX_CHANNELS = MI_MIXER_MAX_CHANNELS; // audiomixer.c:29
 Pool *leg_pool_of(LegBank *b);                            // leg_chain.inl
-void leg_conf_walked(LegBank *b, int c);
 double leg_trace_ms(LegBank *b);
 uint64_t leg_trace_now();
 constexpr uint64_t BYPASS_MODE_TIMEOUT = 1000;            // audiomixer.c:31
@@ -140,8 +139,11 @@ struct MixerState { // audiomixer.c:132-143
 	bool first_walk;    // the walk right after an attach is still to come (see mixer_process)
 	bool prepared, acquire_failed; // preprocess has sized the tick; a bank slot could not be had
 };
-void leg_push_mixer_controls(MSFilter *f, MixerState *s, bool from_method); // leg_chain.inl
-void server_push_mixer_controls(MSFilter *f, MixerState *s, bool from_method); // server_leg.inl
+// ConfBank::conf_walked / push_mixer_controls (conf_bank.inl) for either kind of bank, which this file knows by name only
+void conf_walked(LegBank *b, int c);
+void conf_walked(ServerBank *b, int c);
+void conf_push_mixer_controls(LegBank *b, MSFilter *f, MixerState *s, bool from_method);
+void conf_push_mixer_controls(ServerBank *b, MSFilter *f, MixerState *s, bool from_method);
 
 void mixer_release_held(MSFilter *f, MixerState *s, bool deliver) {
 	for (auto &pm : *s->held) {
@@ -185,11 +187,11 @@ bool_t has_single_output(MSFilter *f, MixerState *s) { // audiomixer.c:167-176
 // from_method: set by a method on a running filter -- live behind the coming flush (MixerPool::next_*); otherwise (attach) at once
 void mixer_push_controls(MSFilter *f, MixerState *s, bool from_method = false) {
 	if (s->fbank) {
-		leg_push_mixer_controls(f, s, from_method);
+		conf_push_mixer_controls(s->fbank, f, s, from_method);
 		return;
 	}
 	if (s->sbank) {
-		server_push_mixer_controls(f, s, from_method);
+		conf_push_mixer_controls(s->sbank, f, s, from_method);
 		return;
 	}
 	if (!s->pool) return;
@@ -223,7 +225,7 @@ void mixer_preprocess(MSFilter *f) { // audiomixer.c:178-200
 	graph_preprocessed(f);
 }
 // running: the conference left a fused batch while attached -- no preprocess in the reference's terms: the channels' clocks (census,
-// flow control) and the bypass state run on, they are the very fields the batch kept (LegBank / ServerBank::conf_tick)
+// flow control) and the bypass state run on, they are the very fields the batch kept (ConfBank::conf_tick)
 void mixer_prepare(MSFilter *f, bool running) { // (running: the hub locked by the caller; at an attach the filter is the attaching thread's alone)
 	MixerState *s = (MixerState *)f->data;
 	s->bytespertick = (2 * s->nchannels * s->rate * f->ticker->interval) / 1000;
@@ -431,17 +433,17 @@ void mixer_process(MSFilter *f) { // audiomixer.c:288-346
 	if (s->sbank) { // a conference of remote members: as below, on its own kind of bank
 		mixer_release_held(f, s, true);
 		request_flush(f);
-		server_conf_walked(s->sbank, s->sconf);
+		conf_walked(s->sbank, s->sconf);
 		ms_filter_unlock(f);
 		return;
 	}
 	if (s->fbank) { // fused: the conference ticks inside the hub's flush; a pump keeps that flush coming every tick
-		// (no census here: what the members staged in THIS walk meets the mixer in LegBank::conf_tick, whose three cases are
+		// (no census here: what the members staged in THIS walk meets the mixer in ConfBank::conf_tick, whose three cases are
 		// mixer_check_bypass's, audiomixer.c:244-286 -- a pin's clock starts at its first look there, without counting yet)
 		mixer_release_held(f, s, true);
 		request_flush(f);
 		const uint64_t tr2 = trace_ms > 0 ? leg_trace_now() : 0;
-		leg_conf_walked(s->fbank, s->fconf); // the last conference of the bank to be walked sends the bank's work to the device right away
+		conf_walked(s->fbank, s->fconf); // the last conference of the bank to be walked sends the bank's work to the device right away
 		ms_filter_unlock(f);
 		if (trace_ms > 0) {
 			const uint64_t tr3 = leg_trace_now();

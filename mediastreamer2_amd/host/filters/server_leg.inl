@@ -21,9 +21,9 @@
 //     (mi_g711_encode on the mixes where they lie): 80 bytes of G.711 per member and tick come back instead of 160 bytes of PCM,
 //     and the encoder facade only packs them to its ptime (alaw.c:56-90: the codes of two ticks make a 20 ms packet; encoding is
 //     sample by sample, so the packet is the one the facade would have made from the PCM);  any other pin gets its PCM block
-//     from a pinned slab, as LegBank's do;
+//     from a pinned slab (ConfBank::row_block);
 //   * the census (mixer_check_bypass, audiomixer.c:244-286), the channels' queues and flow control (:92-111) run on COUNTS on the
-//     host, exactly as in LegBank::conf_tick (MSMI355X_CHECK_LEVELS compares the device queue with them every flush).
+//     host (ConfBank::conf_tick; MSMI355X_CHECK_LEVELS compares the device queue with them every flush).
 //
 // Equal to the facades one by one bit for bit (tests/test_plugin_server_cpu.py, tests/test_gpu_plugin_server.py), with LegBank's
 // stated exception (a lone contributor is mixed, not forwarded).  Endpoints at ANOTHER rate than the conference (G.711 endpoints
@@ -32,23 +32,20 @@
 // plugin feeding MSVolume (its blocks arrive with the flush, not in the walk) or MSMI355X_NO_FUSE=1 the conference keeps its facades.
 
 struct ServerBank;
-struct ServerLeg {
+struct ServerLeg : ConfMember {
 	ServerBank *bank;
-	int slot, pin;
-	uint32_t lv_from = 0; // MSMI355X_CHECK_LEVELS: the first read-back of the levels (ServerBank::lv_seq) that is this leg's, as FusedLeg::lv_from
-	MSFilter *vol, *mixer;
 	MSFilter *enc = nullptr;   // the pin's output is encoded in the batch (MSAlawEnc / MSUlawEnc of this plugin), else PCM
 	MSFilter *irs = nullptr;   // the endpoint's in_resampler when it really resamples (the endpoint runs at another rate than the conference): its state lives in the bank
 	MSFilter *dec = nullptr;   // the leg's HEAD is MSAlawDec / MSUlawDec of this plugin right in front of MSVolume: its packets are staged as they are and decoded in the batch
 	int staged = 0;            // blocks staged since the last enqueue (launch rounds)
-	int new_samples = 0;       // samples MSVolume put on the mixer's queue since the mixer last looked
-	int chan_samples = 0;      // the mixer channel's bufferizer, samples (what f_chan holds)
-	bool metered = false;
 	bool fuse_checked = false;
+	bool delivered() const { return new_samples > 0; }
+	bool has_staged() const { return staged > 0; }
+	static void prefetch_meters(ServerLeg *const *, size_t, size_t) {}
 };
 
-struct ServerBank : Pool {
-	int rate, ns, mm, nlegs, cap; // cap: samples a staged block may hold (a row of the staging arrays)
+struct ServerBank : ConfBank<ServerLeg> {
+	int rate, cap; // cap: samples a staged block may hold (a row of the staging arrays)
 	// Endpoints at ANOTHER rate than the conference (G.711 endpoints in a 16 kHz conference: audioconference.c:209-257 puts a working
 	// in_resampler in front of every pin and a working out_resampler behind it): MSVolume meters and levels at the endpoint's rate `re`,
 	// the levelled blocks are up-sampled in the batch (MSResample's own kernel on the member's state, 10 ms at a time as the facade
@@ -61,9 +58,6 @@ struct ServerBank : Pool {
 	int16_t *h_down = nullptr;                        // [nlegs][nse8] pinned: the down-sampled mixes of pins whose out_resampler is followed by somebody else's filter (PCM at `re`)
 	int32_t *h_un = nullptr, *d_un = nullptr;         // [kMaxRounds][nlegs]: the up-sampled counts
 	int pieces = 1, nse8 = 0;
-	mi_volume *vol = nullptr, *vol_id = nullptr;
-	mi_fifo *f_chan = nullptr;
-	mi_mixer *mix = nullptr;
 	int16_t *h_in, *d_in;        // [kMaxRounds][nlegs][cap] / [nlegs][cap]
 	int32_t *h_n, *d_n;          // [kMaxRounds][nlegs]
 	// legs headed by a G.711 decoder: the packets' bytes [kMaxRounds][nlegs][cap], and the rounds' counts by kind -- [0] MSVolume-headed,
@@ -71,49 +65,14 @@ struct ServerBank : Pool {
 	uint8_t *h_cin = nullptr;
 	int32_t *h_nk[4] = {nullptr, nullptr, nullptr, nullptr};
 	int ndec = 0;
-	int16_t *d_mix, *d_scratch;  // [capacity][mm][ns]; [nlegs][ns]
 	uint8_t *h_codes, *d_codes;  // [nlegs][ns]: the encoded pins' G.711 bytes of this flush
 	int32_t *h_len[2], *d_len[2]; // [nlegs] per law: ns where the pin's mix is encoded with that law in this launch, else 0
-	uint8_t *h_run, *d_run;      // [capacity]
-	uint8_t *h_dgate, *d_dgate;  // [nlegs]
 	int32_t *h_lv, *d_lv;        // MSMI355X_CHECK_LEVELS
-	mi_volume_state *h_vstate, *h_vround;
-	std::vector<uint8_t> vhas;
-	int vrounds = 0;
-	int16_t *h_copy;
-	std::vector<MixSlab *> slabs;
-	MixSlab *cur = nullptr;
-	mblk_t *root = nullptr;
-	std::vector<ServerLeg *> legs;
 	std::vector<MSFilter *> orss; // [nlegs]: the working out_resampler in front of that encoder (endpoints at another rate), or NULL
 	std::vector<MSFilter *> encs; // [nlegs]: the encoder behind output pin (c, pin), also where no member feeds that pin (a listener)
-	std::vector<uint8_t> conf_ready, flags;
-	std::vector<int> lone;
-	std::vector<float> gains;
-	bool ctl_dirty = true;
-	std::vector<uint8_t> next_flags, next_conf; // (what a method set while blocks were waiting for the coming flush: LegBank's comment)
-	std::vector<float> next_gains;
-	bool next_any = false;
-	std::vector<mi_volume_params> vparams;
-	std::vector<mi_volume_state> vstate;
-	std::vector<uint8_t> vp_dirty, vs_dirty;
-	bool v_dirty = false;
-	struct GainPatch {
-		float gain, target;
-		bool also_target;
-	};
-	std::vector<GainPatch> vpatch;
-	std::vector<std::pair<int, int>> sdrops;
-	std::vector<uint64_t> conf_time;
-	std::vector<uint32_t> walk_tick;
-	uint32_t walk_epoch = 0;
-	int walked = 0;
-	bool staged_since = false, outstanding = false, early = false, early_any = false, no_early = false;
-	bool mixed = false, pcm_out = false, check_levels = false, lv_fresh = false, zero_copy = true;
-	uint32_t lv_seq = 0;
-	uint64_t launches = 0;
+	bool pcm_out = false; // some pin of this launch gets its mix as PCM: the slab goes downstream
 
-	ServerBank(int cap_conf, int r, int members, int endpoint_rate) : rate(r), mm(members), re(endpoint_rate) {
+	ServerBank(int cap_conf, int r, int members, int endpoint_rate) : ConfBank(members), rate(r), re(endpoint_rate) {
 		Building b(this, cap_conf);
 		ns = rate / 100;
 		q = rate / re;
@@ -162,34 +121,12 @@ struct ServerBank : Pool {
 		d_lv = devmem<int32_t>(L);
 		h_vstate = pinned<mi_volume_state>(L);
 		h_vround = pinned<mi_volume_state>((size_t)kLegMeterRounds * L);
-		vhas.assign((size_t)kLegMeterRounds * L, 0);
 		h_copy = pinned<int16_t>(L * ns);
-		legs.assign(L, nullptr);
 		encs.assign(L, nullptr);
 		orss.assign(L, nullptr);
-		conf_ready.assign((size_t)capacity, 0);
-		lone.assign((size_t)capacity, -1);
-		flags.assign(L, 0);
-		gains.assign(L, 1.0f);
-		next_flags.assign(L, 0);
-		next_gains.assign(L, 1.0f);
-		next_conf.assign((size_t)capacity, 0);
-		mi_volume_params p;
-		mi_volume_default_params(&p);
-		vparams.assign(L, p);
-		vstate.resize(L);
-		vp_dirty.assign(L, 0);
-		vs_dirty.assign(L, 0);
-		vpatch.assign(L, GainPatch{1.f, 1.f, false});
-		conf_time.assign((size_t)capacity, (uint64_t)-1);
-		walk_tick.assign((size_t)capacity, 0);
-		check_levels = getenv("MSMI355X_CHECK_LEVELS") != nullptr;
-		zero_copy = zero_copy_rows();
-		no_early = getenv("MSMI355X_NO_EARLY_LAUNCH") != nullptr;
+		init_conf();
 	}
 	~ServerBank() override {
-		if (root) freeb(root);
-		for (ServerLeg *l : legs) delete l;
 		if (hub->ctx) mi_ctx_sync(hub->ctx);
 		if (mix) mi_mixer_destroy(mix);
 		if (vol) mi_volume_destroy(vol);
@@ -197,86 +134,9 @@ struct ServerBank : Pool {
 		if (rs_in) mi_resampler_destroy(rs_in);
 		if (rs_out) mi_resampler_destroy(rs_out);
 		if (f_chan) mi_fifo_destroy(f_chan);
-		for (MixSlab *s : slabs)
-			if (s->state.exchange(2, std::memory_order_acq_rel) == 0) mi_host_free(hub->ctx, s);
 	}
-	MixSlab *free_slab() {
-		for (MixSlab *s : slabs)
-			if (s->state.load(std::memory_order_acquire) == 0) return s;
-		if (slabs.size() >= 4 || failed) return nullptr;
-		const size_t bytes = (size_t)nlegs * ns * 2;
-		void *p = mi_host_alloc(hub->ctx, 64 + bytes);
-		if (!p) return nullptr;
-		MixSlab *s = new (p) MixSlab();
-		s->bytes = bytes;
-		slabs.push_back(s);
-		return s;
-	}
+	size_t slab_bytes() const override { return (size_t)nlegs * ns * 2; }
 
-	// one tick of a conference on counts: LegBank::conf_tick's `light` case (the channel's bufferizer holds the levelled blocks,
-	// the tick reads 10 ms of them or nothing, audiomixer.c:78-90) with the census of mixer_check_bypass (:244-286)
-	void conf_tick(int c, uint64_t now) {
-		MSFilter *mx = owner[(size_t)c];
-		MixerState *s = (MixerState *)mx->data;
-		conf_ready[(size_t)c] = 0;
-		lone[(size_t)c] = -1;
-		int count = 0, who = -1;
-		for (int pin = 0; pin < mm; ++pin) {
-			ServerLeg *leg = legs[(size_t)(c * mm + pin)];
-			if (!leg) continue;
-			uint64_t &seen = s->channels[pin].last_activity;
-			bool contributes;
-			if (leg->new_samples > 0) {
-				seen = now;
-				contributes = true;
-			} else if (seen == (uint64_t)-1) {
-				seen = now; // first look at a silent pin only starts its clock
-				contributes = false;
-			} else {
-				contributes = now - seen < BYPASS_MODE_TIMEOUT;
-			}
-			if (contributes) ++count, who = pin;
-		}
-		if (count == 0) return;
-		if ((count == 1) != (s->bypass_mode != FALSE))
-			ms_message("mi355x mixer %p: %s", (void *)mx, count == 1 ? "a single contributor (mixed on the device all the same)" : "two or more contributors");
-		s->bypass_mode = count == 1;
-		for (int pin = 0; pin < mm; ++pin) {
-			ServerLeg *leg = legs[(size_t)(c * mm + pin)];
-			if (!leg) continue;
-			Channel *chan = &s->channels[pin];
-			leg->chan_samples += leg->new_samples;
-			leg->new_samples = 0;
-			if (leg->chan_samples >= ns) leg->chan_samples -= ns;
-			const int skip = channel_flow_control_level(chan, leg->chan_samples * 2, s->skip_threshold, now);
-			if (skip > 0) {
-				const int k = std::min(leg->chan_samples, skip / 2);
-				ms_warning("mi355x mixer: pin %i kept more than two ticks queued for 5 s; %i samples discarded", pin, k);
-				leg->chan_samples -= k;
-				if (k > 0) sdrops.push_back({leg->slot, k});
-			}
-		}
-		conf_ready[(size_t)c] = 1;
-		lone[(size_t)c] = count == 1 ? who : -1;
-	}
-
-	void meter_round(size_t UL) {
-		if (vrounds >= kLegMeterRounds || failed) return;
-		MI_MUST(mi_volume_get_state_async(vol, 0, (int)UL, h_vround + (size_t)vrounds * nlegs));
-		++vrounds;
-	}
-
-	bool enqueue() override {
-		bool any = false;
-		const bool was_early = early;
-		if (early) {
-			early = false;
-			any = early_any;
-		}
-		if (!was_early || staged_since) any |= enqueue_at(hub_time(hub));
-		outstanding = false;
-		return any;
-	}
 	// a round's levelled blocks go onto the channels' queue: as they are, or (endpoints at another rate) up-sampled first, 10 ms at a
 	// time as MSResample's facade frames them -- the p-th launch serves every member whose block has a p-th piece
 	void queue_blocks(int r, int kind, int16_t *rows, const int32_t *cnt_host, const int32_t *cnt_launch) {
@@ -312,7 +172,7 @@ struct ServerBank : Pool {
 		MI_MUST(mi_fifo_push(f_chan, d_up, cap * q, cap * q, zero_copy ? hu : du));
 		++launches;
 	}
-	bool enqueue_at(uint64_t now) {
+	bool enqueue_at(uint64_t now) override {
 		mi_ctx *ctx = hub->ctx;
 		const size_t L = (size_t)nlegs, UL = (size_t)hi * mm;
 		if (outstanding) sync_stream();
@@ -414,14 +274,7 @@ struct ServerBank : Pool {
 			if (!zero_copy) MI_MUST(mi_copy_h2d_pinned(ctx, d_run, h_run, (size_t)capacity));
 			MI_MUST(mi_mixer_process_volume_fifo_flags(mix, vol_id, 0, f_chan, d_mix, MI_VOLMIX_DRY_SKIPS, zero_copy ? h_run : d_run));
 			++launches;
-			for (const auto &dk : sdrops) {
-				memset(h_dgate, 0, L);
-				h_dgate[(size_t)dk.first] = 1;
-				if (!zero_copy) MI_MUST(mi_copy_h2d_pinned(ctx, d_dgate, h_dgate, L));
-				for (int left = dk.second; left > 0; left -= std::min(left, ns))
-					MI_MUST(mi_fifo_pop(f_chan, std::min(left, ns), d_scratch, ns, nullptr, zero_copy ? h_dgate : d_dgate, 0));
-				sync_stream();
-			}
+			discard_sdrops();
 			// the mixes of this launch: encoded where the pin's output is an encoder of ours, PCM elsewhere
 			bool any_law[2] = {false, false};
 			bool down_now = false;
@@ -477,37 +330,17 @@ struct ServerBank : Pool {
 	}
 
 	void finish() override {
-		const size_t L = (size_t)nlegs, UL = (size_t)hi * mm;
+		const size_t UL = (size_t)hi * mm;
 		if (failed) {
 			std::fill(conf_ready.begin(), conf_ready.end(), 0);
 			g_late_events.fetch_add(1, std::memory_order_relaxed);
 			return;
 		}
 		if (mixed) {
-			for (size_t s = 0; s < UL; ++s) {
-				ServerLeg *leg = legs[s];
-				if (!leg) continue;
-				vstate[s] = h_vstate[s];
-				if (leg->metered && hub->ticker) { // update_energy's extremum records, msvolume.c:405-406: one per block, in order
-					VolumeData *vd = (VolumeData *)leg->vol->data;
-					for (int r = 0; r < vrounds; ++r)
-						if (vhas[(size_t)r * L + s]) {
-							vd->max.record_max(hub_time(hub), h_vround[(size_t)r * L + s].energy);
-							vd->min.record_min(hub_time(hub), h_vround[(size_t)r * L + s].energy);
-						}
-					vd->max.record_max(hub_time(hub), vstate[s].energy);
-					vd->min.record_min(hub_time(hub), vstate[s].energy);
-				}
-				leg->metered = false;
-			}
-			std::fill(vhas.begin(), vhas.end(), 0);
-			vrounds = 0;
+			read_meters();
 			mixed = false;
 		}
-		if (pcm_out && cur && !root) {
-			cur->state.store(1, std::memory_order_release);
-			root = esballoc(cur->payload(), cur->bytes, 0, mix_slab_release);
-		}
+		if (pcm_out && cur && !root) slab_out();
 		const bool lv_now = lv_fresh; // (a flush that launched nothing read no levels)
 		lv_fresh = false;
 		if (check_levels && lv_now)
@@ -521,9 +354,7 @@ struct ServerBank : Pool {
 
 	void emit(MSFilter *f, int c) override; // (needs the encoder facade: below)
 	void emitted() override {
-		if (root) freeb(root);
-		root = nullptr;
-		cur = nullptr;
+		ConfBank::emitted();
 		pcm_out = false;
 	}
 	void flushed() override {
@@ -532,69 +363,15 @@ struct ServerBank : Pool {
 			if (vp_dirty[s] == 2) vp_dirty[s] = 1, v_dirty = true;
 			if (vs_dirty[s] == 2) vs_dirty[s] = 1, v_dirty = true;
 		}
-		if (!next_any) return;
-		for (int c = 0; c < hi; ++c) {
-			if (!next_conf[(size_t)c]) continue;
-			const size_t at = (size_t)c * mm;
-			std::copy(next_flags.begin() + at, next_flags.begin() + at + mm, flags.begin() + at);
-			std::copy(next_gains.begin() + at, next_gains.begin() + at + mm, gains.begin() + at);
-			next_conf[(size_t)c] = 0;
-			ctl_dirty = true;
-		}
-		next_any = false;
+		controls_flushed();
 	}
-	// a slot's owner leaves while the bank's work for the coming tick is already out: LegBank::deliver_in_flight
-	// A conference with a SINGLE contributor is in the reference's bypass mode (audiomixer.c:219-286): that pin's blocks go to the other
-	// outputs AS THEY ARE -- no input gain, no regard for MS_AUDIO_MIXER_SET_ACTIVE (mixer_dispatch_output never looks at the channel).
-	// The batch mixes such a conference all the same, with that pin's controls set to "active, gain 1" for as long as it is alone:
-	// the sum of one is the block itself (but for a sample of -32768, which the sum saturates to -32767: the stated exception).
-	std::vector<int> lone_ctl;           // per conference: the pin whose controls are overridden right now, -1 = none
-	std::vector<uint8_t> eff_flags;
-	std::vector<float> eff_gains;
-	void push_controls() {
-		if (!mix) return;
-		bool moved = false;
-		if (lone_ctl.size() != lone.size()) lone_ctl.assign(lone.size(), -1), moved = true;
-		for (size_t c = 0; c < lone.size(); ++c) {
-			if (!owner[c] && lone_ctl[c] >= 0) lone_ctl[c] = -1, moved = true; // (the slot was given up)
-			if (owner[c] && conf_ready[c] && lone_ctl[c] != lone[c]) lone_ctl[c] = lone[c], moved = true; // (a conference that does not tick keeps what it had)
-		}
-		if (!ctl_dirty && !moved) return;
-		eff_flags = flags, eff_gains = gains;
-		for (size_t c = 0; c < lone_ctl.size(); ++c)
-			if (lone_ctl[c] >= 0) {
-				const size_t at = c * (size_t)mm + (size_t)lone_ctl[c];
-				eff_flags[at] |= MI_MIX_ACTIVE;
-				eff_gains[at] = 1.0f;
-			}
-		MI_MUST(mi_mixer_set_controls(mix, eff_flags.data(), eff_gains.data()));
-		ctl_dirty = false;
-	}
-	// a graph is being detached between two ticks (deliver_server_in_scope): rows staged in the last walk whose launches have not left --
-	// a bank without early launch, a conference that joined the bank mid-walk -- leave now, as the coming flush would send them
-	// (the walks are over and the ticker's clock reads what that flush would read): the tick in flight includes them
-	void launch_staged() {
-		if (failed || !staged_since || !hub->ticker) return;
-		const bool more = enqueue_at(hub_time(hub));
-		early_any = early ? (early_any || more) : more;
-		early = true;
-	}
-	void deliver_in_flight(MSFilter *owner_filter, int slot) {
-		if (failed || (!outstanding && !early)) return;
-		sync_stream();
-		if (failed) return;
-		outstanding = false;
+	// The two banks differ here, since when is unknown: this one leaves the hub's scope as it finds it, LegBank narrows it to the owner's graph.
+	void deliver_now(MSFilter *owner_filter, int slot) override {
 		finish();
 		emit(owner_filter, slot);
 	}
-	void settle_meters() {
-		if (!outstanding && !early) return;
-		if (failed) return;
-		sync_stream();
-		if (failed) return;
-		for (size_t s = 0; s < (size_t)nlegs; ++s)
-			if (legs[s] && !vs_dirty[s]) vstate[s] = h_vstate[s];
-	}
+	// The two banks differ here, since when is unknown: this one takes the read-back whatever the launches did, LegBank only when one levelled something.
+	bool meters_came_back() const override { return true; }
 };
 
 // ---- the encoder facade's half: the codes of one tick, packed to the encoder's ptime (alaw_enc_process, alaw.c:56-90)
@@ -626,7 +403,6 @@ void ServerBank::emit(MSFilter *f, int c) { // mixer_process :336-343 (conferenc
 	if (!conf_ready[(size_t)c]) return;
 	conf_ready[(size_t)c] = 0;
 	MixerState *s = (MixerState *)f->data;
-	const uint8_t *base = root ? cur->payload() : reinterpret_cast<const uint8_t *>(h_copy);
 	for (int pin = 0; pin < mm && pin < MIXER_MAX_CHANNELS; ++pin) {
 		MSQueue *q = f->outputs[pin];
 		if (!q || !s->channels[pin].output_enabled || pin == lone[(size_t)c]) continue;
@@ -647,18 +423,7 @@ void ServerBank::emit(MSFilter *f, int c) { // mixer_process :336-343 (conferenc
 			}
 			continue;
 		}
-		uint8_t *row = const_cast<uint8_t *>(base) + (at * ns) * 2;
-		mblk_t *om;
-		if (root) {
-			om = dupb(root);
-			om->b_rptr = row;
-			om->b_wptr = row + (size_t)ns * 2;
-		} else {
-			om = allocb((size_t)ns * 2, 0);
-			memcpy(om->b_wptr, row, (size_t)ns * 2);
-			om->b_wptr += ns * 2;
-		}
-		ms_queue_put(q, om);
+		ms_queue_put(q, row_block(at * ns, ns));
 	}
 }
 
@@ -738,17 +503,7 @@ void server_stage_codes(MSFilter *f, MapFilter *d) {
 	}
 }
 
-// every conference of the bank has been walked in this tick: the bank's work leaves now (leg_conf_walked)
-void server_conf_walked(ServerBank *b, int c) {
-	if (b->no_early || b->failed || b->early || !b->hub->ticker) return;
-	const uint32_t tick = b->hub->ticker->ticks;
-	if (b->walk_epoch != tick) b->walk_epoch = tick, b->walked = 0;
-	if (b->walk_tick[(size_t)c] == tick) return;
-	b->walk_tick[(size_t)c] = tick;
-	if (++b->walked < b->in_use) return;
-	b->early_any = b->enqueue_at(hub_time(b->hub) + (uint64_t)b->hub->ticker->interval);
-	b->early = true;
-}
+void conf_walked(ServerBank *b, int c) { b->conf_walked(c); } // (mixer.inl, which knows the banks by name only)
 
 // ---- fusing ------------------------------------------------------------------------------------------------------------
 bool is_g711_enc(const MSFilterDesc *d) { return d == &ms_mi355x_alaw_enc_desc || d == &ms_mi355x_ulaw_enc_desc; }
@@ -1075,35 +830,9 @@ Pool *server_pool_of(ServerBank *b) { return b; }
 Pool *server_pool_of_map(MapFilter *d) { return (ServerBank *)d->sleg_bank; }
 mi_volume_state *server_vstate(ServerLeg *leg) { return &leg->bank->vstate[(size_t)leg->slot]; }
 void server_push_volume(ServerLeg *leg, const mi_volume_params *p, const float *gain, const float *target) {
-	ServerBank *b = leg->bank;
-	const size_t s = (size_t)leg->slot;
-	const uint8_t when = b->work_waiting() ? 2 : 1;
-	b->vparams[s] = *p;
-	b->vparams[s].peer = -1;
-	b->vp_dirty[s] = when;
-	if (gain) {
-		b->vpatch[s] = {*gain, target ? *target : 0.f, target != nullptr};
-		b->vs_dirty[s] = when;
-	}
-	b->v_dirty = true;
+	leg->bank->push_volume((size_t)leg->slot, p, -1, gain, target);
 }
-void server_push_mixer_controls(MSFilter *f, MixerState *s, bool from_method) {
-	ServerBank *b = s->sbank;
-	const bool later = from_method && b->work_waiting();
-	std::vector<uint8_t> &fl_row = later ? b->next_flags : b->flags;
-	std::vector<float> &g_row = later ? b->next_gains : b->gains;
-	for (int pin = 0; pin < b->mm; ++pin) {
-		const size_t at = (size_t)(s->sconf * b->mm + pin);
-		uint8_t fl = 0;
-		if (f->inputs[pin] && b->legs[at]) fl |= MI_MIX_LINKED;
-		if (s->channels[pin].active) fl |= MI_MIX_ACTIVE;
-		if (f->outputs[pin] && s->channels[pin].output_enabled) fl |= MI_MIX_OUTPUT;
-		fl_row[at] = fl;
-		g_row[at] = s->channels[pin].gain;
-	}
-	if (later) b->next_conf[(size_t)s->sconf] = 1, b->next_any = true;
-	else b->next_conf[(size_t)s->sconf] = 0, b->ctl_dirty = true;
-}
+void conf_push_mixer_controls(ServerBank *b, MSFilter *f, MixerState *s, bool from_method) { b->push_mixer_controls(f, s, s->sconf, from_method); }
 // the encoder of a fused pin was detached or destroyed: its conference leaves the batch
 void server_encoder_gone(MSFilter *e) { // (an encoder OR a decoder of a fused member)
 	MapFilter *d = (MapFilter *)e->data;
@@ -1117,18 +846,4 @@ void server_encoder_gone(MSFilter *e) { // (an encoder OR a decoder of a fused m
 	}
 	if (mx) server_unfuse(mx, false);
 }
-void deliver_server_in_scope(TickerHub &h) {
-	for (Pool *p : h.pools) {
-		if (p->key.compare(0, 4, "srv:") != 0) continue;
-		ServerBank *b = static_cast<ServerBank *>(p);
-		bool ours = false; // (as in deliver_fused_in_scope: the whole bank is launched only when the detaching conference itself has staged blocks that have not left)
-		for (int s = 0; s < b->hi && !ours; ++s) {
-			if (!b->owner[(size_t)s] || !h.scope->count(b->owner[(size_t)s])) continue;
-			for (int pin = 0; pin < b->mm && !ours; ++pin)
-				if (const ServerLeg *leg = b->legs[(size_t)(s * b->mm + pin)]) ours = leg->staged > 0;
-		}
-		if (ours) b->launch_staged();
-		for (int s = 0; s < b->hi; ++s)
-			if (b->owner[(size_t)s] && h.scope->count(b->owner[(size_t)s])) b->deliver_in_flight(b->owner[(size_t)s], s);
-	}
-}
+void deliver_server_in_scope(TickerHub &h) { deliver_banks_in_scope<ServerBank>(h, "srv:"); }
