@@ -338,6 +338,10 @@ def run(plugin_dir, fuse, scenario, h=None):
     n = sc["nconf"] * sc["members"]
     nt, ni, ns = sc["nticks"], sc["in_rate"] // 100, sc["rate"] // 100
     mic, far = scene(n, nt, sc["in_rate"], sc["rate"], seed=sc.get("seed", 7))
+    if sc.get("silence"):   # digital silence in mid-call: the odd legs' sources deliver blocks of exact zeros (a muted microphone), every fourth leg's far end too (a held call)
+        t0, t1 = sc["silence"]
+        mic[1::2, t0 * ni:t1 * ni] = 0
+        far[1::4, t0 * ns:t1 * ns] = 0
     far_codes = None
     if sc.get("g711"):   # what the far endpoints send: their audio as PCMU (the oracle's encoder, pinned against the reference's g711.c)
         if ROOT not in sys.path:
@@ -418,6 +422,8 @@ SCENARIOS = {
     "delay_and_far_gaps": {"delay_ms": 20, "far_gaps": True, "nticks": 150},
     "ptime20": {"ptime20": True, "nticks": 100},
     "odd_pins": {"members": 3, "pins": [0, 5, 9], "nconf": 3, "tail_ms": 64},
+    # 1.5 s of zero blocks in mid-call: the canceller of a leg silent on both pins runs on subnormal state (tests/test_gpu_aec_silence.py)
+    "source_goes_silent_midcall": {"silence": (40, 190), "nticks": 230},
     "gain_method": {"events": [(40, "gain", 1, 0.5), (70, "gain", 5, 2.0)], "no_early_launch": True},
     "gain_method_early": {"events": [(40, "gain", 1, 0.5), (70, "gain", 5, 2.0)]},
     "wideband_8k_16k": {"in_rate": 8000, "rate": 16000, "tail_ms": 128, "nticks": 100},

@@ -13,23 +13,10 @@ import pytest
 
 import mediastreamer2_amd as ms
 from mediastreamer2_amd import _lib
+from aec_silence import make_echo_scene  # noqa: F401  (moved there verbatim; tests/test_gpu_aec512.py imports it from here)
 
 pytestmark = pytest.mark.gpu
 FULL_SCALE = 32768.0
-
-
-def make_echo_scene(seed, rate, nsamp, near_sigma=300.0, far_sigma=3000.0):
-    """mic = 0.5*ref through a fixed 64-tap decaying IR, 20 ms delay, + near-end noise."""
-    rng = np.random.default_rng(0x5EED + seed)
-    far = rng.normal(0, far_sigma, nsamp)
-    far = np.convolve(far, [0.5, 0.3, 0.2])[:nsamp] + 3276.7 * np.sin(2 * np.pi * 1000 * np.arange(nsamp) / rate)
-    ir = np.random.default_rng(1234).normal(0, 1, 64) * np.exp(-np.arange(64) / 12.0)
-    ir /= np.sqrt((ir ** 2).sum())
-    d = int(0.020 * rate)
-    echo = 0.5 * np.convolve(np.concatenate([np.zeros(d), far]), ir)[:nsamp]
-    mic = echo + rng.normal(0, near_sigma, nsamp)
-    to16 = lambda v: np.clip(np.round(v), -32767, 32767).astype(np.int16)
-    return to16(mic), to16(far)
 
 
 @pytest.mark.parametrize("F,group", [(256, 0), (128, 0), (64, 0), (128, 2), (64, 2)])

@@ -297,7 +297,8 @@ def test_chained_tick_pipeline_stage_parity(ctx, oracle):
     assert f_mic.overflows() == f_ref.overflows() == f_out.overflows() == 0
 
 
-def test_the_headline_two_launch_tick_against_the_oracle_chain(ctx, oracle):
+@pytest.mark.parametrize("scene", ["echo", "one_in_four_goes_silent"])
+def test_the_headline_two_launch_tick_against_the_oracle_chain(ctx, oracle, scene):
     """The tick exactly AS THE HEADLINE RUNS IT -- mi_aec_process_fifos_resampled (the leg's MSResample 16k->48k, both FIFO
     appends, every whole 256-sample frame through canceller + post-filter, the output FIFO append: one launch) and
     mi_mixer_process_volume_fifo (FIFO pop, AGC, 32-party mix: one launch) -- at the headline's own configuration: 128 ms
@@ -305,13 +306,19 @@ def test_the_headline_two_launch_tick_against_the_oracle_chain(ctx, oracle):
     enough (416 ticks) for every canceller to adapt and for both kinds of filter copy to occur.  Held DIRECTLY to the chain
     of oracle objects, stage by stage on what the two launches themselves queued (mi_fifo_snapshot reads the rings as they
     lie): <= 1 LSB for the up-sampled block, <= 1e-4 RMS for the cleaned frames (speexec.c:297-298), bit-exact meter +
-    mix given those frames (msvolume.c:471-514, audiomixer.c:288-346)."""
+    mix given those frames (msvolume.c:471-514, audiomixer.c:288-346).
+
+    Scene "one_in_four_goes_silent": the same call in which one member in four of every conference sends exact zeros on
+    both pins from tick 20 on, for 150 ticks, and then talks again -- a muted leg next to active ones in the same launches:
+    its canceller runs on subnormal state (tests/test_gpu_aec_silence.py), and the AGC and the conference mix behind it
+    meter digital silence.  The same bars, stage by stage."""
     torch = pytest.importorskip("torch")
     import bench
     nconf, mm, F, rate, ns, nticks = 2, 32, 256, 48000, 480, 416
     n, flen = nconf * mm, 128 * rate // 1000
     mic16, ref48 = bench.echo_scene()
     P = bench.SCENE_TICKS
+    silent = (lambda s, t: s % 4 == 1 and 20 <= t < 170) if scene == "one_in_four_goes_silent" else (lambda s, t: False)
     rs = ms.ResamplerBatch(ctx, n, 16000, rate)
     aec = ms.AecBatch(ctx, n, rate, frame_size=F, filter_length=flen)
     vol = ms.VolumeBatch(ctx, n, rate)
@@ -347,9 +354,17 @@ def test_the_headline_two_launch_tick_against_the_oracle_chain(ctx, oracle):
         return rings[s, idx]
 
     sq, cnt_s, frames, up_worst, two_frame_ticks = 0.0, 0, 0, 0, 0
+    quiet_frames = 0
     for t in range(nticks):
         k = t % P
-        aec.process_fifos_resampled(rs, d_mic[k], f_mic, f_ref, d_ref[k], f_out, max_frames=2, count_out=cnt)
+        mic_t, ref_t, t_mic, t_ref = mic16[:n, k * 160:(k + 1) * 160], ref48[:n, k * ns:(k + 1) * ns], d_mic[k], d_ref[k]
+        mute = np.array([silent(s, t) for s in range(n)])
+        if mute.any():
+            mic_t, ref_t = mic_t.copy(), ref_t.copy()
+            mic_t[mute], ref_t[mute] = 0, 0
+            t_mic, t_ref = torch.from_numpy(np.ascontiguousarray(mic_t)).cuda(), torch.from_numpy(np.ascontiguousarray(ref_t)).cuda()
+            torch.cuda.synchronize()
+        aec.process_fifos_resampled(rs, t_mic, f_mic, f_ref, t_ref, f_out, max_frames=2, count_out=cnt)
         ctx.sync()
         s_mic, s_out = f_mic.snapshot(), f_out.snapshot()
         g_cnt = cnt.cpu().numpy()
@@ -358,16 +373,17 @@ def test_the_headline_two_launch_tick_against_the_oracle_chain(ctx, oracle):
             rings, head, level = s_mic
             end = int(head[s]) + int(level[s])
             g_up = rings[s, np.arange(end - ns, end) % cap]
-            want = o_rs[s].process(mic16[s, k * 160:(k + 1) * 160])[:ns]
+            want = o_rs[s].process(mic_t[s])[:ns]
             up_worst = max(up_worst, int(np.abs(g_up.astype(int) - want.astype(int)).max()))
             q_mic[s] = np.concatenate([q_mic[s], g_up])            # the oracle continues from what the launch queued
-            q_ref[s] = np.concatenate([q_ref[s], ref48[s, k * ns:(k + 1) * ns]])
+            q_ref[s] = np.concatenate([q_ref[s], ref_t[s]])
             nf = 0
             w_clean = []
             while len(q_mic[s]) >= F and nf < 2:                   # speexec.c:256
                 m, q_mic[s] = q_mic[s][:F], q_mic[s][F:]
                 r, q_ref[s] = q_ref[s][:F], q_ref[s][F:]
                 w_clean.append(o_pp[s].run(o_ec[s].cancel(m, r)))
+                quiet_frames += not (m.any() or r.any())
                 nf += 1
             assert nf == int(g_cnt[s]), (t, s)
             two_frame_ticks += nf == 2
@@ -401,6 +417,10 @@ def test_the_headline_two_launch_tick_against_the_oracle_chain(ctx, oracle):
     o_adapt = np.array([o_ec[s].get("scalars", 16)[8] for s in range(n)])
     assert (o_adapt == 1).all()
     assert f_mic.overflows() + f_ref.overflows() + f_out.overflows() == 0
+    if scene == "one_in_four_goes_silent":   # the zeros reached the cancellers as whole frames of exact zeros on both pins
+        assert quiet_frames >= (n // 4) * (148 * ns // F), quiet_frames
+    else:
+        assert quiet_frames == 0
     for o in (rs, aec, vol, mix, f_mic, f_ref, f_out):
         o.close()
 
