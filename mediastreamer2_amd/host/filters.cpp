@@ -697,6 +697,7 @@ void recv_plc_walk(MSFilter *f, PlcFilter *d);
 void recv_flow_drop(RecvLeg *leg, uint32_t drop, uint32_t total);
 void recv_flow_config(RecvLeg *leg, const MSAudioFlowControlConfig *cfg);
 
+#include "filters/round_bank.inl"
 #include "filters/resample.inl"
 #include "filters/volume.inl"
 #include "filters/equalizer.inl"

@@ -5,7 +5,8 @@
 //
 // One slot per MEMBER (conference * mm + pin).  The census (mixer_check_bypass, audiomixer.c:244-286), the channels' queues and
 // their flow control (:92-111) run on COUNTS on the host; the mixer's controls, MSVolume's parameters and running state, the
-// meters' read-back, the pinned slab the mixes come back in and the early launch at the end of the graph walk live here once.
+// meters' read-back and the pinned slab the mixes come back in live here once; the early launch at the end of the graph walk is
+// EarlyBank's (round_bank.inl), counted per conference (conf_walked).
 // What differs between the two banks is reached through hooks: enqueue_at (the bank's launches), slab_bytes, the members' own
 // delivered() / has_staged() / prefetch_meters(), and the few overrides that say so.
 
@@ -40,7 +41,7 @@ struct ConfMember {
 //   bool has_staged() const    -- it has staged rows whose launches have not left
 //   static void prefetch_meters(Leg *const *legs, size_t s, size_t n)   -- read_meters()'s walk over legs[0, n) is at s
 template <class Leg>
-struct ConfBank : Pool {
+struct ConfBank : EarlyBank<Pool> {
 	int mm = 0, ns = 0, nlegs = 0;
 	mi_volume *vol = nullptr, *vol_id = nullptr; // vol_id: identity batch (gain 1, nothing enabled): volmix_kernel's volume half for a levelled queue
 	mi_fifo *f_chan = nullptr;                   // the mixer channels' bufferizers, where they hold levelled samples
@@ -82,19 +83,12 @@ struct ConfBank : Pool {
 	std::vector<std::pair<int, int>> sdrops; // (leg slot, samples) the mixer channels' flow control discards this flush
 	std::vector<uint64_t> conf_time;         // ticker time of a conference's last tick (one per tick, whoever enqueues)
 	std::vector<uint32_t> walk_tick;         // ticker tick in which a conference's mixer was last walked
-	uint32_t walk_epoch = 0;
-	int walked = 0;                          // conferences whose mixer has run in this tick's graph walk
-	bool staged_since = false;               // something was staged (or a conference joined) since the last enqueue
-	bool outstanding = false;                // an enqueue has not been waited for yet
-	bool early = false, early_any = false;   // this tick's work was enqueued at the end of the walk (conf_walked)
-	bool no_early = false;
 	// The staging rows and the mixes' slab are pinned host memory the device addresses itself: by default the launches read
 	// and write them where they lie (a few hundred bytes per leg, once) and the tick path makes no copy at all -- four
 	// launches and the meters' read-back.  MSMI355X_ZERO_COPY=0: staged through device buffers by copy launches (A/B).
 	bool zero_copy = true;
 	bool mixed = false, check_levels = false, lv_fresh = false;
 	uint32_t lv_seq = 0; // read-backs of the levels so far (ConfMember::lv_from)
-	uint64_t launches = 0;
 
 	explicit ConfBank(int members) : mm(members) {}
 	// the host's rows, once the derived constructor knows capacity and nlegs (the device's and the pinned ones are the derived bank's to size)
@@ -120,7 +114,6 @@ struct ConfBank : Pool {
 		vpatch.assign(L, GainPatch{1.f, 1.f, false});
 		check_levels = getenv("MSMI355X_CHECK_LEVELS") != nullptr;
 		zero_copy = zero_copy_rows();
-		no_early = getenv("MSMI355X_NO_EARLY_LAUNCH") != nullptr; // A/B switch: everything leaves at the flush
 	}
 	~ConfBank() override { // (behind the derived bank's: the stream has been waited for, the batch objects are gone)
 		if (root) freeb(root);
@@ -129,7 +122,7 @@ struct ConfBank : Pool {
 			if (s->state.exchange(2, std::memory_order_acq_rel) == 0) mi_host_free(hub->ctx, s);
 	}
 
-	virtual bool enqueue_at(uint64_t now) = 0; // the bank's uploads and launches for everything staged, the conferences ticking at `now`
+	// (enqueue_at(now), EarlyBank's hook: the bank's uploads and launches for everything staged, the conferences ticking at `now`)
 	virtual size_t slab_bytes() const = 0;     // what one flush downloads into a slab
 
 	MixSlab *free_slab() {
@@ -333,48 +326,12 @@ struct ConfBank : Pool {
 		vrounds = 0;
 	}
 
-	bool enqueue() override {
-		bool any = false;
-		const bool was_early = early;
-		if (early) { // already out since the end of the last graph walk
-			early = false;
-			any = early_any;
-		}
-		// (what was staged after an early enqueue -- a conference that joined the bank later in that walk -- goes out now)
-		if (!was_early || staged_since) any |= enqueue_at(hub_time(hub));
-		outstanding = false; // the hub waits for the stream right behind this
-		return any;
-	}
-	// Every conference of the bank has been walked in this tick (its mixer runs behind all of its members in the ticker's
-	// depth-first order, msticker.c:261-282, so everything the tick will stage IS staged): the bank's uploads and launches go
-	// out NOW, at the end of the graph walk, instead of at the start of the next tick -- the device works through the idle
-	// part of the interval and the next tick's flush finds the results waiting.  Same results, same one tick of latency; the
-	// launches just leave the tick's critical path.  (A tick in which some mixer did not run falls back to the flush.)
+	// a conference's mixer runs behind all of its members: the last conference of the bank to be walked sends the bank's work off
 	void conf_walked(int c) {
 		if (!walk_begins()) return;
 		if (walk_tick[(size_t)c] == hub->ticker->ticks) return;
 		walk_tick[(size_t)c] = hub->ticker->ticks;
 		walk_counted();
-	}
-	bool walk_begins() { // false: no early launch (switched off, or this tick's has left already)
-		if (no_early || failed || early || !hub->ticker) return false;
-		const uint32_t tick = hub->ticker->ticks;
-		if (walk_epoch != tick) walk_epoch = tick, walked = 0;
-		return true;
-	}
-	void walk_counted() { // one more of the bank's slots has been walked in this tick: the last one launches
-		if (++walked < in_use) return;
-		early_any = enqueue_at(hub_time(hub) + (uint64_t)hub->ticker->interval); // the mixers' clock reads what the flush would
-		early = true;
-	}
-	// a graph is being detached between two ticks (deliver_in_scope): rows staged in the last walk whose launches have not left --
-	// a bank without early launch, a conference that joined the bank mid-walk -- leave now, as the coming flush would send them
-	// (the walks are over and the ticker's clock reads what that flush would read): the tick in flight includes them
-	void launch_staged() {
-		if (failed || !staged_since || !hub->ticker) return;
-		const bool more = enqueue_at(hub_time(hub));
-		early_any = early ? (early_any || more) : more;
-		early = true;
 	}
 	// A slot's owner leaves while the bank's work for the coming tick is already out (it left at the end of the last graph walk):
 	// the reference's filters would have handed that tick's audio on in the walk itself, so it goes out now -- the owner's own

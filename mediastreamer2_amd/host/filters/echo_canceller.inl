@@ -1,6 +1,6 @@
 // filters/echo_canceller.inl -- MSSpeexEC facade (src/audiofilters/speexec.c).
 // Part of the single translation unit filters.cpp (included inside its anonymous namespace, after the pool / hub
-// infrastructure); not compiled on its own.
+// infrastructure and round_bank.inl, which its bank's round staging comes from); not compiled on its own.
 
 // ============================================================== echo canceller
 // A slot's frames of one tick are staged back to back, kEcTickFrames to a row, and a row is ONE launch of the canceller's
@@ -8,12 +8,11 @@
 // HBM once, the foreground filter streamed once) -- the while loop of speexec.c:256-305 unrolled into a count per slot.  A
 // burst of more frames (a 20 ms packet, a network hiccup) takes the next row: kMaxRounds launches, one wait.
 constexpr int kEcTickFrames = MI_AEC_MAX_TICK_FRAMES;
-struct EcPool : Pool {
+struct EcPool : RoundBank {
 	int rate, F, flen;
 	mi_aec *a = nullptr;
 	int16_t *h_mic, *h_ref, *h_out, *d_mic, *d_ref, *d_out;
-	uint8_t *h_cnt, *d_cnt;
-	std::vector<int> staged, ready; // FRAMES per slot
+	uint8_t *h_cnt, *d_cnt; // (`staged` / `ready` count FRAMES here, kEcTickFrames to a round: the launch takes frame counts, not the base's lengths)
 	EcPool(int cap, int r, int frame, int filter_length) : rate(r), F(frame), flen(filter_length) {
 		Building b(this, cap);
 		if (!failed) MI_MUST(mi_aec_create(hub->ctx, capacity, rate, F, flen, &a));
@@ -26,8 +25,7 @@ struct EcPool : Pool {
 		d_ref = devmem<int16_t>(c * row);
 		d_out = devmem<int16_t>(kMaxRounds * c * row); // a row of results per round: the rounds' downloads need not wait for each other
 		d_cnt = devmem<uint8_t>(kMaxRounds * c);
-		staged.assign(c, 0);
-		ready.assign(c, 0);
+		init_rounds(false);
 	}
 	~EcPool() override {
 		if (a) mi_aec_destroy(a);
@@ -38,11 +36,8 @@ struct EcPool : Pool {
 	bool enqueue() override {
 		mi_ctx *ctx = hub->ctx;
 		const size_t c = (size_t)capacity, u = (size_t)hi, row = (size_t)kEcTickFrames * F; // rows [0, hi) are all that was ever handed out
-		int maxf = 0;
-		for (int s = 0; s < hi; ++s)
-			if (!parked(s)) maxf = std::max(maxf, staged[(size_t)s]);
-		const int rounds = (maxf + kEcTickFrames - 1) / kEcTickFrames;
-		for (int r = 0; r < rounds; ++r) {
+		const int nrounds = (rounds() + kEcTickFrames - 1) / kEcTickFrames;
+		for (int r = 0; r < nrounds; ++r) {
 			for (int s = 0; s < capacity; ++s)
 				h_cnt[r * c + s] = s < hi && !parked(s) ? (uint8_t)std::clamp(staged[(size_t)s] - r * kEcTickFrames, 0, kEcTickFrames) : 0;
 			if (zero_copy_rows()) { // the launch reads the pinned rows and writes the results where they lie: no copy at all (leg_chain.inl says why)
@@ -55,20 +50,15 @@ struct EcPool : Pool {
 			MI_MUST(mi_aec_process_frames(a, d_mic, d_ref, d_out + r * c * row, (int)row, d_cnt + r * c, kEcTickFrames, MI_AEC_POSTFILTER));
 			MI_MUST(mi_copy_d2h_pinned(ctx, h_out + r * c * row, d_out + r * c * row, u * row * 2));
 		}
-		return rounds > 0;
+		return nrounds > 0;
 	}
 	void finish() override {
 		if (failed) { // the launch did not happen: the microphone frames leave uncancelled (what bypass mode does, speexec.c:229-237)
 			for (int s = 0; s < hi; ++s)
 				for (int k = 0; k < staged[(size_t)s] && !parked(s); ++k) memcpy(h_out + frame_at((size_t)s, k), h_mic + frame_at((size_t)s, k), (size_t)F * 2);
 		}
-		for (int s = 0; s < hi; ++s) {
-			if (parked(s)) continue;
-			ready[(size_t)s] = staged[(size_t)s];
-			staged[(size_t)s] = 0;
-		}
+		settle();
 	}
-	bool scoped() const override { return true; }
 	void flushed() override; // (a bypass switch waiting for the last walk's frames goes live: below SpeexECState)
 	void emit(MSFilter *f, int slot) override {
 		const size_t sl = (size_t)slot;

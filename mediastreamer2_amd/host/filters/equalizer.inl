@@ -1,14 +1,12 @@
 // filters/equalizer.inl -- MSEqualizer facade (src/audiofilters/equalizer.c).
 // Part of the single translation unit filters.cpp (included inside its anonymous namespace, after the pool / hub
-// infrastructure); not compiled on its own.
+// infrastructure and round_bank.inl, which its bank's round staging comes from); not compiled on its own.
 
 // =================================================================== equalizer
-struct EqualizerPool : Pool {
+struct EqualizerPool : RoundBank {
 	int rate, cap_samples;
 	mi_equalizer *e = nullptr;
 	int16_t *h_buf, *d_buf;
-	int32_t *h_n, *d_n, *h_nsc; // (h_nsc: as VolumePool's)
-	std::vector<int> staged, ready;
 	// MS_EQUALIZER_SET_GAIN / SET_ACTIVE while the last walk's blocks are still waiting for the coming flush (Pool::work_waiting): they go
 	// live behind that flush (flushed()), as the reference's process() of that walk ran before the call
 	struct Op {
@@ -42,12 +40,8 @@ struct EqualizerPool : Pool {
 		cap_samples = (std::max(960, rate / 100 * 2) + 7) & ~7;
 		const size_t c = (size_t)capacity;
 		h_buf = pinned<int16_t>(kMaxRounds * c * cap_samples);
-		h_n = pinned<int32_t>(kMaxRounds * c);
-		h_nsc = pinned<int32_t>(kMaxRounds * c);
+		init_rounds();
 		d_buf = devmem<int16_t>(c * cap_samples);
-		d_n = devmem<int32_t>(c);
-		staged.assign(c, 0);
-		ready.assign(c, 0);
 	}
 	~EqualizerPool() override {
 		if (e) mi_equalizer_destroy(e);
@@ -55,41 +49,24 @@ struct EqualizerPool : Pool {
 	bool enqueue() override {
 		mi_ctx *ctx = hub->ctx;
 		const size_t c = (size_t)capacity, u = (size_t)hi; // rows [0, hi) are all that was ever handed out
-		int maxr = 0;
-		for (int s = 0; s < hi; ++s)
-			if (!parked(s)) maxr = std::max(maxr, staged[(size_t)s]);
+		const int maxr = rounds();
 		for (int r = 0; r < maxr; ++r) {
-			const int32_t *nrow = h_n + r * c;
-			if (hub->scope) { // a detaching graph's slots alone (see VolumePool::enqueue)
-				for (int s = 0; s < capacity; ++s) h_nsc[r * c + s] = (s < hi && staged[(size_t)s] > r && !parked(s)) ? h_n[r * c + s] : 0;
-				nrow = h_nsc + r * c;
-			} else {
-				for (int s = 0; s < capacity; ++s)
-					if (s >= hi || staged[(size_t)s] <= r) h_n[r * c + s] = 0;
-			}
-			if (zero_copy_rows()) { // (in place in pinned memory, as VolumePool)
+			const int32_t *nrow = len_row(r);
+			if (zero_copy_rows()) { // (in place in pinned memory)
 				MI_MUST(mi_equalizer_process_masked(e, h_buf + r * c * cap_samples, cap_samples, cap_samples, nrow));
 			} else {
 				MI_MUST(mi_copy_h2d_pinned(ctx, d_buf, h_buf + r * c * cap_samples, u * cap_samples * 2));
-				MI_MUST(mi_copy_h2d_pinned(ctx, d_n, nrow, c * 4));
-				MI_MUST(mi_equalizer_process_masked(e, d_buf, cap_samples, cap_samples, d_n));
+				MI_MUST(mi_equalizer_process_masked(e, d_buf, cap_samples, cap_samples, on_device(nrow)));
 				MI_MUST(mi_copy_d2h_pinned(ctx, h_buf + r * c * cap_samples, d_buf, u * cap_samples * 2));
 			}
 		}
 		return maxr > 0;
 	}
-	void finish() override {
-		for (int s = 0; s < hi; ++s) { // after a failed launch the staged blocks leave as they came (flat response)
-			if (parked(s)) continue;
-			ready[(size_t)s] = staged[(size_t)s];
-			staged[(size_t)s] = 0;
-		}
-	}
-	bool scoped() const override { return true; }
+	void finish() override { settle(); } // (after a failed launch the staged blocks leave as they came: flat response)
 	void emit(MSFilter *f, int slot) override {
 		const size_t c = (size_t)capacity, s = (size_t)slot;
 		for (int r = 0; r < ready[s]; ++r) {
-			const int n = h_n[r * c + s];
+			const int n = h_len[r * c + s];
 			mblk_t *om = allocb((size_t)n * 2, 0);
 			memcpy(om->b_wptr, h_buf + (r * c + s) * cap_samples, (size_t)n * 2);
 			om->b_wptr += n * 2;
@@ -270,7 +247,7 @@ void equalizer_process(MSFilter *f) { // equalizer.c:279-288
 		} else {
 			break;
 		}
-		p->h_n[p->staged[s] * c + s] = n;
+		p->h_len[p->staged[s] * c + s] = n;
 		p->staged[s]++;
 	}
 	if (p->staged[s]) request_flush(f);

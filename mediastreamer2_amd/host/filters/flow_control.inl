@@ -1,24 +1,19 @@
 // filters/flow_control.inl -- MSAudioFlowControl facade (src/audiofilters/flowcontrol.c).
 // Part of the single translation unit filters.cpp (included inside its anonymous namespace, after the pool / hub
-// infrastructure); not compiled on its own.
+// infrastructure and round_bank.inl, which its bank's round staging comes from); not compiled on its own.
 
 // ---- MSAudioFlowControl flowcontrol.c:154-279
 constexpr int kFlowBlock = 2048; // samples per staged block (mi_flowctl's limit); longer blocks are split
-struct FlowPool : Pool {
+struct FlowPool : RoundBank {
 	mi_flowctl *fc = nullptr;
 	int16_t *h_in, *h_out, *d_in, *d_out;
-	int32_t *h_len, *h_olen, *d_len, *d_olen;
-	int32_t *h_lensc; // the rounds' length rows while a detaching graph's slots alone are flushed (see VolumePool::enqueue)
-	std::vector<uint32_t> req_drop, req_total; // pending MS_AUDIO_FLOW_CONTROL_DROP requests ...
-	std::vector<int> req_round;                // ... and how many staged blocks of the stream precede each
-	std::vector<uint32_t> arm_drop, arm_total;
-	bool have_req = false;
+	int32_t *h_olen, *d_olen;
+	DropRequests drops; // MS_AUDIO_FLOW_CONTROL_DROP calls since the last launch
 	// A method between two walks meets the NEXT walk's blocks in the reference (the filter's next process()).  Here the last walk's blocks
 	// may still be on their way to this bank (they arrive with the coming flush, Pool::work_waiting): a request made then waits in
 	// later_* and is armed when that flush is through (flushed()) -- in front of the blocks of the walk the call preceded
 	std::vector<uint32_t> later_drop, later_total;
 	bool have_later = false;
-	std::vector<int> staged, ready;
 	std::vector<uint8_t> used; // the slot has had a filter since the bank was created (a fresh one is a controller at rest with the default configuration: mi_flowctl_create)
 	std::vector<std::vector<mblk_t *>> held, done; // the blocks themselves: the dropper edits them in place
 	explicit FlowPool(int cap) {
@@ -27,22 +22,14 @@ struct FlowPool : Pool {
 		const size_t c = (size_t)capacity;
 		h_in = pinned<int16_t>(kMaxRounds * c * kFlowBlock);
 		h_out = pinned<int16_t>(kMaxRounds * c * kFlowBlock);
-		h_len = pinned<int32_t>(kMaxRounds * c);
-		h_lensc = pinned<int32_t>(kMaxRounds * c);
+		init_rounds();
 		h_olen = pinned<int32_t>(kMaxRounds * c);
 		d_in = devmem<int16_t>(c * kFlowBlock);
 		d_out = devmem<int16_t>(c * kFlowBlock);
-		d_len = devmem<int32_t>(c);
 		d_olen = devmem<int32_t>(c);
-		req_drop.assign(c, 0);
-		req_total.assign(c, 0);
-		req_round.assign(c, 0);
-		arm_drop.assign(c, 0);
-		arm_total.assign(c, 0);
+		drops.init(c);
 		later_drop.assign(c, 0);
 		later_total.assign(c, 0);
-		staged.assign(c, 0);
-		ready.assign(c, 0);
 		used.assign(c, 0);
 		held.resize(c);
 		done.resize(c);
@@ -53,69 +40,33 @@ struct FlowPool : Pool {
 	void flush() override {
 		mi_ctx *ctx = hub->ctx;
 		const size_t c = (size_t)capacity;
-		// MS_AUDIO_FLOW_CONTROL_DROP calls since the last launch (:199-211) take effect exactly where they fell in the
-		// stream's block sequence: before round r for a request that r staged blocks preceded (last = everything left).
-		// A stream that is still dropping ignores its request on the device, like :204 does.
-		auto arm = [&](int r, bool last) {
-			if (!have_req) return;
-			bool any = false, left = false;
-			for (int s = 0; s < capacity; ++s) {
-				arm_drop[(size_t)s] = arm_total[(size_t)s] = 0;
-				if (req_drop[(size_t)s] == 0 && req_total[(size_t)s] == 0) continue;
-				if (s < hi && parked(s)) { // (not this flush's business: the request waits for the slot's own)
-					left = true;
-					continue;
-				}
-				if (last || req_round[(size_t)s] <= r) {
-					arm_drop[(size_t)s] = req_drop[(size_t)s], arm_total[(size_t)s] = req_total[(size_t)s];
-					req_drop[(size_t)s] = req_total[(size_t)s] = 0;
-					any = true;
-				} else left = true;
-			}
-			if (any) MI_MUST(mi_flowctl_request_drop(fc, arm_drop.data(), arm_total.data()));
-			have_req = left;
-		};
-		int maxr = 0;
-		for (int s = 0; s < hi; ++s)
-			if (!parked(s)) maxr = std::max(maxr, staged[(size_t)s]);
+		int maxr = rounds();
 		if (failed) { // a broken context is not given more work: the staged blocks leave as they came, nothing dropped
 			for (int r = 0; r < maxr; ++r) {
 				memcpy(h_out + r * c * kFlowBlock, h_in + r * c * kFlowBlock, c * kFlowBlock * 2);
 				for (int s = 0; s < hi; ++s)
 					if (!parked(s)) h_olen[r * c + s] = staged[(size_t)s] > r ? h_len[r * c + s] : 0;
 			}
-			have_req = false;
-			std::fill(req_drop.begin(), req_drop.end(), 0u);
-			std::fill(req_total.begin(), req_total.end(), 0u);
+			drops.clear();
 			maxr = 0;
 		}
 		for (int r = 0; r < maxr; ++r) {
-			arm(r, false);
-			const int32_t *lrow = h_len + r * c;
-			if (hub->scope) {
-				for (int s = 0; s < capacity; ++s) h_lensc[r * c + s] = (s < hi && staged[(size_t)s] > r && !parked(s)) ? h_len[r * c + s] : 0;
-				lrow = h_lensc + r * c;
-			} else {
-				for (int s = 0; s < capacity; ++s)
-					if (staged[(size_t)s] <= r) h_len[r * c + s] = 0;
-			}
+			drops.arm(*this, fc, r, false);
+			const int32_t *lrow = len_row(r);
 			MI_MUST(mi_copy_h2d_pinned(ctx, d_in, h_in + r * c * kFlowBlock, c * kFlowBlock * 2));
-			MI_MUST(mi_copy_h2d_pinned(ctx, d_len, lrow, c * 4));
-			MI_MUST(mi_flowctl_process(fc, d_in, kFlowBlock, d_len, kFlowBlock, d_out, kFlowBlock, d_olen));
+			MI_MUST(mi_flowctl_process(fc, d_in, kFlowBlock, on_device(lrow), kFlowBlock, d_out, kFlowBlock, d_olen));
 			MI_MUST(mi_copy_d2h_pinned(ctx, h_out + r * c * kFlowBlock, d_out, c * kFlowBlock * 2));
 			MI_MUST(mi_copy_d2h_pinned(ctx, h_olen + r * c, d_olen, c * 4));
 		}
-		if (!failed) arm(maxr, true);
+		if (!failed) drops.arm(*this, fc, maxr, true); // (last: everything left)
 		if (maxr) MI_MUST(mi_ctx_sync(ctx));
-		for (int s = 0; s < capacity; ++s) {
-			if (s < hi && parked(s)) continue;
-			ready[(size_t)s] = staged[(size_t)s];
-			staged[(size_t)s] = 0;
+		settle();
+		for (int s = 0; s < hi; ++s) {
+			if (parked(s)) continue;
 			done[(size_t)s].swap(held[(size_t)s]);
 			held[(size_t)s].clear();
 		}
 	}
-	bool scoped() const override { return true; }
 	void flushed() override {
 		if (!have_later) return;
 		bool left = false;
@@ -125,11 +76,7 @@ struct FlowPool : Pool {
 				left = true;
 				continue;
 			}
-			if (req_drop[(size_t)s] == 0 && req_total[(size_t)s] == 0) { // (ignored while one is pending, like :204)
-				req_drop[(size_t)s] = later_drop[(size_t)s], req_total[(size_t)s] = later_total[(size_t)s];
-				req_round[(size_t)s] = staged[(size_t)s];
-				have_req = true;
-			}
+			drops.request((size_t)s, later_drop[(size_t)s], later_total[(size_t)s], staged[(size_t)s]);
 			later_drop[(size_t)s] = later_total[(size_t)s] = 0;
 		}
 		have_later = left;
@@ -174,7 +121,7 @@ void flowctl_release(FlowFilter *d) {
 		v->clear();
 	}
 	d->pool->staged[s] = d->pool->ready[s] = 0;
-	d->pool->req_drop[s] = d->pool->req_total[s] = 0;
+	d->pool->drops.forget(s);
 	d->pool->later_drop[s] = d->pool->later_total[s] = 0;
 	d->pool->release(d->slot);
 	d->pool = nullptr;
@@ -269,25 +216,16 @@ int flowctl_drop(MSFilter *f, void *arg) { // :199-211; applied by the next laun
 	const MSAudioFlowControlDropEvent *ev = (const MSAudioFlowControlDropEvent *)arg;
 	HubLock lk(f);
 	ms_filter_lock(f);
-	if (d->rleg)
-		recv_flow_drop(d->rleg, (ev->drop_ms * (uint32_t)d->samplerate * (uint32_t)d->nchannels) / 1000,
-		               (ev->flow_control_interval_ms * (uint32_t)d->samplerate * (uint32_t)d->nchannels) / 1000);
-	if (d->pool && f->ticker && d->pool->work_waiting()) { // the last walk's blocks are still on their way here: behind them (FlowPool::flushed)
-		FlowPool *p = d->pool;
-		const size_t s = (size_t)d->slot;
-		if (p->later_drop[s] == 0 && p->later_total[s] == 0 && p->req_drop[s] == 0 && p->req_total[s] == 0) {
-			p->later_drop[s] = (ev->drop_ms * (uint32_t)d->samplerate * (uint32_t)d->nchannels) / 1000;
-			p->later_total[s] = (ev->flow_control_interval_ms * (uint32_t)d->samplerate * (uint32_t)d->nchannels) / 1000;
+	const uint32_t drop = DropRequests::samples(ev->drop_ms, d->samplerate, d->nchannels), total = DropRequests::samples(ev->flow_control_interval_ms, d->samplerate, d->nchannels);
+	FlowPool *p = d->pool;
+	const size_t s = (size_t)d->slot;
+	if (d->rleg) recv_flow_drop(d->rleg, drop, total);
+	if (p && f->ticker && p->work_waiting()) { // the last walk's blocks are still on their way here: behind them (FlowPool::flushed)
+		if (p->later_drop[s] == 0 && p->later_total[s] == 0 && !p->drops.pending(s)) {
+			p->later_drop[s] = drop, p->later_total[s] = total;
 			p->have_later = true;
 		}
-	} else {
-		if (d->pool && d->pool->req_drop[(size_t)d->slot] == 0 && d->pool->req_total[(size_t)d->slot] == 0) {
-			d->pool->req_drop[(size_t)d->slot] = (ev->drop_ms * (uint32_t)d->samplerate * (uint32_t)d->nchannels) / 1000;
-			d->pool->req_total[(size_t)d->slot] = (ev->flow_control_interval_ms * (uint32_t)d->samplerate * (uint32_t)d->nchannels) / 1000;
-			d->pool->req_round[(size_t)d->slot] = d->pool->staged[(size_t)d->slot];
-			d->pool->have_req = true;
-		}
-	}
+	} else if (p) p->drops.request(s, drop, total, p->staged[s]);
 	ms_filter_unlock(f);
 	return 0;
 }

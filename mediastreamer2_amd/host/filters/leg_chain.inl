@@ -1443,7 +1443,7 @@ bool leg_take_peer(LegBank *b, FusedLeg *leg, MSFilter *pf) {
 	if (VolumePool *p = pd->pool) {
 		const size_t c = (size_t)p->capacity, ps = (size_t)pd->slot;
 		for (int r = 0; r < p->staged[ps]; ++r) {
-			const int n = p->h_n[(size_t)r * c + ps];
+			const int n = p->h_len[(size_t)r * c + ps];
 			const int16_t *row = p->h_buf + ((size_t)r * c + ps) * p->cap_samples;
 			if (n <= 0) continue;
 			if (leg->peer_staged < kMaxRounds && n <= b->pcap) {

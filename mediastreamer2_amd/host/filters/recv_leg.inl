@@ -22,7 +22,7 @@
 //     whatever follows the chain (dtmfgen): ONE wait for the whole receiving side, one tick of added latency in total.
 //
 // MS_AUDIO_FLOW_CONTROL_DROP (flowcontrol.c:199-211: MSSpeexEC's and the sound card's events) and SET_CONFIG reach the bank's slot;
-// a drop request takes effect where it fell in the stream's block sequence, as in FlowPool.  The filters leave the batch at detach
+// a drop request takes effect where it fell in the stream's block sequence (DropRequests).  The filters leave the batch at detach
 // (the tick in flight is delivered first, filters.cpp: facade_detached) or when MSGenericPLC is given another rate in mid-call (its
 // context then starts over, as the facade's does).  A packet longer than a row (60 ms of G.711) sends the stream back to its facades.
 // MSMI355X_NO_FUSE=1: every facade on its own bank (what the tests compare against).
@@ -42,7 +42,6 @@ struct RecvLeg {
 	RecvBank *bank;
 	int slot;
 	MSFilter *dec, *plc, *fc, *mixer, *tail; // dec / fc / mixer (a forwarding local_mixer that is looked through) may be NULL; tail: whose output the blocks leave on
-	int staged = 0;   // device rounds staged since the last launch
 	int counted = 0;  // entries the PLC's walk has accounted for (ms_concealer_inc_sample_time)
 	int nent = 0, nout = 0;
 	RecvEntry ent[kRecvEntries]; // staged since the last launch
@@ -51,28 +50,19 @@ struct RecvLeg {
 	std::atomic<bool> unfuse_wanted{false};
 };
 
-struct RecvBank : Pool {
+struct RecvBank : EarlyBank<RoundBank> { // (`staged[slot]`: device rounds the stream has staged since the last launch; `ready` is not used: RecvLeg::out)
 	int rate, law; // law: MI_LAW_PCMA / MI_LAW_PCMU, -1 = no decoder (MSGenericPLC heads the chain)
 	bool with_fc;
 	mi_plc *plc = nullptr;
 	mi_flowctl *fc = nullptr;
 	uint8_t *h_codes = nullptr, *d_codes = nullptr; // [kMaxRounds][cap][kRecvBlock] pinned / [cap][kRecvBlock]
 	int16_t *h_pcm, *d_pcm, *d_out = nullptr;       // [kMaxRounds][cap][kRecvBlock] pinned: staged PCM (no decoder) and every round's results; [cap][kRecvBlock]
-	int32_t *h_len, *h_lensc, *d_len;               // [kMaxRounds][cap]; the same while a detaching graph's slots alone are flushed; [cap]
-	uint8_t *h_mode, *h_modesc, *d_mode;            // MI_PLC_* per round and stream
 	int32_t *h_olen, *d_olen = nullptr;             // [kMaxRounds][cap]: samples MSAudioFlowControl left of the block (0: dropped)
 	std::vector<RecvLeg *> legs;
 	std::vector<uint8_t> used; // the slot has had a stream since the bank was created (a fresh one needs no reset: recv_try_fuse)
-	// MS_AUDIO_FLOW_CONTROL_DROP requests since the last launch and how many staged rounds of the stream precede each (FlowPool)
-	std::vector<uint32_t> req_drop, req_total, arm_drop, arm_total;
-	std::vector<int> req_round;
-	bool have_req = false;
-	bool zero_copy = true, no_early = false;
-	bool staged_since = false, outstanding = false, early = false, early_any = false;
+	DropRequests drops; // MS_AUDIO_FLOW_CONTROL_DROP requests since the last launch
+	bool zero_copy = true;
 	int launched_rounds = 0;
-	int walked = 0;
-	uint32_t walk_epoch = 0;
-	uint64_t launches = 0;
 
 	RecvBank(int cap, int r, int l, bool flow) : rate(r), law(l), with_fc(flow) {
 		Building b(this, cap);
@@ -86,20 +76,13 @@ struct RecvBank : Pool {
 		h_pcm = pinned<int16_t>(kMaxRounds * c * kRecvBlock);
 		d_pcm = devmem<int16_t>(c * kRecvBlock);
 		if (with_fc) d_out = devmem<int16_t>(c * kRecvBlock);
-		h_len = pinned<int32_t>(kMaxRounds * c);
-		h_lensc = pinned<int32_t>(kMaxRounds * c);
-		d_len = devmem<int32_t>(c);
-		h_mode = pinned<uint8_t>(kMaxRounds * c);
-		h_modesc = pinned<uint8_t>(kMaxRounds * c);
-		d_mode = devmem<uint8_t>(c);
+		init_rounds(true, true);
 		h_olen = pinned<int32_t>(kMaxRounds * c);
 		if (with_fc) d_olen = devmem<int32_t>(c);
 		legs.assign(c, nullptr);
 		used.assign(c, 0);
-		req_drop.assign(c, 0), req_total.assign(c, 0), arm_drop.assign(c, 0), arm_total.assign(c, 0);
-		req_round.assign(c, 0);
+		drops.init(c);
 		zero_copy = zero_copy_rows();
-		no_early = getenv("MSMI355X_NO_EARLY_LAUNCH") != nullptr;
 	}
 	~RecvBank() override {
 		for (RecvLeg *l : legs)
@@ -111,71 +94,31 @@ struct RecvBank : Pool {
 		if (plc) mi_plc_destroy(plc);
 		if (fc) mi_flowctl_destroy(fc);
 	}
-	static void drop_entries(RecvLeg *l) {
+	void drop_entries(RecvLeg *l) {
 		for (int i = 0; i < l->nent; ++i)
 			if (l->ent[i].m) freemsg(l->ent[i].m);
 		for (int i = 0; i < l->nout; ++i)
 			if (l->out[i].m) freemsg(l->out[i].m);
-		l->nent = l->nout = l->staged = l->counted = 0;
-	}
-	bool scoped() const override { return true; }
-
-	// MS_AUDIO_FLOW_CONTROL_DROP requests that fell before round r of their stream (last: everything left) go to the device
-	void arm(int r, bool last) {
-		if (!have_req || !fc) return;
-		bool any = false, left = false;
-		for (int s = 0; s < capacity; ++s) {
-			arm_drop[(size_t)s] = arm_total[(size_t)s] = 0;
-			if (req_drop[(size_t)s] == 0 && req_total[(size_t)s] == 0) continue;
-			if (s < hi && parked(s)) {
-				left = true;
-				continue;
-			}
-			if (last || req_round[(size_t)s] <= r) {
-				arm_drop[(size_t)s] = req_drop[(size_t)s], arm_total[(size_t)s] = req_total[(size_t)s];
-				req_drop[(size_t)s] = req_total[(size_t)s] = 0;
-				any = true;
-			} else left = true;
-		}
-		if (any) MI_MUST(mi_flowctl_request_drop(fc, arm_drop.data(), arm_total.data()));
-		have_req = left;
+		l->nent = l->nout = l->counted = staged[(size_t)l->slot] = 0;
 	}
 
-	bool enqueue() override {
-		bool any = false;
-		const bool was_early = early;
-		if (early) { // already out since the end of the last graph walk
-			early = false;
-			any = early_any;
-		}
-		if (!was_early || staged_since) any |= enqueue_now(); // (what was staged after an early launch -- a stream that joined the bank later in that walk, a PLC run by the flush -- goes out now)
-		outstanding = false; // the hub waits for the stream right behind this
-		return any;
-	}
-	bool enqueue_now() {
+	// (the ticker's time is no input here: no mixer's clock in this bank)
+	bool enqueue_at(uint64_t) override {
 		mi_ctx *ctx = hub->ctx;
 		const size_t c = (size_t)capacity, UL = (size_t)hi;
 		if (outstanding) sync_stream(); // (rare: a second launch before the first was collected) the length rows are about to be rewritten
 		staged_since = false;
-		int rounds = 0;
+		const int rounds = this->rounds();
+		const int32_t *lrows[kMaxRounds];
+		for (int r = 0; r < rounds; ++r) lrows[r] = len_row(r); // (while `staged` still says who takes part)
 		for (size_t s = 0; s < UL; ++s) {
 			RecvLeg *leg = legs[s];
 			const bool in = leg && !parked((int)s);
 			if (leg && !in && leg->nent) staged_since = true; // (not this flush's business: it leaves with the ticker's own)
-			const int st = in ? leg->staged : 0;
-			rounds = std::max(rounds, st);
-			if (hub->scope) { // a detaching graph's slots alone: everybody else counts as empty in THIS launch and keeps what it staged
-				for (int r = 0; r < kMaxRounds; ++r) {
-					h_lensc[(size_t)r * c + s] = r < st ? h_len[(size_t)r * c + s] : 0;
-					h_modesc[(size_t)r * c + s] = r < st ? h_mode[(size_t)r * c + s] : (uint8_t)MI_PLC_NONE;
-				}
-			} else {
-				for (int r = leg ? leg->staged : 0; r < kMaxRounds; ++r) h_len[(size_t)r * c + s] = 0, h_mode[(size_t)r * c + s] = MI_PLC_NONE;
-			}
 			if (!in) continue;
 			// what the stream staged is on its way now: the flush that collects this launch hands it on
 			for (int i = 0; i < leg->nent && leg->nout < kRecvEntries; ++i) leg->out[leg->nout++] = leg->ent[i];
-			leg->nent = leg->staged = leg->counted = 0;
+			leg->nent = leg->counted = staged[s] = 0;
 		}
 		if (failed) { // a broken context is given no more work: received blocks pass as they came (undecoded: silence), a concealment is silence
 			for (int r = 0; r < rounds; ++r)
@@ -187,16 +130,10 @@ struct RecvBank : Pool {
 			return false;
 		}
 		for (int r = 0; r < rounds; ++r) {
-			const int32_t *lrow = (hub->scope ? h_lensc : h_len) + (size_t)r * c;
-			const uint8_t *mrow = (hub->scope ? h_modesc : h_mode) + (size_t)r * c;
+			const int32_t *lrow = lrows[r];
 			int16_t *res = h_pcm + (size_t)r * c * kRecvBlock; // where this round's blocks end up
-			const int32_t *dl = lrow;
-			const uint8_t *dm = mrow;
-			if (!zero_copy) {
-				MI_MUST(mi_copy_h2d_pinned(ctx, d_len, lrow, c * 4));
-				MI_MUST(mi_copy_h2d_pinned(ctx, d_mode, mrow, c));
-				dl = d_len, dm = d_mode;
-			}
+			const int32_t *dl = zero_copy ? lrow : on_device(lrow);
+			const uint8_t *dm = zero_copy ? mode_row(r) : on_device(mode_row(r));
 			int16_t *work = d_pcm;
 			if (law >= 0) { // alaw_dec_process alaw.c:208-221: the packet's code bytes -> PCM, on the device from here on
 				const uint8_t *codes = h_codes + (size_t)r * c * kRecvBlock;
@@ -214,7 +151,7 @@ struct RecvBank : Pool {
 			MI_MUST(mi_plc_process(plc, work, kRecvBlock, dl, dm));
 			++launches;
 			if (fc) {
-				arm(r, false);
+				drops.arm(*this, fc, r, false);
 				int16_t *to = zero_copy ? res : d_out;
 				int32_t *ol = zero_copy ? h_olen + (size_t)r * c : d_olen;
 				MI_MUST(mi_flowctl_process(fc, work, kRecvBlock, dl, kRecvBlock, to, kRecvBlock, ol));
@@ -228,7 +165,7 @@ struct RecvBank : Pool {
 				for (size_t s = 0; s < UL; ++s) h_olen[(size_t)r * c + s] = lrow[s];
 			}
 		}
-		if (fc) arm(rounds, true);
+		drops.arm(*this, fc, rounds, true);
 		launched_rounds = std::max(launched_rounds, rounds);
 		outstanding |= rounds > 0;
 		return rounds > 0;
@@ -266,7 +203,7 @@ struct RecvBank : Pool {
 				o = allocb((size_t)left * 2, 0);
 				memcpy(o->b_wptr, row, (size_t)left * 2);
 				o->b_wptr += (size_t)left * 2;
-				if (e.kind == MI_PLC_CONCEAL) o->reserved2 |= 1u << 2; // mblk_set_plc_flag msqueue.h:113
+				if (e.kind == MI_PLC_CONCEAL) o->reserved2 |= kMblkPlcFlag;
 				if (e.m) {
 					mblk_meta_copy(e.m, o);
 					freemsg(e.m);
@@ -276,13 +213,7 @@ struct RecvBank : Pool {
 		}
 		leg->nout = 0;
 	}
-	// a graph is being detached between two ticks: rows staged in the last walk whose launches have not left go now
-	void launch_staged() {
-		if (failed || !staged_since) return;
-		const bool more = enqueue_now();
-		early_any = early ? (early_any || more) : more;
-		early = true;
-	}
+	// (unlike ConfBank's: emits even when nothing was outstanding, and whatever `failed` says)
 	void deliver_in_flight(int slot) {
 		if (outstanding || early) {
 			sync_stream();
@@ -301,22 +232,20 @@ void recv_disqualify(RecvLeg *leg) {
 }
 
 // every stream of the bank has had its PLC run in this tick's walk: everything the tick will stage IS staged, the launches leave now
+// (not while the hub's flush is what runs the PLC -- a pump behind the decoder: unlike ConfBank, whose mixers count there too)
 void recv_walked(RecvBank *b, RecvLeg *leg) {
-	if (b->no_early || b->failed || b->early || !b->hub->ticker || b->hub->in_flush) return;
-	const uint32_t tick = b->hub->ticker->ticks;
-	if (b->walk_epoch != tick) b->walk_epoch = tick, b->walked = 0;
-	if (leg->walk_stamp == (uint64_t)tick + 1) return;
-	leg->walk_stamp = (uint64_t)tick + 1;
-	if (++b->walked < b->in_use) return;
-	b->early_any = b->enqueue_now();
-	b->early = true;
+	if (!b->walk_begins(false)) return;
+	const uint64_t stamp = (uint64_t)b->hub->ticker->ticks + 1;
+	if (leg->walk_stamp == stamp) return;
+	leg->walk_stamp = stamp;
+	b->walk_counted();
 }
 
 // a row for one more block of the stream, or NULL when the launch rounds of this flush are taken
 int recv_new_round(RecvBank *b, RecvLeg *leg, int mode, int n) {
-	if (leg->staged >= kMaxRounds || leg->nent >= kRecvEntries) return -1;
+	if (b->staged[(size_t)leg->slot] >= kMaxRounds || leg->nent >= kRecvEntries) return -1;
 	const size_t c = (size_t)b->capacity;
-	const int r = leg->staged++;
+	const int r = b->staged[(size_t)leg->slot]++;
 	b->h_len[(size_t)r * c + (size_t)leg->slot] = n;
 	b->h_mode[(size_t)r * c + (size_t)leg->slot] = (uint8_t)mode;
 	return r;
@@ -399,32 +328,24 @@ void recv_plc_walk(MSFilter *f, PlcFilter *d) {
 		}
 		any = true;
 	}
-	if (d->concealer->required(f->ticker->time)) { // :117-166
-		const int buff = d->rate * nch * f->ticker->interval / 1000; // samples
-		if (d->cng_set || d->cng_running) { // comfort noise: a silent block flagged as such, no concealer involved
-			if (leg->nent < kRecvEntries) {
-				mblk_t *o = allocb((size_t)buff * 2, 0);
-				memset(o->b_wptr, 0, (size_t)buff * 2);
-				o->b_wptr += (size_t)buff * 2;
-				o->reserved2 |= 1u << 3; // mblk_set_cng_flag msqueue.h:116
-				leg->ent[leg->nent++] = RecvEntry{0, 0, buff, o};
-				leg->counted = leg->nent;
-			}
-			if (d->cng_set) {
-				d->cng_set = false;
-				d->cng_running = true;
-			}
-			any = true;
-		} else if (buff <= kRecvBlock) {
-			const int r = recv_new_round(b, leg, MI_PLC_CONCEAL, buff);
-			if (r >= 0) {
-				leg->ent[leg->nent++] = RecvEntry{MI_PLC_CONCEAL, (uint8_t)r, buff, nullptr};
-				leg->counted = leg->nent;
-			} else g_late_events.fetch_add(1, std::memory_order_relaxed); // (the rounds are taken by a burst of packets: this concealment is skipped, counted)
-			any = true;
-		}
-		d->concealer->inc_sample_time(f->ticker->time, (uint32_t)f->ticker->interval, false);
-	}
+	plc_tick_concealment(
+	    f, d, nch,
+	    [&](mblk_t *o, int buff) {
+		    if (leg->nent < kRecvEntries) {
+			    leg->ent[leg->nent++] = RecvEntry{0, 0, buff, o};
+			    leg->counted = leg->nent;
+		    } else freemsg(o); // (the stream's entries of this flush are taken)
+		    any = true;
+	    },
+	    [&](int buff) {
+		    if (buff > kRecvBlock) return;
+		    const int r = recv_new_round(b, leg, MI_PLC_CONCEAL, buff);
+		    if (r >= 0) {
+			    leg->ent[leg->nent++] = RecvEntry{MI_PLC_CONCEAL, (uint8_t)r, buff, nullptr};
+			    leg->counted = leg->nent;
+		    } else g_late_events.fetch_add(1, std::memory_order_relaxed); // (the rounds are taken by a burst of packets: this concealment is skipped, counted)
+		    any = true;
+	    });
 	if (any || leg->nent) {
 		b->staged_since = true;
 		request_flush(f);
@@ -436,10 +357,7 @@ void recv_plc_walk(MSFilter *f, PlcFilter *d) {
 void recv_flow_drop(RecvLeg *leg, uint32_t drop, uint32_t total) {
 	RecvBank *b = leg->bank;
 	const size_t s = (size_t)leg->slot;
-	if (!b->fc || b->req_drop[s] || b->req_total[s]) return; // (a request is ignored while one is pending, as in FlowPool)
-	b->req_drop[s] = drop, b->req_total[s] = total;
-	b->req_round[s] = leg->staged;
-	b->have_req = true;
+	if (b->fc) b->drops.request(s, drop, total, b->staged[s]);
 }
 void recv_flow_config(RecvLeg *leg, const MSAudioFlowControlConfig *cfg) {
 	RecvBank *b = leg->bank;
@@ -517,7 +435,7 @@ bool recv_try_fuse(MSFilter *head) {
 		b->release(s);
 		return false;
 	}
-	b->req_drop[(size_t)s] = b->req_total[(size_t)s] = 0;
+	b->drops.forget((size_t)s);
 	RecvLeg *leg = new RecvLeg();
 	leg->bank = b, leg->slot = s;
 	leg->dec = dec, leg->plc = plcf, leg->fc = fcf, leg->mixer = mixer, leg->tail = tail;
@@ -575,12 +493,12 @@ void recv_release(RecvLeg *leg, bool keep_running) {
 	if (b->legs[(size_t)s] != leg) return;
 	if (leg->nent && !b->failed) { // staged in a walk whose launch has not left (a bank without early launch): it leaves now
 		b->staged_since = true;
-		b->launch_staged();
+		b->launch_staged(true);
 	}
 	b->deliver_in_flight(s);
-	RecvBank::drop_entries(leg);
+	b->drop_entries(leg);
 	b->legs[(size_t)s] = nullptr;
-	b->req_drop[(size_t)s] = b->req_total[(size_t)s] = 0;
+	b->drops.forget((size_t)s);
 	if (leg->dec) {
 		MapFilter *dd = (MapFilter *)leg->dec->data;
 		dd->rleg = nullptr;
@@ -607,7 +525,7 @@ void deliver_recv_in_scope(TickerHub &h) {
 		bool ours = false;
 		for (int s = 0; s < b->hi && !ours; ++s) ours = b->owner[(size_t)s] && h.scope->count(b->owner[(size_t)s]);
 		if (!ours) continue;
-		b->launch_staged();
+		b->launch_staged(true); // (unlike ConfBank's: whether or not the hub still has its ticker)
 		for (int s = 0; s < b->hi; ++s)
 			if (b->owner[(size_t)s] && h.scope->count(b->owner[(size_t)s])) b->deliver_in_flight(s);
 	}

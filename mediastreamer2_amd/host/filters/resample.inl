@@ -1,16 +1,15 @@
 // filters/resample.inl -- MSResample facade (src/audiofilters/msresample.c).
 // Part of the single translation unit filters.cpp (included inside its anonymous namespace, after the pool / hub
-// infrastructure); not compiled on its own.
+// infrastructure and round_bank.inl, which its bank's round staging comes from); not compiled on its own.
 
 // =================================================================== resampler
-struct ResamplePool : Pool {
+struct ResamplePool : RoundBank {
 	uint32_t in_rate, out_rate;
 	int in_len, ostride;
 	mi_resampler *r = nullptr;
 	int16_t *h_in, *h_out, *d_in, *d_out;
 	int32_t *h_olen, *d_olen;
-	uint8_t *h_run, *d_run;
-	std::vector<int> staged, ready;
+	uint8_t *h_run, *d_run; // (the launch takes a run MASK, not lengths: the base's rows would have to be converted round by round)
 	ResamplePool(int cap, uint32_t ir, uint32_t orate) : in_rate(ir), out_rate(orate) {
 		Building b(this, cap);
 		if (!failed) MI_MUST(mi_resampler_create(hub->ctx, capacity, ir, orate, 3 /* SPEEX_RESAMPLER_QUALITY_VOIP */, &r));
@@ -25,8 +24,7 @@ struct ResamplePool : Pool {
 		d_out = devmem<int16_t>(c * ostride);
 		d_olen = devmem<int32_t>(c);
 		d_run = devmem<uint8_t>(c);
-		staged.assign(c, 0);
-		ready.assign(c, 0);
+		init_rounds(false);
 	}
 	~ResamplePool() override {
 		if (r) mi_resampler_destroy(r);
@@ -34,9 +32,7 @@ struct ResamplePool : Pool {
 	bool enqueue() override {
 		mi_ctx *ctx = hub->ctx;
 		const size_t c = (size_t)capacity, u = (size_t)hi; // rows [0, hi) are all that was ever handed out
-		int maxr = 0;
-		for (int s = 0; s < hi; ++s)
-			if (!parked(s)) maxr = std::max(maxr, staged[(size_t)s]);
+		const int maxr = rounds();
 		for (int r_ = 0; r_ < maxr; ++r_) {
 			for (int s = 0; s < capacity; ++s) h_run[r_ * c + s] = s < hi && staged[(size_t)s] > r_ && !parked(s);
 			MI_MUST(mi_copy_h2d_pinned(ctx, d_in, h_in + r_ * c * in_len, u * in_len * 2));
@@ -47,14 +43,7 @@ struct ResamplePool : Pool {
 		}
 		return maxr > 0;
 	}
-	void finish() override {
-		for (int s = 0; s < hi; ++s) {
-			if (parked(s)) continue;
-			ready[(size_t)s] = failed ? 0 : staged[(size_t)s]; // a failed launch delivers nothing (late event counted)
-			staged[(size_t)s] = 0;
-		}
-	}
-	bool scoped() const override { return true; }
+	void finish() override { settle(!failed); } // a failed launch delivers nothing (late event counted)
 	void emit(MSFilter *f, int slot) override;
 };
 

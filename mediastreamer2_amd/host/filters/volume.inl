@@ -1,6 +1,6 @@
 // filters/volume.inl -- MSVolume facade (src/audiofilters/msvolume.c).
 // Part of the single translation unit filters.cpp (included inside its anonymous namespace, after the pool / hub
-// infrastructure); not compiled on its own.
+// infrastructure and round_bank.inl, which its bank's round staging comes from); not compiled on its own.
 
 // ====================================================================== volume
 struct Extremum { // OrtpExtremum (oRTP utils): windowed min/max, period in ms
@@ -33,16 +33,13 @@ struct Extremum { // OrtpExtremum (oRTP utils): windowed min/max, period in ms
 	}
 };
 
-struct VolumePool : Pool {
+struct VolumePool : RoundBank {
 	int rate, cap_samples;
 	mi_volume *v = nullptr;
 	int16_t *h_buf, *d_buf;
-	int32_t *h_n, *d_n;
-	int32_t *h_nsc; // the rounds' count rows while a detaching graph's slots alone are flushed (the others' h_n rows stay as staged)
 	mi_volume_state *h_state; // pinned: the meters come back with the blocks, no synchronisation of their own
 	bool fetched = false;
 	int rounds_fetched = 0;
-	std::vector<int> staged, ready;
 	// [kMaxRounds][capacity]: the row is a COPY for the meter -- the block itself went on in the walk, untouched (volume_process: an
 	// MSVolume that is a meter and nothing else); emit() records its energy and makes no block of it
 	std::vector<uint8_t> quiet;
@@ -67,13 +64,9 @@ struct VolumePool : Pool {
 		cap_samples = (cap_samples + 7) & ~7;
 		const size_t c = (size_t)capacity;
 		h_buf = pinned<int16_t>(kMaxRounds * c * cap_samples);
-		h_n = pinned<int32_t>(kMaxRounds * c);
-		h_nsc = pinned<int32_t>(kMaxRounds * c);
+		init_rounds();
 		d_buf = devmem<int16_t>(c * cap_samples);
-		d_n = devmem<int32_t>(c);
 		h_state = pinned<mi_volume_state>(kMaxRounds * c); // row r: the meters behind round r (every chunk's energy is recorded, msvolume.c:405-406)
-		staged.assign(c, 0);
-		ready.assign(c, 0);
 		quiet.assign(kMaxRounds * c, 0);
 		mi_volume_params p;
 		mi_volume_default_params(&p);
@@ -122,24 +115,14 @@ struct VolumePool : Pool {
 			MI_MUST(mi_volume_set_state(v, s, e - s, &state[(size_t)s]));
 			s = e;
 		}
-		int maxr = 0;
-		for (int s = 0; s < hi; ++s)
-			if (!parked(s)) maxr = std::max(maxr, staged[(size_t)s]);
+		const int maxr = rounds();
 		for (int r = 0; r < maxr; ++r) {
-			const int32_t *nrow = h_n + r * c;
-			if (hub->scope) { // a detaching graph's slots alone: everybody else counts as empty in THIS launch and keeps what it staged
-				for (int s = 0; s < capacity; ++s) h_nsc[r * c + s] = (s < hi && staged[(size_t)s] > r && !parked(s)) ? h_n[r * c + s] : 0;
-				nrow = h_nsc + r * c;
-			} else {
-				for (int s = 0; s < capacity; ++s)
-					if (s >= hi || staged[(size_t)s] <= r) h_n[r * c + s] = 0;
-			}
+			const int32_t *nrow = len_row(r);
 			if (zero_copy_rows()) { // the launch reads and levels the blocks where they lie in pinned memory: what crosses PCIe is the audio, not the rows' capacity
 				MI_MUST(mi_volume_process(v, h_buf + r * c * cap_samples, cap_samples, cap_samples, nrow));
 			} else {
 				MI_MUST(mi_copy_h2d_pinned(ctx, d_buf, h_buf + r * c * cap_samples, u * cap_samples * 2));
-				MI_MUST(mi_copy_h2d_pinned(ctx, d_n, nrow, c * 4));
-				MI_MUST(mi_volume_process(v, d_buf, cap_samples, cap_samples, d_n));
+				MI_MUST(mi_volume_process(v, d_buf, cap_samples, cap_samples, on_device(nrow)));
 				MI_MUST(mi_copy_d2h_pinned(ctx, h_buf + r * c * cap_samples, d_buf, u * cap_samples * 2));
 			}
 			if (!failed) MI_MUST(mi_volume_get_state_async(v, 0, hi, h_state + r * c)); // meters for the app thread
@@ -153,13 +136,8 @@ struct VolumePool : Pool {
 			for (int s = 0; s < hi; ++s)
 				if (!(state_dirty[(size_t)s] && gain_patch[(size_t)s].whole)) state[(size_t)s] = h_state[(size_t)(rounds_fetched - 1) * capacity + s];
 		fetched = false;
-		for (int s = 0; s < hi; ++s) {
-			if (parked(s)) continue;
-			ready[(size_t)s] = staged[(size_t)s]; // after a failed launch the staged blocks leave as they came (unity gain)
-			staged[(size_t)s] = 0;
-		}
+		settle(); // (after a failed launch the staged blocks leave as they came: unity gain)
 	}
-	bool scoped() const override { return true; }
 	void flushed() override;
 	void emit(MSFilter *f, int slot) override;
 };
@@ -496,7 +474,7 @@ void volume_process(MSFilter *f) { // msvolume.c:471-514
 			}
 			ms_bufferizer_read(d->buffer, (uint8_t *)(p->h_buf + (p->staged[s] * c + s) * p->cap_samples), nbytes);
 			p->quiet[p->staged[s] * c + s] = 0;
-			p->h_n[p->staged[s] * c + s] = d->nsamples;
+			p->h_len[p->staged[s] * c + s] = d->nsamples;
 			p->staged[s]++;
 		}
 	} else { // :505-512 light path: one chunk per mblk.  A block longer than a batch row (20 ms and more than 960 samples)
@@ -538,7 +516,7 @@ void volume_process(MSFilter *f) { // msvolume.c:471-514
 				break;
 			}
 			p->quiet[p->staged[s] * c + s] = row_quiet;
-			p->h_n[p->staged[s] * c + s] = n;
+			p->h_len[p->staged[s] * c + s] = n;
 			p->staged[s]++;
 		}
 	}
@@ -549,7 +527,7 @@ void VolumePool::emit(MSFilter *f, int slot) {
 	VolumeData *d = (VolumeData *)f->data;
 	const size_t c = (size_t)capacity, s = (size_t)slot;
 	for (int r = 0; r < ready[s]; ++r) {
-		const int n = h_n[r * c + s];
+		const int n = h_len[r * c + s];
 		if (quiet[r * c + s]) continue; // (the block went on in the walk)
 		mblk_t *om = allocb((size_t)n * 2, 0);
 		memcpy(om->b_wptr, h_buf + (r * c + s) * cap_samples, (size_t)n * 2);
