@@ -863,3 +863,109 @@ class Session(_Batch):
         db = np.zeros(nconf, np.float32)
         check(self.ctx.L.mi_session_active_speakers(self.h, C.c_uint64(int(now_ms)), _ptr(win), _ptr(db)))
         return win, db
+
+
+class BridgeConfig(C.Structure):
+    _fields_ = [("nstreams", C.c_int32), ("members_per_conference", C.c_int32), ("rate", C.c_int32),
+                ("in_codec", C.c_int32), ("out_codec", C.c_int32), ("plc", C.c_int32)]
+
+
+class Bridge(_Batch):
+    """mi_bridge (include/msmi355x_bridge.h): a conference server's member chain -- [G.711 ->] MSVolume -> conference mix
+    [-> G.711], no echo canceller -- one launch per tick, fed from host buffers, three ticks in flight.  ctx=None: a
+    Context of its own on `device`."""
+    _destroy = "mi_bridge_destroy"
+
+    def __init__(self, ctx, nstreams, members=32, rate=8000, in_codec=MI_SESSION_PCMU, out_codec=MI_SESSION_PCMU, plc=False, device=0):
+        self._own_ctx = ctx is None
+        self.ctx = ctx = Context(device) if ctx is None else ctx
+        cfg = BridgeConfig()
+        ctx.L.mi_bridge_default_config(C.byref(cfg))
+        cfg.nstreams, cfg.members_per_conference, cfg.rate = nstreams, members, rate
+        cfg.in_codec, cfg.out_codec, cfg.plc = in_codec, out_codec, int(plc)
+        h = C.c_void_p()
+        check(ctx.L.mi_bridge_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        self.n, self.members, self.len = nstreams, members, rate // 100
+        self.in_dtype = C.c_uint8 if in_codec else C.c_int16
+        self.out_dtype = C.c_uint8 if out_codec else C.c_int16
+
+    def close(self):
+        super().close()
+        if getattr(self, "_own_ctx", False):
+            self.ctx.close()
+            self._own_ctx = False
+
+    def _view(self, ptr, ctype, *shape):
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=shape)
+
+    def tick_bytes(self):
+        a, b = C.c_int32(), C.c_int32()
+        check(self.ctx.L.mi_bridge_tick_bytes(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def acquire(self):
+        """numpy views of the pinned staging of the next tick: (in [n, len] code words or PCM, present [n] uint8 preset to 1)."""
+        pi, pp = C.c_void_p(), C.c_void_p()
+        check(self.ctx.L.mi_bridge_acquire(self.h, C.byref(pi), C.byref(pp)))
+        return self._view(pi, self.in_dtype, self.n, self.len), self._view(pp, C.c_uint8, self.n)
+
+    def submit(self):
+        check(self.ctx.L.mi_bridge_submit(self.h))
+
+    def collect(self):
+        """numpy view of the oldest in-flight tick's output [n, len] (pinned; valid for three more submits)."""
+        po = C.c_void_p()
+        check(self.ctx.L.mi_bridge_collect(self.h, C.byref(po)))
+        return self._view(po, self.out_dtype, self.n, self.len)
+
+    def in_flight(self):
+        return self.ctx.L.mi_bridge_in_flight(self.h)
+
+    def set_controls(self, flags=None, gain=None):
+        f = None if flags is None else np.ascontiguousarray(flags, np.uint8)
+        g = None if gain is None else np.ascontiguousarray(gain, np.float32)
+        check(self.ctx.L.mi_bridge_set_controls(self.h, _ptr(f), _ptr(g)))
+
+    def set_volume_params(self, params, first=0):
+        arr = (VolumeParams * len(params))(*params)
+        check(self.ctx.L.mi_bridge_set_volume_params(self.h, first, len(params), arr))
+
+    def reset_streams(self, first, count):
+        check(self.ctx.L.mi_bridge_reset_streams(self.h, first, count))
+
+    def levels(self):
+        out = np.zeros(self.n, np.float32)
+        check(self.ctx.L.mi_bridge_get_levels(self.h, _ptr(out)))
+        return out
+
+    def add_member(self, stream):
+        check(self.ctx.L.mi_bridge_add_member(self.h, int(stream)))
+
+    def remove_member(self, stream):
+        check(self.ctx.L.mi_bridge_remove_member(self.h, int(stream)))
+
+    def member_count(self, conference):
+        n = self.ctx.L.mi_bridge_member_count(self.h, int(conference))
+        check(min(n, 0))
+        return n
+
+    def active_speakers(self, now_ms=0):
+        """(winner stream per conference or -1, its MS_VOLUME_GET_MAX in dBm0): audioconference.c:436-452"""
+        nconf = self.n // self.members
+        win = np.zeros(nconf, np.int32)
+        db = np.zeros(nconf, np.float32)
+        check(self.ctx.L.mi_bridge_active_speakers(self.h, C.c_uint64(int(now_ms)), _ptr(win), _ptr(db)))
+        return win, db
+
+    def volume_state(self, first=0, count=None):
+        count = self.n - first if count is None else count
+        arr = (VolumeState * count)()
+        check(self.ctx.L.mi_bridge_get_volume_state(self.h, first, count, arr))
+        return arr
+
+    def volume_max(self, first=0, count=None):
+        count = self.n - first if count is None else count
+        out = np.zeros(count, np.float32)
+        check(self.ctx.L.mi_bridge_get_volume_max(self.h, first, count, _ptr(out)))
+        return out

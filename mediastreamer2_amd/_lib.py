@@ -55,6 +55,15 @@ EXPORTS = [
     "mi_fifo_create", "mi_fifo_destroy", "mi_fifo_push", "mi_fifo_push_gated", "mi_fifo_pop", "mi_fifo_pop_frames", "mi_fifo_push_frames", "mi_fifo_levels", "mi_fifo_push_lead", "mi_fifo_phase_of", "mi_fifo_overflows", "mi_fifo_reset", "mi_fifo_reset_range", "mi_fifo_reset_range_at", "mi_fifo_push_silence", "mi_fifo_snapshot", "mi_fifo_export_range", "mi_fifo_import_range",
 ]
 
+# every symbol include/msmi355x_bridge.h declares: the bridge sessions, in the same library
+BRIDGE_EXPORTS = [
+    "mi_bridge_default_config", "mi_bridge_create", "mi_bridge_destroy", "mi_bridge_tick_bytes",
+    "mi_bridge_acquire", "mi_bridge_submit", "mi_bridge_collect", "mi_bridge_in_flight",
+    "mi_bridge_set_controls", "mi_bridge_set_volume_params", "mi_bridge_reset_streams",
+    "mi_bridge_add_member", "mi_bridge_remove_member", "mi_bridge_member_count",
+    "mi_bridge_get_levels", "mi_bridge_active_speakers", "mi_bridge_get_volume_state", "mi_bridge_get_volume_max",
+]
+
 
 class VolumeParams(C.Structure):
     _fields_ = [
@@ -263,6 +272,26 @@ def load():
         L.mi_session_member_count.argtypes = [vp, i32]
         L.mi_session_active_speakers.argtypes = [vp, C.c_uint64, vp, vp]
         L.mi_session_reset_streams.argtypes = [vp, i32, i32]
+    L.mi_bridge_default_config.argtypes = [vp]
+    L.mi_bridge_default_config.restype = None
+    L.mi_bridge_create.argtypes = [vp, vp, pp]
+    L.mi_bridge_destroy.argtypes = [vp]
+    L.mi_bridge_destroy.restype = None
+    L.mi_bridge_tick_bytes.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.mi_bridge_acquire.argtypes = [vp, pp, pp]
+    L.mi_bridge_submit.argtypes = [vp]
+    L.mi_bridge_collect.argtypes = [vp, pp]
+    L.mi_bridge_in_flight.argtypes = [vp]
+    L.mi_bridge_set_controls.argtypes = [vp, vp, vp]
+    L.mi_bridge_set_volume_params.argtypes = [vp, i32, i32, C.POINTER(VolumeParams)]
+    L.mi_bridge_reset_streams.argtypes = [vp, i32, i32]
+    L.mi_bridge_add_member.argtypes = [vp, i32]
+    L.mi_bridge_remove_member.argtypes = [vp, i32]
+    L.mi_bridge_member_count.argtypes = [vp, i32]
+    L.mi_bridge_get_levels.argtypes = [vp, vp]
+    L.mi_bridge_active_speakers.argtypes = [vp, C.c_uint64, vp, vp]
+    L.mi_bridge_get_volume_state.argtypes = [vp, i32, i32, C.POINTER(VolumeState)]
+    L.mi_bridge_get_volume_max.argtypes = [vp, i32, i32, vp]
     if hasattr(L, "mi_fifo_create"):
         L.mi_fifo_create.argtypes = [vp, i32, i32, pp]
         L.mi_fifo_destroy.argtypes = [vp]

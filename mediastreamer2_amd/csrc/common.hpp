@@ -115,6 +115,16 @@ struct MixerView {
 struct mi_mixer;
 void mi_mixer_view(const mi_mixer *m, MixerView *v);
 
+// What the bridge's fused tick kernel (bridge.hip) needs of an mi_volume: parameters, running state and the one-second
+// maximum windows of its streams (x = current maximum, y = ms since the window started, < 0: not started)
+struct VolumeView {
+	const mi_volume_params *params = nullptr;
+	mi_volume_state *state = nullptr;
+	float2 *win = nullptr;
+	int nstreams = 0, sample_rate = 0, device = -1;
+};
+void mi_volume_view(const mi_volume *v, VolumeView *out);
+
 struct mi_ctx {
 	int device = 0;
 	hipStream_t stream = nullptr;

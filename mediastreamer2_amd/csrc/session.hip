@@ -10,6 +10,7 @@
 // tick computes and the one before comes down; events order the three, hipGraphs (one per buffer slot) replay the
 // kernel sequence.  Pinned host buffers belong to the session: the caller fills / reads them in place.
 #include "common.hpp"
+#include "conference.hpp"
 
 #include <cmath>
 
@@ -468,33 +469,15 @@ int mi_session_member_count(const mi_session *s, int conference) {
 	return c;
 }
 
-// ms_audio_conference_process_events' election in mixer mode (:436-452): per conference the unmuted member whose
-// MS_VOLUME_GET_MAX -- the maximum of the smoothed energy over a one-second window (msvolume.c:143-148,:402-406), in
-// dBm0 -- is the largest and above -30 dB (audioconference.c:31).  now_ms: the caller's clock (the ticker's time).
+// ms_audio_conference_process_events' election in mixer mode (:436-452, mi::elect_active_speakers).  now_ms: the caller's
+// clock (the ticker's time).
 int mi_session_active_speakers(mi_session *s, uint64_t now_ms, int32_t *h_winner, float *h_max_db) {
 	MI_CHECK_ARG(s && h_winner);
 	(void)now_ms; // the windows run on the device, one record per tick (msvolume.c:404)
 	std::vector<float> mx((size_t)s->n);
 	const int rc = mi_volume_get_max(s->vol, 0, s->n, mx.data());
 	if (rc != MI_OK) return rc;
-	const int mm = s->cfg.members_per_conference;
-	for (int c = 0; c < s->nconf; ++c) {
-		float best = -120.f; // MS_VOLUME_DB_LOWEST
-		int win = -1;
-		uint32_t win_joined = 0;
-		for (int m = 0; m < mm; ++m) {
-			const size_t i = (size_t)c * mm + m;
-			const uint8_t f = s->flags[i];
-			if (!(f & MI_MIX_LINKED) || !(f & MI_MIX_ACTIVE)) continue; // not plumbed / muted (:445)
-			const float lin = mx[i];
-			const float db = lin == 0 ? -120.f : 10 * log10f(lin); // ms_volume_linear_to_dbm0 msvolume.c:565-568
-			if (db <= -30.0f) continue;
-			// the list is walked in joining order and a later member must be strictly louder (:449): of equals, the earliest joiner
-			if (db > best || (db == best && win >= 0 && s->joined[i] < win_joined)) best = db, win = (int)i, win_joined = s->joined[i];
-		}
-		h_winner[c] = win;
-		if (h_max_db) h_max_db[c] = best;
-	}
+	mi::elect_active_speakers(mx.data(), s->flags.data(), s->joined.data(), s->nconf, s->cfg.members_per_conference, h_winner, h_max_db);
 	return MI_OK;
 }
 
