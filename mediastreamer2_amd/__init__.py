@@ -763,6 +763,55 @@ class PlcBatch(_Batch):
         check(self.ctx.L.mi_plc_reset(self.h, first, self.nstreams - first if count is None else count))
 
 
+class _ConferenceBatch(_Batch):
+    """What Session and Bridge share through their mi_<_prefix>_* entry points: submit / in_flight of the tick ring and
+    MSAudioConference's control plane over self.n streams in conferences of self.members."""
+    _prefix = None
+
+    def _call(self, name, *args):
+        return getattr(self.ctx.L, f"mi_{self._prefix}_{name}")(self.h, *args)
+
+    def submit(self):
+        check(self._call("submit"))
+
+    def in_flight(self):
+        return self._call("in_flight")
+
+    def set_controls(self, flags=None, gain=None):
+        f = None if flags is None else np.ascontiguousarray(flags, np.uint8)
+        g = None if gain is None else np.ascontiguousarray(gain, np.float32)
+        check(self._call("set_controls", _ptr(f), _ptr(g)))
+
+    def reset_streams(self, first, count):
+        check(self._call("reset_streams", first, count))
+
+    def levels(self):
+        out = np.zeros(self.n, np.float32)
+        check(self._call("get_levels", _ptr(out)))
+        return out
+
+    def add_member(self, stream):
+        """ms_audio_conference_add_member: a NEW endpoint takes the slot (fresh per-leg state), its mixer pin is plumbed."""
+        check(self._call("add_member", int(stream)))
+
+    def remove_member(self, stream):
+        """ms_audio_conference_remove_member: the pin is unplumbed; the other members carry on untouched."""
+        check(self._call("remove_member", int(stream)))
+
+    def member_count(self, conference):
+        n = self._call("member_count", int(conference))
+        check(min(n, 0))
+        return n
+
+    def active_speakers(self, now_ms):
+        """(winner stream per conference or -1, its MS_VOLUME_GET_MAX in dBm0): audioconference.c:436-452"""
+        nconf = self.n // self.members
+        win = np.zeros(nconf, np.int32)
+        db = np.zeros(nconf, np.float32)
+        check(self._call("active_speakers", C.c_uint64(int(now_ms)), _ptr(win), _ptr(db)))
+        return win, db
+
+
 class SessionConfig(C.Structure):
     _fields_ = [("nstreams", C.c_int32), ("members_per_conference", C.c_int32), ("in_rate", C.c_int32),
                 ("rate", C.c_int32), ("tail_ms", C.c_int32), ("agc", C.c_int32), ("use_graphs", C.c_int32),
@@ -773,10 +822,10 @@ class SessionConfig(C.Structure):
 MI_SESSION_PCM16, MI_SESSION_PCMA, MI_SESSION_PCMU = 0, 1, 2
 
 
-class Session(_Batch):
+class Session(_ConferenceBatch):
     """mi_session: the chained path ([G.711 ->] resample -> AEC -> AGC -> conference mix [-> resample -> G.711]) fed
     from host buffers, three ticks in flight on three HIP streams."""
-    _destroy = "mi_session_destroy"
+    _destroy, _prefix = "mi_session_destroy", "session"
 
     def __init__(self, ctx, nstreams, members=32, in_rate=16000, rate=48000, tail_ms=128, agc=True, use_graphs=True,
                  mic_codec=0, out_rate=0, out_codec=0, ref_loopback=False, ref_delay_ms=0, plc=False, stagger=False):
@@ -818,51 +867,11 @@ class Session(_Batch):
         check(self.ctx.L.mi_session_events(self.h, C.byref(pe)))
         return np.ctypeslib.as_array(C.cast(pe, C.POINTER(C.c_uint8)), shape=(self.n,))
 
-    def submit(self):
-        check(self.ctx.L.mi_session_submit(self.h))
-
     def collect(self):
         """numpy view of the oldest in-flight tick's output [n, out_len] (pinned; valid for three more submits)."""
         po = C.c_void_p()
         check(self.ctx.L.mi_session_collect(self.h, C.byref(po)))
         return self._view(po, self.out_len, self.out_dtype)
-
-    def in_flight(self):
-        return self.ctx.L.mi_session_in_flight(self.h)
-
-    def set_controls(self, flags=None, gain=None):
-        f = None if flags is None else np.ascontiguousarray(flags, np.uint8)
-        g = None if gain is None else np.ascontiguousarray(gain, np.float32)
-        check(self.ctx.L.mi_session_set_controls(self.h, _ptr(f), _ptr(g)))
-
-    def reset_streams(self, first, count):
-        check(self.ctx.L.mi_session_reset_streams(self.h, first, count))
-
-    def levels(self):
-        out = np.zeros(self.n, np.float32)
-        check(self.ctx.L.mi_session_get_levels(self.h, _ptr(out)))
-        return out
-
-    def add_member(self, stream):
-        """ms_audio_conference_add_member: a NEW endpoint takes the slot (fresh per-leg state), its mixer pin is plumbed."""
-        check(self.ctx.L.mi_session_add_member(self.h, int(stream)))
-
-    def remove_member(self, stream):
-        """ms_audio_conference_remove_member: the pin is unplumbed; the other members carry on untouched."""
-        check(self.ctx.L.mi_session_remove_member(self.h, int(stream)))
-
-    def member_count(self, conference):
-        n = self.ctx.L.mi_session_member_count(self.h, int(conference))
-        check(min(n, 0))
-        return n
-
-    def active_speakers(self, now_ms):
-        """(winner stream per conference or -1, its MS_VOLUME_GET_MAX in dBm0): audioconference.c:436-452"""
-        nconf = self.n // self.members
-        win = np.zeros(nconf, np.int32)
-        db = np.zeros(nconf, np.float32)
-        check(self.ctx.L.mi_session_active_speakers(self.h, C.c_uint64(int(now_ms)), _ptr(win), _ptr(db)))
-        return win, db
 
 
 class BridgeConfig(C.Structure):
@@ -870,11 +879,11 @@ class BridgeConfig(C.Structure):
                 ("in_codec", C.c_int32), ("out_codec", C.c_int32), ("plc", C.c_int32)]
 
 
-class Bridge(_Batch):
+class Bridge(_ConferenceBatch):
     """mi_bridge (include/msmi355x_bridge.h): a conference server's member chain -- [G.711 ->] MSVolume -> conference mix
     [-> G.711], no echo canceller -- one launch per tick, fed from host buffers, three ticks in flight.  ctx=None: a
     Context of its own on `device`."""
-    _destroy = "mi_bridge_destroy"
+    _destroy, _prefix = "mi_bridge_destroy", "bridge"
 
     def __init__(self, ctx, nstreams, members=32, rate=8000, in_codec=MI_SESSION_PCMU, out_codec=MI_SESSION_PCMU, plc=False, device=0):
         self._own_ctx = ctx is None
@@ -910,53 +919,18 @@ class Bridge(_Batch):
         check(self.ctx.L.mi_bridge_acquire(self.h, C.byref(pi), C.byref(pp)))
         return self._view(pi, self.in_dtype, self.n, self.len), self._view(pp, C.c_uint8, self.n)
 
-    def submit(self):
-        check(self.ctx.L.mi_bridge_submit(self.h))
-
     def collect(self):
         """numpy view of the oldest in-flight tick's output [n, len] (pinned; valid for three more submits)."""
         po = C.c_void_p()
         check(self.ctx.L.mi_bridge_collect(self.h, C.byref(po)))
         return self._view(po, self.out_dtype, self.n, self.len)
 
-    def in_flight(self):
-        return self.ctx.L.mi_bridge_in_flight(self.h)
-
-    def set_controls(self, flags=None, gain=None):
-        f = None if flags is None else np.ascontiguousarray(flags, np.uint8)
-        g = None if gain is None else np.ascontiguousarray(gain, np.float32)
-        check(self.ctx.L.mi_bridge_set_controls(self.h, _ptr(f), _ptr(g)))
-
     def set_volume_params(self, params, first=0):
         arr = (VolumeParams * len(params))(*params)
         check(self.ctx.L.mi_bridge_set_volume_params(self.h, first, len(params), arr))
 
-    def reset_streams(self, first, count):
-        check(self.ctx.L.mi_bridge_reset_streams(self.h, first, count))
-
-    def levels(self):
-        out = np.zeros(self.n, np.float32)
-        check(self.ctx.L.mi_bridge_get_levels(self.h, _ptr(out)))
-        return out
-
-    def add_member(self, stream):
-        check(self.ctx.L.mi_bridge_add_member(self.h, int(stream)))
-
-    def remove_member(self, stream):
-        check(self.ctx.L.mi_bridge_remove_member(self.h, int(stream)))
-
-    def member_count(self, conference):
-        n = self.ctx.L.mi_bridge_member_count(self.h, int(conference))
-        check(min(n, 0))
-        return n
-
     def active_speakers(self, now_ms=0):
-        """(winner stream per conference or -1, its MS_VOLUME_GET_MAX in dBm0): audioconference.c:436-452"""
-        nconf = self.n // self.members
-        win = np.zeros(nconf, np.int32)
-        db = np.zeros(nconf, np.float32)
-        check(self.ctx.L.mi_bridge_active_speakers(self.h, C.c_uint64(int(now_ms)), _ptr(win), _ptr(db)))
-        return win, db
+        return super().active_speakers(now_ms)
 
     def volume_state(self, first=0, count=None):
         count = self.n - first if count is None else count

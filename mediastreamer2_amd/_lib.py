@@ -252,44 +252,22 @@ def load():
         L.mi_scaler_process.argtypes = [vp, i32, vp, sz, vp, sz]
         L.mi_scaler_process_host.argtypes = [vp, i32, vp, sz, vp, sz]
         L.mi_scaler_process_planes_host.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(i32)]
+    # what mi_session and mi_bridge share: the tick ring and MSAudioConference's control plane
+    for p in ("session", "bridge") if hasattr(L, "mi_session_create") else ("bridge",):
+        for name, args in (("default_config", [vp]), ("create", [vp, vp, pp]), ("destroy", [vp]), ("acquire", [vp, pp, pp]),
+                           ("submit", [vp]), ("collect", [vp, pp]), ("in_flight", [vp]), ("set_controls", [vp, vp, vp]),
+                           ("reset_streams", [vp, i32, i32]), ("get_levels", [vp, vp]), ("add_member", [vp, i32]),
+                           ("remove_member", [vp, i32]), ("member_count", [vp, i32]), ("active_speakers", [vp, C.c_uint64, vp, vp])):
+            f = getattr(L, f"mi_{p}_{name}")
+            f.argtypes = args
+            if name in ("default_config", "destroy"):
+                f.restype = None
     if hasattr(L, "mi_session_create"):
-        L.mi_session_default_config.argtypes = [vp]
-        L.mi_session_default_config.restype = None
-        L.mi_session_create.argtypes = [vp, vp, pp]
-        L.mi_session_destroy.argtypes = [vp]
-        L.mi_session_destroy.restype = None
         L.mi_session_tick_samples.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
         L.mi_session_tick_bytes.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
         L.mi_session_events.argtypes = [vp, pp]
-        L.mi_session_acquire.argtypes = [vp, pp, pp]
-        L.mi_session_submit.argtypes = [vp]
-        L.mi_session_collect.argtypes = [vp, pp]
-        L.mi_session_in_flight.argtypes = [vp]
-        L.mi_session_set_controls.argtypes = [vp, vp, vp]
-        L.mi_session_get_levels.argtypes = [vp, vp]
-        L.mi_session_add_member.argtypes = [vp, i32]
-        L.mi_session_remove_member.argtypes = [vp, i32]
-        L.mi_session_member_count.argtypes = [vp, i32]
-        L.mi_session_active_speakers.argtypes = [vp, C.c_uint64, vp, vp]
-        L.mi_session_reset_streams.argtypes = [vp, i32, i32]
-    L.mi_bridge_default_config.argtypes = [vp]
-    L.mi_bridge_default_config.restype = None
-    L.mi_bridge_create.argtypes = [vp, vp, pp]
-    L.mi_bridge_destroy.argtypes = [vp]
-    L.mi_bridge_destroy.restype = None
     L.mi_bridge_tick_bytes.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    L.mi_bridge_acquire.argtypes = [vp, pp, pp]
-    L.mi_bridge_submit.argtypes = [vp]
-    L.mi_bridge_collect.argtypes = [vp, pp]
-    L.mi_bridge_in_flight.argtypes = [vp]
-    L.mi_bridge_set_controls.argtypes = [vp, vp, vp]
     L.mi_bridge_set_volume_params.argtypes = [vp, i32, i32, C.POINTER(VolumeParams)]
-    L.mi_bridge_reset_streams.argtypes = [vp, i32, i32]
-    L.mi_bridge_add_member.argtypes = [vp, i32]
-    L.mi_bridge_remove_member.argtypes = [vp, i32]
-    L.mi_bridge_member_count.argtypes = [vp, i32]
-    L.mi_bridge_get_levels.argtypes = [vp, vp]
-    L.mi_bridge_active_speakers.argtypes = [vp, C.c_uint64, vp, vp]
     L.mi_bridge_get_volume_state.argtypes = [vp, i32, i32, C.POINTER(VolumeState)]
     L.mi_bridge_get_volume_max.argtypes = [vp, i32, i32, vp]
     if hasattr(L, "mi_fifo_create"):

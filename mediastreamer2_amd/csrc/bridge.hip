@@ -1,9 +1,10 @@
 // bridge.hip -- mi_bridge (include/msmi355x_bridge.h): a conference server's member chain
 //   decoder -> MSVolume (level / meter) -> MSAudioMixer pin -> encoder      (src/voip/audioconference.c:209-257)
 // for a batch of conferences, a conference's whole 10 ms tick in ONE launch, fed from host buffers like mi_session
-// (session.hip): three slots of pinned staging, upload / kernel / download on three HIP streams, up to three ticks in
-// flight.  No echo canceller -- that is the endpoint's.  Built with -ffp-contract=off like volume.hip: MSVolume's control
-// chain is float32 evaluated unfused in source order, and every output sample depends on it bit for bit.
+// (session.hip): three slots of pinned staging, upload / kernel / download on three HIP streams (mi::TickPipe,
+// tick_pipe.hpp), up to three ticks in flight.  No echo canceller -- that is the endpoint's.  Built with
+// -ffp-contract=off like volume.hip: MSVolume's control chain is float32 evaluated unfused in source order, and every
+// output sample depends on it bit for bit.
 //
 // bridge_tick_kernel<IN, OUT>: one workgroup of 256 lanes = one conference; the members' ticks live in LDS as packed
 // int16 rows whose pitch is an odd number of 8-byte words (volmix_kernel's layout, volume.hip), so the lanes that walk
@@ -29,6 +30,7 @@
 #include "common.hpp"
 #include "conference.hpp"
 #include "g711.hpp"
+#include "tick_pipe.hpp"
 #include "volume_ctl.hpp"
 
 #include "../../include/msmi355x_bridge.h"
@@ -241,18 +243,12 @@ struct mi_bridge {
 	mi_volume *vol = nullptr; // the meters: parameters, state, one-second windows
 	mi_mixer *mix = nullptr;  // the pins' controls
 	mi_plc *plc = nullptr;
-	hipStream_t s_up = nullptr, s_down = nullptr;
+	mi::TickPipe pipe;
 	uint8_t *h_in[SLOTS] = {}, *h_present[SLOTS] = {}, *h_ev[SLOTS] = {}, *h_out[SLOTS] = {};
 	uint8_t *d_in[SLOTS] = {}, *d_present[SLOTS] = {}, *d_ev[SLOTS] = {}, *d_out[SLOTS] = {};
 	int16_t *d_pcm = nullptr; // plc behind a decoder: the decoded rows the concealer edits
 	int32_t *d_evlen = nullptr;
-	hipEvent_t ev_up[SLOTS] = {}, ev_done[SLOTS] = {}, ev_down[SLOTS] = {};
-	bool used[SLOTS] = {};
-	long long submitted = 0, collected = 0;
-	bool acquired = false;
-	std::vector<uint8_t> flags;   // MI_MIX_* per stream as last set
-	std::vector<uint32_t> joined; // joining order (mi::elect_active_speakers)
-	uint32_t join_seq = 0;
+	mi::Roster roster;
 };
 
 namespace {
@@ -308,25 +304,19 @@ void mi_bridge_destroy(mi_bridge *b) {
 	if (!b) return;
 	mi_ctx *c = b->ctx;
 	(void)c->activate();
-	(void)hipStreamSynchronize(c->stream);
-	if (b->s_up) (void)hipStreamSynchronize(b->s_up);
-	if (b->s_down) (void)hipStreamSynchronize(b->s_down);
+	b->pipe.drain();
 	for (int i = 0; i < SLOTS; ++i) {
 		for (uint8_t *p : {b->h_in[i], b->h_present[i], b->h_ev[i], b->h_out[i]})
 			if (p) mi_host_free(c, p);
 		for (uint8_t *p : {b->d_in[i], b->d_present[i], b->d_ev[i], b->d_out[i]})
 			if (p) mi_dev_free(c, p);
-		if (b->ev_up[i]) (void)hipEventDestroy(b->ev_up[i]);
-		if (b->ev_done[i]) (void)hipEventDestroy(b->ev_done[i]);
-		if (b->ev_down[i]) (void)hipEventDestroy(b->ev_down[i]);
 	}
 	if (b->d_pcm) mi_dev_free(c, b->d_pcm);
 	if (b->d_evlen) mi_dev_free(c, b->d_evlen);
 	if (b->plc) mi_plc_destroy(b->plc);
 	if (b->vol) mi_volume_destroy(b->vol);
 	if (b->mix) mi_mixer_destroy(b->mix);
-	if (b->s_up) (void)hipStreamDestroy(b->s_up);
-	if (b->s_down) (void)hipStreamDestroy(b->s_down);
+	b->pipe.destroy();
 	delete b;
 }
 
@@ -352,7 +342,7 @@ int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) 
 	}
 	if (ctx->activate() != MI_OK) return MI_ENODEV;
 	mi_bridge *b = new mi_bridge();
-	b->ctx = ctx;
+	b->ctx = b->pipe.ctx = ctx;
 	b->cfg = *cfg;
 	b->n = cfg->nstreams;
 	b->mm = mm;
@@ -364,9 +354,7 @@ int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) 
 	b->nslice = std::max(1, std::min(mm, BT / (len >> 2)));
 	b->in_bytes = (size_t)len * (cfg->in_codec ? 1 : 2);
 	b->out_bytes = (size_t)len * (cfg->out_codec ? 1 : 2);
-	b->flags.assign((size_t)b->n, (uint8_t)(MI_MIX_LINKED | MI_MIX_ACTIVE | MI_MIX_OUTPUT));
-	b->joined.resize((size_t)b->n);
-	for (int i = 0; i < b->n; ++i) b->joined[(size_t)i] = ++b->join_seq; // a bridge is created full: joined in pin order
+	b->roster.init(b->n, mm);
 	int rc = MI_OK;
 	auto fail = [&](int code) {
 		mi_bridge_destroy(b);
@@ -374,11 +362,7 @@ int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) 
 	};
 	if ((rc = mi_volume_create(ctx, b->n, cfg->rate, &b->vol)) != MI_OK) return fail(rc);
 	if ((rc = mi_mixer_create(ctx, b->nconf, mm, len, &b->mix)) != MI_OK) return fail(rc);
-	if (hipStreamCreateWithFlags(&b->s_up, hipStreamNonBlocking) != hipSuccess ||
-	    hipStreamCreateWithFlags(&b->s_down, hipStreamNonBlocking) != hipSuccess) {
-		mi::set_error("hipStreamCreate failed");
-		return fail(MI_ENODEV);
-	}
+	if ((rc = b->pipe.create(ctx, SLOTS)) != MI_OK) return fail(rc);
 	const size_t n = (size_t)b->n;
 	for (int i = 0; i < SLOTS; ++i) {
 		b->h_in[i] = (uint8_t *)mi_host_alloc(ctx, n * b->in_bytes);
@@ -391,12 +375,6 @@ int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) 
 		// rows of pins whose output is off are never written: they read as zeros
 		MI_HIP(hipMemsetAsync(b->d_out[i], 0, n * b->out_bytes, ctx->stream));
 		memset(b->h_out[i], 0, n * b->out_bytes);
-		if (hipEventCreateWithFlags(&b->ev_up[i], hipEventDisableTiming) != hipSuccess ||
-		    hipEventCreateWithFlags(&b->ev_done[i], hipEventDisableTiming) != hipSuccess ||
-		    hipEventCreateWithFlags(&b->ev_down[i], hipEventDisableTiming) != hipSuccess) {
-			mi::set_error("hipEventCreate failed");
-			return fail(MI_ENODEV);
-		}
 	}
 	if (cfg->plc) {
 		if ((rc = mi_plc_create(ctx, b->n, cfg->rate, len, &b->plc)) != MI_OK) return fail(rc);
@@ -424,76 +402,58 @@ int mi_bridge_tick_bytes(const mi_bridge *b, int *in_bytes, int *out_bytes) {
 
 int mi_bridge_acquire(mi_bridge *b, void **h_in, uint8_t **h_present) {
 	MI_CHECK_ARG(b && h_in && h_present);
-	if (b->submitted - b->collected >= SLOTS) {
-		mi::set_error("all %d ticks in flight: collect one first", SLOTS);
-		return MI_EINVAL;
-	}
-	const int slot = (int)(b->submitted % SLOTS);
-	if (b->ctx->activate() != MI_OK) return MI_ENODEV;
+	int slot;
 	// the slot's previous upload must have been consumed by its kernels before the host overwrites the staging
-	if (b->used[slot]) MI_HIP(hipEventSynchronize(b->ev_done[slot]));
+	const int rc = b->pipe.acquire(mi::TickPipe::CONSUMED, &slot);
+	if (rc == mi::TickPipe::FULL) mi::set_error("all %d ticks in flight: collect one first", SLOTS);
+	if (rc != MI_OK) return rc;
 	*h_in = b->h_in[slot];
 	*h_present = b->h_present[slot];
 	memset(b->h_present[slot], 1, (size_t)b->n);
-	b->acquired = true;
 	return MI_OK;
 }
 
 int mi_bridge_submit(mi_bridge *b) {
 	MI_CHECK_ARG(b != nullptr);
-	if (!b->acquired) {
+	if (!b->pipe.acquired) {
 		mi::set_error("mi_bridge_submit without mi_bridge_acquire");
 		return MI_EINVAL;
 	}
-	mi_ctx *c = b->ctx;
-	if (c->activate() != MI_OK) return MI_ENODEV;
-	const int slot = (int)(b->submitted % SLOTS);
 	const size_t n = (size_t)b->n;
-	// upload on its own stream
-	MI_HIP(hipMemcpyAsync(b->d_in[slot], b->h_in[slot], n * b->in_bytes, hipMemcpyHostToDevice, b->s_up));
-	if (b->plc) { // an absent leg is the concealer's to fill
-		for (size_t i = 0; i < n; ++i) b->h_ev[slot][i] = b->h_present[slot][i] ? MI_PLC_RECEIVED : MI_PLC_CONCEAL;
-		MI_HIP(hipMemcpyAsync(b->d_ev[slot], b->h_ev[slot], n, hipMemcpyHostToDevice, b->s_up));
-	} else {
-		MI_HIP(hipMemcpyAsync(b->d_present[slot], b->h_present[slot], n, hipMemcpyHostToDevice, b->s_up));
-	}
-	MI_HIP(hipEventRecord(b->ev_up[slot], b->s_up));
-	// kernels wait for this tick's upload and for the download that last read this slot's output buffer
-	MI_HIP(hipStreamWaitEvent(c->stream, b->ev_up[slot], 0));
-	if (b->used[slot]) MI_HIP(hipStreamWaitEvent(c->stream, b->ev_down[slot], 0));
-	const int rc = run_tick_kernels(b, slot);
-	if (rc != MI_OK) return rc;
-	MI_HIP(hipEventRecord(b->ev_done[slot], c->stream));
-	// download on its own stream
-	MI_HIP(hipStreamWaitEvent(b->s_down, b->ev_done[slot], 0));
-	MI_HIP(hipMemcpyAsync(b->h_out[slot], b->d_out[slot], n * b->out_bytes, hipMemcpyDeviceToHost, b->s_down));
-	MI_HIP(hipEventRecord(b->ev_down[slot], b->s_down));
-	b->used[slot] = true;
-	b->submitted++;
-	b->acquired = false;
-	return MI_OK;
+	return b->pipe.submit(
+	    [&](int slot) {
+		    MI_HIP(hipMemcpyAsync(b->d_in[slot], b->h_in[slot], n * b->in_bytes, hipMemcpyHostToDevice, b->pipe.s_up));
+		    if (b->plc) { // an absent leg is the concealer's to fill
+			    for (size_t i = 0; i < n; ++i) b->h_ev[slot][i] = b->h_present[slot][i] ? MI_PLC_RECEIVED : MI_PLC_CONCEAL;
+			    MI_HIP(hipMemcpyAsync(b->d_ev[slot], b->h_ev[slot], n, hipMemcpyHostToDevice, b->pipe.s_up));
+		    } else {
+			    MI_HIP(hipMemcpyAsync(b->d_present[slot], b->h_present[slot], n, hipMemcpyHostToDevice, b->pipe.s_up));
+		    }
+		    return MI_OK;
+	    },
+	    [&](int slot) { return run_tick_kernels(b, slot); },
+	    [&](int slot) {
+		    MI_HIP(hipMemcpyAsync(b->h_out[slot], b->d_out[slot], n * b->out_bytes, hipMemcpyDeviceToHost, b->pipe.s_down));
+		    return MI_OK;
+	    });
 }
 
 int mi_bridge_collect(mi_bridge *b, const void **h_out) {
 	MI_CHECK_ARG(b && h_out);
-	if (b->collected >= b->submitted) {
-		mi::set_error("nothing in flight");
-		return MI_EINVAL;
-	}
-	if (b->ctx->activate() != MI_OK) return MI_ENODEV;
-	const int slot = (int)(b->collected % SLOTS);
-	MI_HIP(hipEventSynchronize(b->ev_down[slot]));
+	int slot;
+	const int rc = b->pipe.collect(&slot);
+	if (rc == mi::TickPipe::EMPTY) mi::set_error("nothing in flight");
+	if (rc != MI_OK) return rc;
 	*h_out = b->h_out[slot];
-	b->collected++;
 	return MI_OK;
 }
 
-int mi_bridge_in_flight(const mi_bridge *b) { return b ? (int)(b->submitted - b->collected) : 0; }
+int mi_bridge_in_flight(const mi_bridge *b) { return b ? b->pipe.in_flight() : 0; }
 
 // ---- control plane, as mi_session's (session.hip).  The mixer's and the meter's setters wait for the ticks submitted.
 int mi_bridge_set_controls(mi_bridge *b, const uint8_t *h_flags, const float *h_gain) {
 	MI_CHECK_ARG(b && (h_flags || h_gain));
-	if (h_flags) b->flags.assign(h_flags, h_flags + b->n);
+	if (h_flags) b->roster.set_flags(h_flags);
 	return mi_mixer_set_controls(b->mix, h_flags, h_gain); // [nconf][members] == [nstreams]
 }
 
@@ -512,43 +472,35 @@ int mi_bridge_reset_streams(mi_bridge *b, int first, int count) {
 	MI_CHECK_ARG(b && first >= 0 && count >= 0 && first + count <= b->n);
 	if (count == 0) return MI_OK;
 	int rc;
-	mi_volume_state st;
-	memset(&st, 0, sizeof(st));
-	st.gain = st.target_gain = 1; // volume_init msvolume.c:92
-	st.ng_gain = 1;               // :112
-	std::vector<mi_volume_state> all((size_t)count, st);
-	if ((rc = mi_volume_set_state(b->vol, first, count, all.data())) != MI_OK) return rc;
-	if ((rc = mi_volume_reset_max(b->vol, first, count)) != MI_OK) return rc;
+	if ((rc = mi::reset_meters(b->vol, first, count)) != MI_OK) return rc;
 	if (b->plc && (rc = mi_plc_reset(b->plc, first, count)) != MI_OK) return rc;
 	return MI_OK;
 }
 
 int mi_bridge_add_member(mi_bridge *b, int stream) {
 	MI_CHECK_ARG(b && stream >= 0 && stream < b->n);
-	if (b->flags[(size_t)stream] & MI_MIX_LINKED) {
+	if (b->roster.is_member(stream)) {
 		mi::set_error("mi_bridge_add_member: stream %d is a member already", stream);
 		return MI_EINVAL;
 	}
 	const int rc = mi_bridge_reset_streams(b, stream, 1);
 	if (rc != MI_OK) return rc;
-	b->flags[(size_t)stream] = MI_MIX_LINKED | MI_MIX_ACTIVE | MI_MIX_OUTPUT;
-	b->joined[(size_t)stream] = ++b->join_seq; // appended to the member list
-	return mi_mixer_set_controls(b->mix, b->flags.data(), nullptr);
+	b->roster.join(stream);
+	return mi_mixer_set_controls(b->mix, b->roster.flags.data(), nullptr);
 }
 
 int mi_bridge_remove_member(mi_bridge *b, int stream) {
 	MI_CHECK_ARG(b && stream >= 0 && stream < b->n);
-	if (!(b->flags[(size_t)stream] & MI_MIX_LINKED)) {
+	if (!b->roster.leave(stream)) {
 		mi::set_error("mi_bridge_remove_member: stream %d is no member", stream);
 		return MI_EINVAL;
 	}
-	b->flags[(size_t)stream] = 0;
-	const int rc = mi_mixer_set_controls(b->mix, b->flags.data(), nullptr);
+	const int rc = mi_mixer_set_controls(b->mix, b->roster.flags.data(), nullptr);
 	if (rc != MI_OK) return rc;
 	if (b->ctx->activate() != MI_OK) return MI_ENODEV;
 	// an unplumbed pin's row is left alone from now on: what the departed leg last heard must not linger in the buffers
 	MI_HIP(hipStreamSynchronize(b->ctx->stream));
-	MI_HIP(hipStreamSynchronize(b->s_down));
+	MI_HIP(hipStreamSynchronize(b->pipe.s_down));
 	for (int i = 0; i < SLOTS; ++i) {
 		MI_HIP(hipMemsetAsync(b->d_out[i] + (size_t)stream * b->out_bytes, 0, b->out_bytes, b->ctx->stream));
 		memset(b->h_out[i] + (size_t)stream * b->out_bytes, 0, b->out_bytes);
@@ -558,28 +510,18 @@ int mi_bridge_remove_member(mi_bridge *b, int stream) {
 
 int mi_bridge_member_count(const mi_bridge *b, int conference) {
 	if (!b || conference < 0 || conference >= b->nconf) return MI_EINVAL;
-	int c = 0;
-	for (int m = 0; m < b->mm; ++m) c += (b->flags[(size_t)conference * b->mm + m] & MI_MIX_LINKED) != 0;
-	return c;
+	return b->roster.count(conference);
 }
 
 int mi_bridge_get_levels(mi_bridge *b, float *h_linear) {
 	MI_CHECK_ARG(b && h_linear);
-	std::vector<mi_volume_state> st((size_t)b->n);
-	const int rc = mi_volume_get_state(b->vol, 0, b->n, st.data());
-	if (rc != MI_OK) return rc;
-	for (int i = 0; i < b->n; ++i) h_linear[i] = st[(size_t)i].energy; // volume_get_linear msvolume.c:129-134
-	return MI_OK;
+	return mi::get_levels(b->vol, b->n, h_linear);
 }
 
 int mi_bridge_active_speakers(mi_bridge *b, uint64_t now_ms, int32_t *h_winner, float *h_max_db) {
 	MI_CHECK_ARG(b && h_winner);
-	(void)now_ms; // the windows run on the device, one record per tick (msvolume.c:404)
-	std::vector<float> mx((size_t)b->n);
-	const int rc = mi_volume_get_max(b->vol, 0, b->n, mx.data());
-	if (rc != MI_OK) return rc;
-	mi::elect_active_speakers(mx.data(), b->flags.data(), b->joined.data(), b->nconf, b->mm, h_winner, h_max_db);
-	return MI_OK;
+	(void)now_ms; // not read (mi::active_speakers)
+	return mi::active_speakers(b->vol, b->roster, h_winner, h_max_db);
 }
 
 int mi_bridge_get_volume_state(mi_bridge *b, int first, int count, mi_volume_state *h_state) {

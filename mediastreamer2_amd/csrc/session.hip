@@ -7,10 +7,11 @@
 // tests/test_gpu_pipeline.py's chain.
 //
 // Three HIP streams: uploads, kernels (the context's stream), downloads.  A tick's inputs go up while the previous
-// tick computes and the one before comes down; events order the three, hipGraphs (one per buffer slot) replay the
-// kernel sequence.  Pinned host buffers belong to the session: the caller fills / reads them in place.
+// tick computes and the one before comes down; events order the three (mi::TickPipe, tick_pipe.hpp), hipGraphs (one per
+// buffer slot) replay the kernel sequence.  Pinned host buffers belong to the session: the caller fills / reads them in place.
 #include "common.hpp"
 #include "conference.hpp"
+#include "tick_pipe.hpp"
 
 #include <cmath>
 
@@ -21,7 +22,7 @@ constexpr int SLOTS = 3; // upload | compute | download can each hold a differen
 struct mi_session {
 	mi_ctx *ctx = nullptr;
 	mi_session_config cfg;
-	int n = 0, nconf = 0, in_len = 0, len = 0, frame = 0, up_stride = 0;
+	int n = 0, in_len = 0, len = 0, frame = 0, up_stride = 0;
 	int out_len = 0, down_stride = 0;               // samples per tick leaving, row pitch of the down-sampled mix
 	size_t mic_bytes = 0, ref_bytes = 0, out_bytes = 0; // per stream and tick, on the host side
 	mi_resampler *rs = nullptr, *rs_out = nullptr;
@@ -34,27 +35,16 @@ struct mi_session {
 	mi_volume *vol = nullptr;
 	mi_mixer *mix = nullptr;
 	mi_fifo *f_mic = nullptr, *f_ref = nullptr, *f_out = nullptr;
-	hipStream_t s_up = nullptr, s_down = nullptr;
+	mi::TickPipe pipe;
 	int16_t *h_mic[SLOTS] = {}, *h_ref[SLOTS] = {}, *h_out[SLOTS] = {};
 	int16_t *d_mic[SLOTS] = {}, *d_ref[SLOTS] = {}, *d_out[SLOTS] = {};
 	int16_t *d_up = nullptr, *d_tick = nullptr;
 	bool fold_resampler = true; // the canceller's launch runs the up-sampler too (until it says it cannot)
 	bool fuse_mix = true;       // volume + conference mix in one launch (likewise)
-	// the canceller's frames of a tick (up to ROUNDS_MAX per leg, back to back in one row): frames in, cleaned frames out,
-	// frames each leg had ready (buffers [0] only; the arrays are kept for the reset helpers)
-	static constexpr int ROUNDS_MAX = MI_AEC_MAX_TICK_FRAMES;
-	int rounds = 0;
-	int16_t *d_micf[ROUNDS_MAX] = {}, *d_reff[ROUNDS_MAX] = {}, *d_clean[ROUNDS_MAX] = {};
-	uint8_t *d_ok[ROUNDS_MAX] = {};
-	hipEvent_t ev_up[SLOTS] = {}, ev_done[SLOTS] = {}, ev_down[SLOTS] = {};
-	bool used[SLOTS] = {};
+	int rounds = 0;                 // the canceller's frames of a tick, at most (max_frames of its call)
+	uint8_t *d_reset_gate = nullptr; // [n] mi_session_reset_streams: 1 = the leg's reference FIFO gets its delay again
 	mi_graph *graph[SLOTS] = {};
-	long long submitted = 0, collected = 0;
-	bool acquired = false;
-	// conference membership / active-speaker election (MSAudioConference, src/voip/audioconference.c)
-	std::vector<uint8_t> flags;      // MI_MIX_* per stream as last set (default: every pin linked, active, output on)
-	std::vector<uint32_t> joined;    // the conference's member LIST is in joining order (bctbx_list_append, audioconference.c:328): of two
-	uint32_t join_seq = 0;           // equally loud members the election takes the one that joined first (:449 compares strictly)
+	mi::Roster roster; // conference membership / active-speaker election (MSAudioConference, src/voip/audioconference.c)
 };
 
 namespace {
@@ -150,9 +140,7 @@ void mi_session_destroy(mi_session *s) {
 	if (!s) return;
 	mi_ctx *c = s->ctx;
 	(void)c->activate();
-	(void)hipStreamSynchronize(c->stream);
-	if (s->s_up) (void)hipStreamSynchronize(s->s_up);
-	if (s->s_down) (void)hipStreamSynchronize(s->s_down);
+	s->pipe.drain();
 	for (int i = 0; i < SLOTS; ++i) {
 		if (s->graph[i]) mi_graph_destroy(s->graph[i]);
 		if (s->h_mic[i]) mi_host_free(c, s->h_mic[i]);
@@ -164,16 +152,10 @@ void mi_session_destroy(mi_session *s) {
 		if (s->d_mix[i]) mi_dev_free(c, s->d_mix[i]);
 		if (s->h_ev[i]) mi_host_free(c, s->h_ev[i]);
 		if (s->d_ev[i]) mi_dev_free(c, s->d_ev[i]);
-		if (s->ev_up[i]) (void)hipEventDestroy(s->ev_up[i]);
-		if (s->ev_done[i]) (void)hipEventDestroy(s->ev_done[i]);
-		if (s->ev_down[i]) (void)hipEventDestroy(s->ev_down[i]);
 	}
-	void *dv[] = {s->d_up, s->d_tick, s->d_pcm, s->d_down, s->d_zero, s->d_evlen};
+	void *dv[] = {s->d_up, s->d_tick, s->d_pcm, s->d_down, s->d_zero, s->d_evlen, s->d_reset_gate};
 	for (void *p : dv)
 		if (p) mi_dev_free(c, p);
-	for (int r = 0; r < mi_session::ROUNDS_MAX; ++r)
-		for (void *p : {(void *)s->d_micf[r], (void *)s->d_reff[r], (void *)s->d_clean[r], (void *)s->d_ok[r]})
-			if (p) mi_dev_free(c, p);
 	if (s->rs) mi_resampler_destroy(s->rs);
 	if (s->rs_out) mi_resampler_destroy(s->rs_out);
 	if (s->plc) mi_plc_destroy(s->plc);
@@ -183,8 +165,7 @@ void mi_session_destroy(mi_session *s) {
 	if (s->f_mic) mi_fifo_destroy(s->f_mic);
 	if (s->f_ref) mi_fifo_destroy(s->f_ref);
 	if (s->f_out) mi_fifo_destroy(s->f_out);
-	if (s->s_up) (void)hipStreamDestroy(s->s_up);
-	if (s->s_down) (void)hipStreamDestroy(s->s_down);
+	s->pipe.destroy();
 	delete s;
 }
 
@@ -198,13 +179,10 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 	MI_CHECK_ARG(cfg->out_rate >= 0 && cfg->out_rate % 100 == 0 && cfg->ref_delay_ms >= 0 && cfg->ref_delay_ms <= 1000);
 	if (ctx->activate() != MI_OK) return MI_ENODEV;
 	mi_session *s = new mi_session();
-	s->ctx = ctx;
+	s->ctx = s->pipe.ctx = ctx;
 	s->cfg = *cfg;
 	s->n = cfg->nstreams;
-	s->nconf = cfg->nstreams / cfg->members_per_conference;
-	s->flags.assign((size_t)s->n, (uint8_t)(MI_MIX_LINKED | MI_MIX_ACTIVE | MI_MIX_OUTPUT));
-	s->joined.resize((size_t)s->n);
-	for (int i = 0; i < s->n; ++i) s->joined[(size_t)i] = ++s->join_seq; // a session is created full: joined in pin order
+	s->roster.init(s->n, cfg->members_per_conference);
 	s->in_len = cfg->in_rate / 100;
 	s->len = cfg->rate / 100;
 	const bool down = cfg->out_rate != 0 && cfg->out_rate != cfg->rate;
@@ -235,7 +213,7 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 		std::vector<mi_volume_params> all((size_t)s->n, p);
 		if ((rc = mi_volume_set_params(s->vol, 0, s->n, all.data())) != MI_OK) return fail(rc);
 	}
-	if ((rc = mi_mixer_create(ctx, s->nconf, cfg->members_per_conference, s->len, &s->mix)) != MI_OK) return fail(rc);
+	if ((rc = mi_mixer_create(ctx, s->roster.nconf, cfg->members_per_conference, s->len, &s->mix)) != MI_OK) return fail(rc);
 	// capacities: whole frames (the canceller reads / writes the rings frame-wise, mi_aec_process_fifos), two ticks + two
 	// frames, + one frame for the lead of a staggered leg (its output queue stands one frame fuller)
 	const int cap = (2 * s->len + (cfg->stagger ? 3 : 2) * s->frame + s->frame - 1) / s->frame * s->frame;
@@ -244,11 +222,7 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 	if ((rc = mi_fifo_create(ctx, s->n, cap, &s->f_mic)) != MI_OK || (rc = mi_fifo_create(ctx, s->n, ref_cap, &s->f_ref)) != MI_OK ||
 	    (rc = mi_fifo_create(ctx, s->n, cap, &s->f_out)) != MI_OK)
 		return fail(rc);
-	if (hipStreamCreateWithFlags(&s->s_up, hipStreamNonBlocking) != hipSuccess ||
-	    hipStreamCreateWithFlags(&s->s_down, hipStreamNonBlocking) != hipSuccess) {
-		mi::set_error("hipStreamCreate failed");
-		return fail(MI_ENODEV);
-	}
+	if ((rc = s->pipe.create(ctx, SLOTS)) != MI_OK) return fail(rc);
 	const size_t n = (size_t)s->n;
 	for (int i = 0; i < SLOTS; ++i) {
 		s->h_mic[i] = (int16_t *)mi_host_alloc(ctx, n * s->mic_bytes);
@@ -266,23 +240,11 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 			if (!s->d_mix[i]) return fail(MI_ENOMEM);
 			MI_HIP(hipMemsetAsync(s->d_mix[i], 0, n * s->len * 2, ctx->stream));
 		}
-		if (hipEventCreateWithFlags(&s->ev_up[i], hipEventDisableTiming) != hipSuccess ||
-		    hipEventCreateWithFlags(&s->ev_done[i], hipEventDisableTiming) != hipSuccess ||
-		    hipEventCreateWithFlags(&s->ev_down[i], hipEventDisableTiming) != hipSuccess) {
-			mi::set_error("hipEventCreate failed");
-			return fail(MI_ENODEV);
-		}
 	}
 	if (s->rs) s->d_up = (int16_t *)mi_dev_alloc(ctx, n * s->up_stride * 2);
 	s->rounds = (s->len + s->frame - 1) / s->frame;
-	if (s->rounds > mi_session::ROUNDS_MAX) return fail(MI_ENOTSUP);
-	for (int r = 0; r < 1; ++r) {
-		s->d_micf[r] = (int16_t *)mi_dev_alloc(ctx, n * s->rounds * s->frame * 2);
-		s->d_reff[r] = (int16_t *)mi_dev_alloc(ctx, n * s->rounds * s->frame * 2);
-		s->d_clean[r] = (int16_t *)mi_dev_alloc(ctx, n * s->rounds * s->frame * 2);
-		s->d_ok[r] = (uint8_t *)mi_dev_alloc(ctx, n);
-		if (!s->d_micf[r] || !s->d_reff[r] || !s->d_clean[r] || !s->d_ok[r]) return fail(MI_ENOMEM);
-	}
+	if (s->rounds > MI_AEC_MAX_TICK_FRAMES) return fail(MI_ENOTSUP);
+	if (!(s->d_reset_gate = (uint8_t *)mi_dev_alloc(ctx, n))) return fail(MI_ENOMEM);
 	s->d_tick = (int16_t *)mi_dev_alloc(ctx, n * s->len * 2);
 	if ((s->rs && !s->d_up) || !s->d_tick) return fail(MI_ENOMEM);
 	if (cfg->mic_codec && !(s->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * s->in_len * 2))) return fail(MI_ENOMEM);
@@ -326,98 +288,81 @@ int mi_session_tick_bytes(const mi_session *s, int *mic_bytes, int *ref_bytes, i
 
 int mi_session_acquire(mi_session *s, int16_t **h_mic, int16_t **h_ref) {
 	MI_CHECK_ARG(s && h_mic && h_ref);
-	if (s->submitted - s->collected >= SLOTS) {
-		mi::set_error("all %d ticks in flight: collect one first", SLOTS);
-		return MI_EINVAL;
-	}
-	const int slot = (int)(s->submitted % SLOTS);
-	if (s->ctx->activate() != MI_OK) return MI_ENODEV;
+	int slot;
 	// the slot's previous upload must have been consumed by its kernels before the host overwrites the staging
-	if (s->used[slot]) MI_HIP(hipEventSynchronize(s->ev_done[slot]));
+	const int rc = s->pipe.acquire(mi::TickPipe::CONSUMED, &slot);
+	if (rc == mi::TickPipe::FULL) mi::set_error("all %d ticks in flight: collect one first", SLOTS);
+	if (rc != MI_OK) return rc;
 	*h_mic = s->h_mic[slot];
 	*h_ref = s->h_ref[slot];
 	if (s->plc) memset(s->h_ev[slot], MI_PLC_RECEIVED, (size_t)s->n);
-	s->acquired = true;
 	return MI_OK;
 }
 
 int mi_session_events(mi_session *s, uint8_t **h_events) {
 	MI_CHECK_ARG(s && h_events);
-	if (!s->plc || !s->acquired) {
+	if (!s->plc || !s->pipe.acquired) {
 		mi::set_error(s->plc ? "mi_session_events outside acquire .. submit" : "the session was created without plc");
 		return MI_EINVAL;
 	}
-	*h_events = s->h_ev[(int)(s->submitted % SLOTS)];
+	*h_events = s->h_ev[s->pipe.next_slot()];
 	return MI_OK;
 }
 
 int mi_session_submit(mi_session *s) {
 	MI_CHECK_ARG(s != nullptr);
-	if (!s->acquired) {
+	if (!s->pipe.acquired) {
 		mi::set_error("mi_session_submit without mi_session_acquire");
 		return MI_EINVAL;
 	}
 	mi_ctx *c = s->ctx;
-	if (c->activate() != MI_OK) return MI_ENODEV;
-	const int slot = (int)(s->submitted % SLOTS);
 	const size_t n = (size_t)s->n;
-	// upload on its own stream
-	MI_HIP(hipMemcpyAsync(s->d_mic[slot], s->h_mic[slot], n * s->mic_bytes, hipMemcpyHostToDevice, s->s_up));
-	if (s->ref_bytes) MI_HIP(hipMemcpyAsync(s->d_ref[slot], s->h_ref[slot], n * s->ref_bytes, hipMemcpyHostToDevice, s->s_up));
-	if (s->plc) MI_HIP(hipMemcpyAsync(s->d_ev[slot], s->h_ev[slot], n, hipMemcpyHostToDevice, s->s_up));
-	MI_HIP(hipEventRecord(s->ev_up[slot], s->s_up));
-	// kernels wait for this tick's upload and for the download that last read this slot's output buffer
-	MI_HIP(hipStreamWaitEvent(c->stream, s->ev_up[slot], 0));
-	if (s->used[slot]) MI_HIP(hipStreamWaitEvent(c->stream, s->ev_down[slot], 0));
-	int rc;
-	if (s->cfg.use_graphs) {
-		if (!s->graph[slot]) {
-			// first use of the slot: run eagerly once is not an option (state would advance twice), so capture directly
-			if ((rc = mi_ctx_capture_begin(c)) != MI_OK) return rc;
-			rc = run_tick_kernels(s, slot);
-			mi_graph *g = nullptr;
-			const int rc2 = mi_ctx_capture_end(c, &g);
-			if (rc != MI_OK) return rc;
-			if (rc2 != MI_OK) return rc2;
-			s->graph[slot] = g;
-		}
-		if ((rc = mi_graph_launch(s->graph[slot])) != MI_OK) return rc;
-	} else if ((rc = run_tick_kernels(s, slot)) != MI_OK) {
-		return rc;
-	}
-	MI_HIP(hipEventRecord(s->ev_done[slot], c->stream));
-	// download on its own stream
-	MI_HIP(hipStreamWaitEvent(s->s_down, s->ev_done[slot], 0));
-	MI_HIP(hipMemcpyAsync(s->h_out[slot], s->d_out[slot], n * s->out_bytes, hipMemcpyDeviceToHost, s->s_down));
-	MI_HIP(hipEventRecord(s->ev_down[slot], s->s_down));
-	s->used[slot] = true;
-	s->submitted++;
-	s->acquired = false;
-	return MI_OK;
+	return s->pipe.submit(
+	    [&](int slot) {
+		    MI_HIP(hipMemcpyAsync(s->d_mic[slot], s->h_mic[slot], n * s->mic_bytes, hipMemcpyHostToDevice, s->pipe.s_up));
+		    if (s->ref_bytes) MI_HIP(hipMemcpyAsync(s->d_ref[slot], s->h_ref[slot], n * s->ref_bytes, hipMemcpyHostToDevice, s->pipe.s_up));
+		    if (s->plc) MI_HIP(hipMemcpyAsync(s->d_ev[slot], s->h_ev[slot], n, hipMemcpyHostToDevice, s->pipe.s_up));
+		    return MI_OK;
+	    },
+	    [&](int slot) {
+		    if (!s->cfg.use_graphs) return run_tick_kernels(s, slot);
+		    int rc;
+		    if (!s->graph[slot]) {
+			    // first use of the slot: run eagerly once is not an option (state would advance twice), so capture directly
+			    if ((rc = mi_ctx_capture_begin(c)) != MI_OK) return rc;
+			    rc = run_tick_kernels(s, slot);
+			    mi_graph *g = nullptr;
+			    const int rc2 = mi_ctx_capture_end(c, &g);
+			    if (rc != MI_OK) return rc;
+			    if (rc2 != MI_OK) return rc2;
+			    s->graph[slot] = g;
+		    }
+		    return mi_graph_launch(s->graph[slot]);
+	    },
+	    [&](int slot) {
+		    MI_HIP(hipMemcpyAsync(s->h_out[slot], s->d_out[slot], n * s->out_bytes, hipMemcpyDeviceToHost, s->pipe.s_down));
+		    return MI_OK;
+	    });
 }
 
 int mi_session_collect(mi_session *s, const int16_t **h_out) {
 	MI_CHECK_ARG(s && h_out);
-	if (s->collected >= s->submitted) {
-		mi::set_error("nothing in flight");
-		return MI_EINVAL;
-	}
-	if (s->ctx->activate() != MI_OK) return MI_ENODEV;
-	const int slot = (int)(s->collected % SLOTS);
-	MI_HIP(hipEventSynchronize(s->ev_down[slot]));
+	int slot;
+	const int rc = s->pipe.collect(&slot);
+	if (rc == mi::TickPipe::EMPTY) mi::set_error("nothing in flight");
+	if (rc != MI_OK) return rc;
 	*h_out = s->h_out[slot];
-	s->collected++;
 	return MI_OK;
 }
 
-int mi_session_in_flight(const mi_session *s) { return s ? (int)(s->submitted - s->collected) : 0; }
+int mi_session_in_flight(const mi_session *s) { return s ? s->pipe.in_flight() : 0; }
 
 // ---- conference control plane (what MSAudioConference drives through the mixer's methods, src/voip/audioconference.c:
 // mute = MS_AUDIO_MIXER_SET_ACTIVE 0, listen-only = MS_AUDIO_MIXER_ENABLE_OUTPUT ..., per-member input gain) and the level
 // meter read-out (MS_VOLUME_GET_LINEAR) an active-speaker detector polls.  Both wait for the ticks already submitted.
 int mi_session_set_controls(mi_session *s, const uint8_t *h_flags, const float *h_gain) {
 	MI_CHECK_ARG(s && (h_flags || h_gain));
-	if (h_flags) s->flags.assign(h_flags, h_flags + s->n);
+	if (h_flags) s->roster.set_flags(h_flags);
 	return mi_mixer_set_controls(s->mix, h_flags, h_gain); // [nconf][members] == [nstreams]
 }
 
@@ -427,32 +372,30 @@ int mi_session_set_controls(mi_session *s, const uint8_t *h_flags, const float *
 // their state (their MSFilter objects survive) and so do their streams here.
 int mi_session_add_member(mi_session *s, int stream) {
 	MI_CHECK_ARG(s && stream >= 0 && stream < s->n);
-	if (s->flags[(size_t)stream] & MI_MIX_LINKED) {
+	if (s->roster.is_member(stream)) {
 		mi::set_error("mi_session_add_member: stream %d is a member already", stream);
 		return MI_EINVAL;
 	}
 	const int rc = mi_session_reset_streams(s, stream, 1);
 	if (rc != MI_OK) return rc;
-	s->flags[(size_t)stream] = MI_MIX_LINKED | MI_MIX_ACTIVE | MI_MIX_OUTPUT;
-	s->joined[(size_t)stream] = ++s->join_seq; // appended to the member list
-	return mi_mixer_set_controls(s->mix, s->flags.data(), nullptr);
+	s->roster.join(stream);
+	return mi_mixer_set_controls(s->mix, s->roster.flags.data(), nullptr);
 }
 
 // ms_audio_conference_remove_member (:366-374): the pin is unplumbed -- it neither contributes nor receives; the row of
 // its output is left alone from now on (zeros in a fresh download buffer).  The others carry on.
 int mi_session_remove_member(mi_session *s, int stream) {
 	MI_CHECK_ARG(s && stream >= 0 && stream < s->n);
-	if (!(s->flags[(size_t)stream] & MI_MIX_LINKED)) {
+	if (!s->roster.leave(stream)) {
 		mi::set_error("mi_session_remove_member: stream %d is no member", stream);
 		return MI_EINVAL;
 	}
-	s->flags[(size_t)stream] = 0;
-	const int rc = mi_mixer_set_controls(s->mix, s->flags.data(), nullptr);
+	const int rc = mi_mixer_set_controls(s->mix, s->roster.flags.data(), nullptr);
 	if (rc != MI_OK) return rc;
 	if (s->ctx->activate() != MI_OK) return MI_ENODEV;
 	// the mixer leaves an unplumbed pin's row alone: what the departed leg last heard must not linger in the buffers
 	MI_HIP(hipStreamSynchronize(s->ctx->stream));
-	if (s->s_down) MI_HIP(hipStreamSynchronize(s->s_down));
+	if (s->pipe.s_down) MI_HIP(hipStreamSynchronize(s->pipe.s_down));
 	for (int i = 0; i < SLOTS; ++i) {
 		if (s->d_out[i]) MI_HIP(hipMemsetAsync((uint8_t *)s->d_out[i] + (size_t)stream * s->out_bytes, 0, s->out_bytes, s->ctx->stream));
 		if (s->d_mix[i]) MI_HIP(hipMemsetAsync(s->d_mix[i] + (size_t)stream * s->len, 0, (size_t)s->len * 2, s->ctx->stream));
@@ -462,23 +405,16 @@ int mi_session_remove_member(mi_session *s, int stream) {
 }
 
 int mi_session_member_count(const mi_session *s, int conference) {
-	if (!s || conference < 0 || conference >= s->nconf) return MI_EINVAL;
-	const int mm = s->cfg.members_per_conference;
-	int c = 0;
-	for (int m = 0; m < mm; ++m) c += (s->flags[(size_t)conference * mm + m] & MI_MIX_LINKED) != 0;
-	return c;
+	if (!s || conference < 0 || conference >= s->roster.nconf) return MI_EINVAL;
+	return s->roster.count(conference);
 }
 
-// ms_audio_conference_process_events' election in mixer mode (:436-452, mi::elect_active_speakers).  now_ms: the caller's
-// clock (the ticker's time).
+// ms_audio_conference_process_events' election in mixer mode (:436-452, mi::Roster::elect).  now_ms: the caller's clock
+// (the ticker's time); not read (mi::active_speakers).
 int mi_session_active_speakers(mi_session *s, uint64_t now_ms, int32_t *h_winner, float *h_max_db) {
 	MI_CHECK_ARG(s && h_winner);
-	(void)now_ms; // the windows run on the device, one record per tick (msvolume.c:404)
-	std::vector<float> mx((size_t)s->n);
-	const int rc = mi_volume_get_max(s->vol, 0, s->n, mx.data());
-	if (rc != MI_OK) return rc;
-	mi::elect_active_speakers(mx.data(), s->flags.data(), s->joined.data(), s->nconf, s->cfg.members_per_conference, h_winner, h_max_db);
-	return MI_OK;
+	(void)now_ms;
+	return mi::active_speakers(s->vol, s->roster, h_winner, h_max_db);
 }
 
 // A call leg leaves and another takes its place: every per-stream state of the chain goes back to its initial value
@@ -490,13 +426,7 @@ int mi_session_reset_streams(mi_session *s, int first, int count) {
 	if (s->ctx->activate() != MI_OK) return MI_ENODEV;
 	if (s->rs && (rc = mi_resampler_reset(s->rs, first, count)) != MI_OK) return rc;
 	if ((rc = mi_aec_reset(s->aec, first, count)) != MI_OK) return rc;
-	mi_volume_state st;
-	memset(&st, 0, sizeof(st));
-	st.gain = st.target_gain = 1; // volume_init msvolume.c:92
-	st.ng_gain = 1;               // :112
-	std::vector<mi_volume_state> all((size_t)count, st);
-	if ((rc = mi_volume_set_state(s->vol, first, count, all.data())) != MI_OK) return rc;
-	if ((rc = mi_volume_reset_max(s->vol, first, count)) != MI_OK) return rc;
+	if ((rc = mi::reset_meters(s->vol, first, count)) != MI_OK) return rc;
 	if ((rc = mi_fifo_reset_range(s->f_mic, first, count)) != MI_OK || (rc = mi_fifo_reset_range(s->f_ref, first, count)) != MI_OK ||
 	    (rc = mi_fifo_reset_range(s->f_out, first, count)) != MI_OK)
 		return rc;
@@ -509,8 +439,8 @@ int mi_session_reset_streams(mi_session *s, int first, int count) {
 		const int delay = s->cfg.ref_delay_ms * s->cfg.rate / 1000;
 		std::vector<uint8_t> gate((size_t)s->n, 0);
 		for (int i = 0; i < count; ++i) gate[(size_t)(first + i)] = 1;
-		MI_HIP(hipMemcpyAsync(s->d_ok[0], gate.data(), (size_t)s->n, hipMemcpyHostToDevice, s->ctx->stream));
-		if ((rc = mi_fifo_push_gated(s->f_ref, s->d_zero, delay, delay, s->d_ok[0])) != MI_OK) return rc;
+		MI_HIP(hipMemcpyAsync(s->d_reset_gate, gate.data(), (size_t)s->n, hipMemcpyHostToDevice, s->ctx->stream));
+		if ((rc = mi_fifo_push_gated(s->f_ref, s->d_zero, delay, delay, s->d_reset_gate)) != MI_OK) return rc;
 		MI_HIP(hipStreamSynchronize(s->ctx->stream)); // gate is a stack-lifetime buffer
 	}
 	if (s->cfg.stagger && (rc = mi_aec_stagger_fifos(s->aec, s->f_mic, s->f_ref, s->len, first, count)) != MI_OK) return rc;
@@ -519,11 +449,7 @@ int mi_session_reset_streams(mi_session *s, int first, int count) {
 
 int mi_session_get_levels(mi_session *s, float *h_linear) {
 	MI_CHECK_ARG(s && h_linear);
-	std::vector<mi_volume_state> st((size_t)s->n);
-	const int rc = mi_volume_get_state(s->vol, 0, s->n, st.data());
-	if (rc != MI_OK) return rc;
-	for (int i = 0; i < s->n; ++i) h_linear[i] = st[(size_t)i].energy; // volume_get_linear msvolume.c:129-134
-	return MI_OK;
+	return mi::get_levels(s->vol, s->n, h_linear);
 }
 
 } // extern "C"

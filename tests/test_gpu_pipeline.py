@@ -526,6 +526,55 @@ def test_session_mute_and_levels(ctx):
     se.close()
 
 
+def test_session_refusals_leave_the_ring_as_it_was(ctx):
+    """submit without acquire, collect with nothing in flight and a fourth acquire at three in flight each raise MiError and
+    leave in_flight() where it was; the seven ticks that follow (three in flight, so every slot is used at least twice more)
+    and the three before them come out as from a second session fed the same input one tick at a time without the refusals."""
+    n, ns, before, after = 2, 160, 3, 7
+    mk = lambda: ms.Session(ctx, n, members=n, in_rate=16000, rate=16000, tail_ms=32, agc=False, use_graphs=False)
+    mic = np.stack([synth_pcm(70 + s, ns * (before + after), rate=16000, sigma=2500.0) for s in range(n)])
+    far = np.stack([synth_pcm(80 + s, ns * (before + after), rate=16000, sigma=3000.0) for s in range(n)])
+
+    def feed(se, t):
+        m, r = se.acquire()
+        m[:] = mic[:, t * ns:(t + 1) * ns]
+        r[:] = far[:, t * ns:(t + 1) * ns]
+        se.submit()
+
+    def refused(se, call):
+        held = se.in_flight()
+        with pytest.raises(ms.MiError):
+            call()
+        assert se.in_flight() == held
+
+    b = mk()
+    want = []
+    for t in range(before + after):
+        feed(b, t)
+        want.append(b.collect().copy())
+    assert np.stack(want).any()
+
+    a = mk()
+    refused(a, a.submit)
+    refused(a, a.collect)
+    for t in range(before):
+        feed(a, t)
+    assert a.in_flight() == 3
+    refused(a, a.acquire)
+    refused(a, a.submit)
+    got = [a.collect().copy() for _ in range(before)]
+    refused(a, a.collect)
+    for t in range(before, before + after):
+        if a.in_flight() == 3:
+            got.append(a.collect().copy())
+        feed(a, t)
+    while a.in_flight():
+        got.append(a.collect().copy())
+    np.testing.assert_array_equal(np.stack(got), np.stack(want))
+    a.close()
+    b.close()
+
+
 def test_session_members_join_and_leave_like_msaudioconference(ctx):
     """ms_audio_conference_remove_member / add_member (src/voip/audioconference.c:322-374) on a running session.
     A leg that leaves neither contributes nor hears: the remaining members' rows equal those of a twin session in which

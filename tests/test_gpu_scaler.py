@@ -131,3 +131,43 @@ def test_the_pipelined_scaler_equals_the_synchronous_one(ctx):
     np.testing.assert_array_equal(got, want)
     pipe.close()
     sc.close()
+
+
+@pytest.mark.parametrize("depth", [1, 2])
+def test_the_scaler_pipe_reuses_its_slots(ctx, depth):
+    """mi_scaler_pipe at depth 1 (every submit reuses the one slot) and 2: five batches of up to two 16x16 -> 8x8 frames,
+    the last of one frame, come out bit-equal to mi_scaler_process_host with the right frame count per batch; submit
+    without acquire, collect with nothing in flight and an acquire beyond the depth raise MiError and leave in_flight()
+    where it was."""
+    rng = np.random.default_rng(17)
+    sc = ms.ScalerBatch(ctx, 16, 16, 8, 8, ms.MI_PIX_RGB24)
+    pipe = ms.ScalerPipe(sc, 2, depth=depth)
+    sizes = [2, 2, 2, 2, 1]
+    frames = rng.integers(0, 256, (sum(sizes), sc.src_bytes), dtype=np.uint8)
+    want = sc.process(frames)
+
+    def refused(call):
+        held = pipe.in_flight()
+        with pytest.raises(ms.MiError):
+            call()
+        assert pipe.in_flight() == held
+
+    refused(lambda: pipe.submit(1))
+    refused(pipe.collect)
+    got, sent = [], 0
+    for n in sizes:
+        if pipe.in_flight() == depth:
+            refused(pipe.acquire)
+            refused(lambda: pipe.submit(1))
+            got.append(pipe.collect()[:, :sc.dst_bytes].copy())
+        buf = pipe.acquire()
+        buf[:n, :sc.src_bytes] = frames[sent:sent + n]
+        pipe.submit(n)
+        sent += n
+    while pipe.in_flight():
+        got.append(pipe.collect()[:, :sc.dst_bytes].copy())
+    refused(pipe.collect)
+    assert [g.shape[0] for g in got] == sizes
+    np.testing.assert_array_equal(np.concatenate(got), want)
+    pipe.close()
+    sc.close()

@@ -34,3 +34,16 @@ def test_host_runtime_is_clean_under_the_sanitizers(built, variant, marks):
         report = [ln for ln in r.stderr.splitlines() if any(m in ln for m in marks)]
         assert r.returncode == 0 and not report, "\n".join(report[:20]) + r.stderr[-1500:]
         assert r.stdout.startswith("ok ")
+
+
+def test_the_roster_is_the_oracle_conference_under_the_sanitizers(built):
+    """mi::Roster (csrc/conference.hpp: what mi_session and mi_bridge keep of MSAudioConference) driven by
+    tests/host/roster_check.cpp next to the oracle's conference book (oracle/conference.c): created full; leave, then count;
+    a rejoin goes to the end of the joining order and loses the tie it used to win; a muted member is skipped; a loudest
+    member at or below -30 dB elects nobody; two conferences are independent; join of a member and leave of a non-member
+    are reported.  Every winner and size is the oracle's; the program runs under AddressSanitizer + UBSan."""
+    r = subprocess.run([os.path.join(HOST, "san-asan", "roster_check")], capture_output=True, text=True, timeout=60,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
+    report = [ln for ln in r.stderr.splitlines() if any(m in ln for m in ("AddressSanitizer", "LeakSanitizer", "runtime error"))]
+    assert r.returncode == 0 and not report, r.stderr[-1500:]
+    assert r.stdout.startswith("ok roster ")
