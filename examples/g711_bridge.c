@@ -6,6 +6,11 @@
  *
  *   cc -std=c99 -Iinclude examples/g711_bridge.c -Lmediastreamer2_amd -lmsmi355x -Wl,-rpath,$PWD/mediastreamer2_amd
  *
+ *   ./a.out            the mix at the legs' own 8 kHz
+ *   ./a.out 16000      the same narrowband legs in a wideband conference (16000, 24000 or 48000): every pin gets the
+ *                      in_resampler and out_resampler of plumb_to_conf (audioconference.c:209-257), inside the same launch
+ *                      (mi_bridge_create_rated).  The rows stay 80 bytes: the pitch is the widest LEG's tick.
+ *
  * Every 10 ms: the RTP side hands over one PCMU payload of 80 bytes per leg (or nothing: the leg is absent for the tick),
  * and takes back the 80 bytes to send to that leg: everybody else in its conference, mixed and encoded.
  */
@@ -34,7 +39,7 @@ static void rtp_send(int leg, const uint8_t payload[80]) {
 	(void)payload;
 }
 
-int main(void) {
+int main(int argc, char **argv) {
 	mi_ctx *ctx;
 	mi_bridge *br;
 	mi_bridge_config cfg;
@@ -43,6 +48,7 @@ int main(void) {
 	uint8_t *flags;
 	int32_t winner[CONFERENCES];
 	float level[CONFERENCES];
+	const int conference_rate = argc > 1 ? atoi(argv[1]) : 8000;
 
 	if (mi_ctx_create(0, NULL, &ctx) != MI_OK) {
 		fprintf(stderr, "no MI355X: %s\n", mi_last_error()); /* there is no CPU fallback */
@@ -51,10 +57,21 @@ int main(void) {
 	mi_bridge_default_config(&cfg); /* 8 kHz, mu-law in, mu-law out */
 	cfg.nstreams = legs;
 	cfg.members_per_conference = MEMBERS;
-	if (mi_bridge_create(ctx, &cfg, &br) != MI_OK) {
+	if (conference_rate == 8000) {
+		rc = mi_bridge_create(ctx, &cfg, &br);
+	} else { /* the legs stay 8 kHz G.711; cfg.rate is the conference's */
+		int32_t *leg_rate = (int32_t *)malloc(sizeof(int32_t) * (size_t)legs);
+		for (leg = 0; leg < legs; ++leg) leg_rate[leg] = 8000;
+		cfg.rate = conference_rate;
+		rc = mi_bridge_create_rated(ctx, &cfg, leg_rate, &br);
+		free(leg_rate);
+	}
+	if (rc != MI_OK) {
 		fprintf(stderr, "mi_bridge_create: %s\n", mi_last_error());
 		return 1;
 	}
+	rc = 0;
+	if (mi_bridge_leg_rate(br, 0) != 8000) return 1;
 	/* pin 1 of every conference is muted (MS_AUDIO_MIXER_SET_ACTIVE 0: it hears, nobody hears it); pin 2 is a source that
 	 * is only listened to -- an announcement player: nothing is sent back to it (MS_AUDIO_MIXER_ENABLE_OUTPUT 0) */
 	flags = (uint8_t *)malloc((size_t)legs);

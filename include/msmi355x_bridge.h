@@ -13,8 +13,18 @@
  * conventions are msmi355x.h's: MI_OK or a negative MI_E* code, mi_last_error() for the message, one thread at a time
  * per context.
  *
+ * Legs at their own rate (mi_bridge_create_rated): plumb_to_conf (audioconference.c:209-257) puts an in_resampler in front
+ * of every mixer pin and an out_resampler behind it, configured from the endpoint's rate and the conference's.  A bridge
+ * runs both inside the same launch (bridge_rated_kernel) for legs at the conference's rate / 2, / 3 or / 6 -- 8 and
+ * 16 kHz legs in a 16, 24 or 48 kHz mix, the ratios of the resampler's tile-FIR kernels at quality 3 -- bit for bit
+ * equal to mi_resampler_process_masked called in front of and behind mi_mixer_process (tests/test_gpu_bridge_rates.py).
+ * MSVolume sits in front of the in_resampler: meter, one-second window and gain run on the leg's own samples at the
+ * leg's rate.  An absent leg gives its in_resampler no block and a pin without MI_MIX_OUTPUT gives its out_resampler
+ * none: their histories stay as they are.
+ *
  * Out of scope, on purpose:
- *   - members at another rate than their conference (resamplers): mi_session and the MSFilter plugin do that;
+ *   - legs ABOVE their conference's rate, ratios that are no whole number (44.1 kHz; 32 kHz in 48 kHz) and whole ratios
+ *     other than 2, 3 and 6: refused with MI_ENOTSUP -- mi_session and the MSFilter plugin resample those;
  *   - jitter buffering and flow control: the host's, as with mi_session -- a leg whose packet is missing at the tick is
  *     flagged absent (or concealed, cfg.plc);
  *   - the plugin's server legs (MSMI355XServer*) keep their own launches: the plugin is built against the same ABI
@@ -42,19 +52,33 @@ typedef struct mi_bridge_config {
 void mi_bridge_default_config(mi_bridge_config *c); /* 32 x 32 legs, 8 kHz, mu-law in and out, no plc */
 /* MI_ENOTSUP: rate % 800 != 0, or a conference's tick that does not fit 64 KB of LDS (50 members up to 64 kHz) */
 int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out);
+/* The same with every leg at a rate of its own: cfg->rate is the conference's, h_leg_rate [nstreams] the rate of each
+ * leg's code words or PCM, in AND out (one endpoint has one rate, audioconference.c:226-230).  h_leg_rate == NULL, or
+ * every entry == cfg->rate, is mi_bridge_create exactly.  Supported: cfg->rate / leg rate in {1, 2, 3, 6} with
+ * leg rate % 800 == 0.  MI_ENOTSUP, the message naming the value, before anything is allocated: a leg above the
+ * conference; a ratio that is no whole number, or another one; cfg->plc with legs of more than one rate (the concealer
+ * batch has one: with one common leg rate it runs at that rate); a conference whose tick plus the resamplers' scratch
+ * does not fit the 64 KB of LDS the kernel allows itself (48 kHz with 8 kHz legs: up to 41 members). */
+int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, mi_bridge **out);
 void mi_bridge_destroy(mi_bridge *b);
-/* bytes per stream and tick of the two host buffers */
+int mi_bridge_leg_rate(const mi_bridge *b, int stream); /* the leg's rate in Hz, or MI_EINVAL */
+/* bytes per stream and tick of the two host buffers: the row pitch, which is the tick of the WIDEST leg of the bridge
+ * (a bridge of 8 kHz G.711 legs in a 48 kHz conference moves 80-byte rows) */
 int mi_bridge_tick_bytes(const mi_bridge *b, int *in_bytes, int *out_bytes);
 
 /* pinned staging of the NEXT tick, to be filled in place: h_in [nstreams][rate/100] uint8 code words or int16 PCM;
  * h_present [nstreams] uint8, preset to 1 -- clear a leg's byte when nothing arrived from it for this tick: its row
  * is ignored, MSVolume gets no chunk (meter state, gain ramp and one-second window stay as they are, msvolume.c:480-486)
  * and the mixer reads silence for the pin (audiomixer.c:88).  With cfg.plc the leg is concealed instead (MI_PLC_CONCEAL)
- * and metered on what the concealer made. */
+ * and metered on what the concealer made.
+ * With legs at their own rate the row pitch is mi_bridge_tick_bytes' (the widest leg's tick); a narrower leg fills the
+ * first leg rate / 100 samples of its row and the rest is ignored. */
 int mi_bridge_acquire(mi_bridge *b, void **h_in, uint8_t **h_present);
 int mi_bridge_submit(mi_bridge *b);
 /* the OLDEST tick in flight: waits for its download, returns the pinned output [nstreams][rate/100] (uint8 code words
- * or int16 PCM; valid until three more ticks have been submitted).  Rows of pins without MI_MIX_OUTPUT are not written. */
+ * or int16 PCM; valid until three more ticks have been submitted).  Rows of pins without MI_MIX_OUTPUT are not written.
+ * With legs at their own rate: rows at mi_bridge_tick_bytes' pitch, a narrower leg's mix in the first leg rate / 100
+ * samples of its row, the rest of the row left as it is. */
 int mi_bridge_collect(mi_bridge *b, const void **h_out);
 int mi_bridge_in_flight(const mi_bridge *b); /* up to three */
 
@@ -65,7 +89,8 @@ int mi_bridge_set_controls(mi_bridge *b, const uint8_t *h_flags, const float *h_
  * mi_volume_default_params (a meter at unity gain).  An echo-limiter peer (params.peer != -1) is MI_ENOTSUP: a bridge
  * has no far end to limit against. */
 int mi_bridge_set_volume_params(mi_bridge *b, int first, int count, const mi_volume_params *h_params);
-/* a leg was replaced: the meter (and concealer) of streams [first, first + count) start over as new filters would */
+/* a leg was replaced: the meter (and concealer, and both resamplers' histories) of streams [first, first + count) start
+ * over as new filters would */
 int mi_bridge_reset_streams(mi_bridge *b, int first, int count);
 /* MSAudioConference membership (audioconference.c:322-374), as mi_session_add_member / _remove_member: a bridge is
  * created full; remove unplumbs the pin and clears its output row, add plumbs it for a NEW endpoint (fresh meter) */

@@ -885,7 +885,10 @@ class Bridge(_ConferenceBatch):
     Context of its own on `device`."""
     _destroy, _prefix = "mi_bridge_destroy", "bridge"
 
-    def __init__(self, ctx, nstreams, members=32, rate=8000, in_codec=MI_SESSION_PCMU, out_codec=MI_SESSION_PCMU, plc=False, device=0):
+    def __init__(self, ctx, nstreams, members=32, rate=8000, in_codec=MI_SESSION_PCMU, out_codec=MI_SESSION_PCMU, plc=False, device=0,
+                 leg_rates=None):
+        """leg_rates: the rate of every leg's code words or PCM [nstreams] (mi_bridge_create_rated: rate / leg rate in
+        {1, 2, 3, 6}); None: every leg at `rate`."""
         self._own_ctx = ctx is None
         self.ctx = ctx = Context(device) if ctx is None else ctx
         cfg = BridgeConfig()
@@ -893,9 +896,15 @@ class Bridge(_ConferenceBatch):
         cfg.nstreams, cfg.members_per_conference, cfg.rate = nstreams, members, rate
         cfg.in_codec, cfg.out_codec, cfg.plc = in_codec, out_codec, int(plc)
         h = C.c_void_p()
-        check(ctx.L.mi_bridge_create(ctx.h, C.byref(cfg), C.byref(h)))
+        if leg_rates is None:
+            check(ctx.L.mi_bridge_create(ctx.h, C.byref(cfg), C.byref(h)))
+        else:
+            lr = np.ascontiguousarray(leg_rates, np.int32)
+            assert lr.shape == (nstreams,), "one rate per leg"
+            check(ctx.L.mi_bridge_create_rated(ctx.h, C.byref(cfg), lr.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(h)))
         self.h = h
-        self.n, self.members, self.len = nstreams, members, rate // 100
+        self.n, self.members = nstreams, members
+        self.len = rate // 100 if leg_rates is None else int(max(leg_rates)) // 100  # the row pitch: the widest leg's tick
         self.in_dtype = C.c_uint8 if in_codec else C.c_int16
         self.out_dtype = C.c_uint8 if out_codec else C.c_int16
 
@@ -913,14 +922,21 @@ class Bridge(_ConferenceBatch):
         check(self.ctx.L.mi_bridge_tick_bytes(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def leg_rate(self, stream):
+        r = self.ctx.L.mi_bridge_leg_rate(self.h, int(stream))
+        check(min(r, 0))
+        return r
+
     def acquire(self):
-        """numpy views of the pinned staging of the next tick: (in [n, len] code words or PCM, present [n] uint8 preset to 1)."""
+        """numpy views of the pinned staging of the next tick: (in [n, len] code words or PCM, present [n] uint8 preset to 1).
+        len is the row pitch, the widest leg's tick; a narrower leg fills the first leg_rate / 100 samples of its row."""
         pi, pp = C.c_void_p(), C.c_void_p()
         check(self.ctx.L.mi_bridge_acquire(self.h, C.byref(pi), C.byref(pp)))
         return self._view(pi, self.in_dtype, self.n, self.len), self._view(pp, C.c_uint8, self.n)
 
     def collect(self):
-        """numpy view of the oldest in-flight tick's output [n, len] (pinned; valid for three more submits)."""
+        """numpy view of the oldest in-flight tick's output [n, len] (pinned; valid for three more submits); len is the row
+        pitch, a narrower leg's mix is the first leg_rate / 100 samples of its row and the rest is left as it is."""
         po = C.c_void_p()
         check(self.ctx.L.mi_bridge_collect(self.h, C.byref(po)))
         return self._view(po, self.out_dtype, self.n, self.len)

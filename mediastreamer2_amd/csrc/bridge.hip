@@ -231,6 +231,355 @@ void launch_out(int out_kind, dim3 grid, size_t lds, hipStream_t st, const Bridg
 	else hipLaunchKernelGGL((bridge_tick_kernel<IN, 2>), grid, dim3(BT), lds, st, a);
 }
 
+// ---- legs at their own rate (mi_bridge_create_rated): in_resampler and out_resampler of plumb_to_conf
+// (audioconference.c:209-257) folded into the tick.  A member's ratio -- conference rate / leg rate, 1, 2, 3 or 6 -- is
+// data: one conference holds 8, 16 and 48 kHz legs side by side.  The rows in LDS are at the conference's rate; a
+// narrower leg's tick sits at the head of its row until its up-sampler has run.
+#include "resample_tile.hpp"
+
+constexpr int RS_FILT = 48, RS_R = 8;       // quality 3: 48 taps per polyphase row, fir_tile's eight positions
+constexpr size_t RATED_STATIC_LDS = 2048;   // bound on the kernel's static LDS (tests/test_bridge_rates_cpu.py holds it)
+
+struct RatedArgs {
+	BridgeArgs b;         // ns, row_w, sum_off, sample_rate: the conference's
+	const uint8_t *ratio; // [nconf * mm] conference rate / leg rate
+	int16_t *hist_in;     // [nconf * mm][48] in_resampler: the last 47 leg-rate samples, as mi_resampler keeps them
+	int16_t *hist_out;    // [nconf * mm][hout_stride] out_resampler: the last ratio * 48 - 1 conference-rate samples
+	const float *tab;     // every table of the bridge, back to back
+	int tab_up[7];        // float offset of ratio r's up table [r][48] (polyphase rows, mi_resampler's own layout)
+	int tab_down[7];      // and of its down table, phase-major [r][48]: tap r * i + p at [p][i]
+	int pitch;            // samples per row of in / out: the widest leg's tick
+	int hout_stride;
+	int scratch_off, scratch_per_wave; // bytes: each wavefront's resampler scratch in the dynamic LDS
+};
+
+// floats per phase array of the down-sampler (history ++ tick split by input phase, + the tile FIR's look-ahead)
+__host__ __device__ inline int rated_plen(int num, int in_len) { return ((num * RS_FILT - 1 + in_len + num - 1) / num + RS_R + 8 + 3) & ~3; }
+
+__device__ __forceinline__ void load_taps(const float *row, f2 (&t2)[RS_FILT / 2]) {
+	const float4 *tp = reinterpret_cast<const float4 *>(row);
+#pragma unroll
+	for (int j = 0; j < RS_FILT / 4; ++j) {
+		const float4 v = tp[j];
+		t2[2 * j] = (f2){v.x, v.y}, t2[2 * j + 1] = (f2){v.z, v.w};
+	}
+}
+
+// One wavefront runs one member's in_resampler: resample_up_kernel's arithmetic in its order (resample.hip) --
+// out[m * den + p] = sum_j table[p][j] * x[m + j] through fir_tile from a zero accumulator, then rs_word2int --, the
+// tick read from the head of the member's row, the result written over the row.  x: [47 + in_len + slack] floats.
+__device__ __forceinline__ void rated_up(float *x, int16_t *row, int16_t *hist, const float *tab, int den, int in_len, int lane) {
+	constexpr int HIST = RS_FILT - 1, HQ = RS_FILT / 4;
+	const int xn = (HIST + in_len + RS_R + 1 + 3) & ~3;
+	for (int q = lane; q < HQ + (in_len >> 2); q += 64) {
+		const bool h = q < HQ;
+		const short4 v = h ? *reinterpret_cast<const short4 *>(hist + 4 * q) : *reinterpret_cast<const short4 *>(row + 4 * (q - HQ));
+		const int b = h ? 4 * q : HIST + 4 * (q - HQ);
+		x[b] = (float)v.x, x[b + 1] = (float)v.y, x[b + 2] = (float)v.z;
+		if (!h || b + 3 < HIST) x[b + 3] = (float)v.w; // the history row's pad slot is not a sample
+	}
+	for (int i = HIST + in_len + lane; i < xn; i += 64) x[i] = 0.f;
+	wave_sync(); // the whole tick is staged before the first output lands on the row
+	const int nlanes = den * (in_len >> 3);
+	for (int base = 0; base < nlanes; base += 64) {
+		const int l = base + lane;
+		const bool on = l < nlanes;
+		const int tile = on ? l / den : 0, p = on ? l - tile * den : 0;
+		f2 t2[RS_FILT / 2], acc2[RS_R / 2];
+		load_taps(tab + p * RS_FILT, t2);
+#pragma unroll
+		for (int q = 0; q < RS_R / 2; ++q) acc2[q] = (f2){0.f, 0.f};
+		fir_tile<RS_FILT, RS_R>(x + tile * RS_R, t2, acc2);
+		if (on) {
+#pragma unroll
+			for (int q = 0; q < RS_R / 2; ++q) {
+				row[(tile * RS_R + 2 * q) * den + p] = rs_word2int(acc2[q].x);
+				row[(tile * RS_R + 2 * q + 1) * den + p] = rs_word2int(acc2[q].y);
+			}
+		}
+	}
+	// new history = the last 47 samples of history ++ tick; the pad slot takes the zero slack
+	if (lane < HQ) {
+		const float *hx = x + in_len + 4 * lane;
+		short4 h;
+		h.x = (int16_t)hx[0], h.y = (int16_t)hx[1], h.z = (int16_t)hx[2], h.w = (int16_t)hx[3];
+		*reinterpret_cast<short4 *>(hist + 4 * lane) = h;
+	}
+	wave_sync(); // x is read out before the wave's next member stages over it
+}
+
+// One wavefront runs one member's out_resampler: resample_down_kernel's arithmetic in its order -- history ++ row split by
+// input phase, each phase's share of eight outputs through fir_tile, the shares added phase upward, rs_word2int --; the
+// leg-rate tick leaves as 16 bytes of PCM or 8 code words per lane.  xp: [num][plen] ++ [in_len] floats.
+template <int OUT>
+__device__ __forceinline__ void rated_down(float *xp, const int16_t *row, int16_t *hist, const float *tab, void *out, size_t at, int num,
+                                           int in_len, int lane) {
+	const int HIST = num * RS_FILT - 1, hq = (num * RS_FILT) >> 2, nq = hq + (in_len >> 2);
+	const int out_len = in_len / num, plen = rated_plen(num, in_len);
+	float *part = xp + num * plen; // [out_len][num] partial sums
+	for (int i = lane; i < num * plen; i += 64) xp[i] = 0.f;
+	wave_sync();
+	for (int q = lane; q < nq; q += 64) {
+		const bool h = q < hq;
+		const short4 v = h ? *reinterpret_cast<const short4 *>(hist + 4 * q) : *reinterpret_cast<const short4 *>(row + 4 * (q - hq));
+		const int b = h ? 4 * q : HIST + 4 * (q - hq); // index in history ++ row
+		const short e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+		for (int k = 0; k < 4; ++k) {
+			const int i = b + k;
+			if (!h || i < HIST) xp[(i % num) * plen + i / num] = (float)e[k];
+		}
+	}
+	wave_sync();
+	const int nlanes = num * (out_len >> 3);
+	for (int base = 0; base < nlanes; base += 64) {
+		const int l = base + lane;
+		const bool on = l < nlanes;
+		const int tile = on ? l / num : 0, p = on ? l - tile * num : 0;
+		f2 t2[RS_FILT / 2], acc2[RS_R / 2];
+		load_taps(tab + p * RS_FILT, t2);
+#pragma unroll
+		for (int q = 0; q < RS_R / 2; ++q) acc2[q] = (f2){0.f, 0.f};
+		fir_tile<RS_FILT, RS_R>(xp + p * plen + tile * RS_R, t2, acc2);
+		if (on) {
+			float *d = part + (tile * RS_R) * num + p;
+#pragma unroll
+			for (int q = 0; q < RS_R / 2; ++q) d[(2 * q) * num] = acc2[q].x, d[(2 * q + 1) * num] = acc2[q].y;
+		}
+	}
+	wave_sync();
+	for (int g = lane; g < (out_len >> 3); g += 64) {
+		const float *ps = part + g * 8 * num;
+		int o[8];
+#pragma unroll
+		for (int k = 0; k < 8; ++k) {
+			float sum = 0.f;
+			for (int p = 0; p < num; ++p) sum += ps[k * num + p];
+			o[k] = rs_word2int(sum);
+		}
+		if (OUT == 0) {
+			*reinterpret_cast<uint4 *>(static_cast<int16_t *>(out) + at + 8 * g) =
+			    make_uint4(pack16(o[0], o[1]), pack16(o[2], o[3]), pack16(o[4], o[5]), pack16(o[6], o[7]));
+		} else {
+			uint32_t cw[2] = {0, 0};
+#pragma unroll
+			for (int k = 0; k < 8; ++k) cw[k >> 2] |= (OUT == 2 ? lin2ulaw(o[k]) : lin2alaw(o[k])) << (8 * (k & 3));
+			*reinterpret_cast<uint2 *>(static_cast<uint8_t *>(out) + at + 8 * g) = make_uint2(cw[0], cw[1]);
+		}
+	}
+	// new history = the last HIST samples of history ++ row; the pad slot of the row takes a zero
+	for (int q = lane; q < hq; q += 64) {
+		short4 h;
+		short *hp = &h.x;
+#pragma unroll
+		for (int k = 0; k < 4; ++k) {
+			const int i = in_len + 4 * q + k;
+			hp[k] = (4 * q + k < HIST) ? (short)xp[(i % num) * plen + i / num] : (short)0;
+		}
+		*reinterpret_cast<short4 *>(hist + 4 * q) = h;
+	}
+	wave_sync();
+}
+
+// bridge_tick_kernel with the two resamplers of every member whose ratio is not 1.  Phases (0) (A) (B) as there, on the leg's
+// own samples (MSVolume sits in front of the in_resampler: chunk length and sample rate are the leg's);
+//   (G) the Q12 gain on the leg-rate samples, in the row;
+//   (U) one wavefront per member, the four waves taking members in turn: the in_resampler of a present, plumbed leg
+//       (the run mask present & linked of mi_resampler_process_masked; any other keeps its history);
+//   (C) (D) at the conference's rate; (D) writes a narrower leg's mix over its own row instead of storing it;
+//   (W) one wavefront per member: the out_resampler of a pin with its output on, then the store / encoder.
+template <int IN, int OUT>
+__global__ __launch_bounds__(BT) void bridge_rated_kernel(RatedArgs ra) {
+	extern __shared__ __attribute__((aligned(16))) char smem[];
+	const BridgeArgs &a = ra.b;
+	uint2 *rows = reinterpret_cast<uint2 *>(smem);
+	int *s_sum = reinterpret_cast<int *>(smem + a.sum_off);
+	__shared__ int s_pk[BMAX], s_dc[BMAX];
+	__shared__ int4 s_par[BMAX];
+	__shared__ unsigned char s_rt[BMAX], s_on[BMAX]; // a member's ratio; whether it is here this tick
+	const int t = threadIdx.x, c = blockIdx.x, mm = a.mm, ns = a.ns, nw = ns >> 2, ng = ns >> 3;
+	const int s0 = c * mm;
+
+	// ---- (0)
+	mi_volume_params p;
+	mi_volume_state st;
+	float2 win = make_float2(0, 0);
+	unsigned mflag = 0;
+	int mgain_bits = 0, rt = 1;
+	bool here = false;
+	if (t < mm) {
+		const int s = s0 + t;
+		p = a.params[s];
+		st = a.state[s];
+		win = a.win[s];
+		mflag = a.flags[s];
+		mgain_bits = __float_as_int(a.gain[s]);
+		here = !a.present || a.present[s] != 0;
+		rt = ra.ratio[s];
+		s_rt[t] = (unsigned char)rt, s_on[t] = here;
+	}
+	for (int i = t; i < ns; i += BT) s_sum[i] = 0;
+
+	// ---- (A) the leg's own groups; the rest of the row is zeros
+	for (int mb = 0; mb < mm; mb += BT / 8) {
+		const int m = mb + (t >> 3), q = t & 7;
+		const bool valid = m < mm;
+		int pk = 0, dc = 0;
+		if (valid) {
+			const bool on = !a.present || a.present[s0 + m] != 0;
+			const int ngl = ng / ra.ratio[s0 + m];
+			for (int g0 = q; g0 < ng; g0 += 32) {
+				uint4 v[4];
+#pragma unroll
+				for (int i = 0; i < 4; ++i) {
+					v[i] = make_uint4(0, 0, 0, 0);
+					if (on && g0 + 8 * i < ngl) v[i] = load_group<IN>(a.in, (size_t)(s0 + m), ra.pitch, g0 + 8 * i);
+				}
+#pragma unroll
+				for (int i = 0; i < 4; ++i) {
+					const int g = g0 + 8 * i;
+					if (g >= ng) continue;
+					rows[m * a.row_w + 2 * g] = make_uint2(v[i].x, v[i].y);
+					rows[m * a.row_w + 2 * g + 1] = make_uint2(v[i].z, v[i].w);
+					const unsigned w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+#pragma unroll
+					for (int k = 0; k < 4; ++k) {
+						const int x0 = lo16(w[k]), x1 = hi16(w[k]);
+						pk = max(pk, max(x0 < 0 ? -x0 : x0, x1 < 0 ? -x1 : x1));
+						dc += x0 + x1;
+					}
+				}
+			}
+		}
+#pragma unroll
+		for (int off = 1; off < 8; off <<= 1) {
+			pk = max(pk, __shfl_xor(pk, off));
+			dc += __shfl_xor(dc, off);
+		}
+		if (valid && q == 0) s_pk[m] = pk, s_dc[m] = dc;
+	}
+	__syncthreads();
+
+	// ---- (B) over the leg's rate / 100 samples
+	if (t < mm) {
+		if (here) {
+			const uint2 *r = rows + t * a.row_w;
+			const int nwl = nw / rt;
+			float acc = 0;
+#pragma unroll 4
+			for (int i = 0; i < nwl; ++i) {
+				const uint2 w = r[i];
+				const int x0 = lo16(w.x), x1 = hi16(w.x), x2 = lo16(w.y), x3 = hi16(w.y);
+				acc += (float)(x0 * x0);
+				acc += (float)(x1 * x1);
+				acc += (float)(x2 * x2);
+				acc += (float)(x3 * x3);
+			}
+			const VolCtl o = volume_control(p, st, 0.f, acc, ns / rt, s_pk[t], s_dc[t], a.sample_rate / rt, win);
+			s_par[t] = make_int4((int)mflag | (o.mode << 8), o.intgain, o.dcoff, mgain_bits);
+			a.state[s0 + t] = st;
+			a.win[s0 + t] = win;
+		} else {
+			s_par[t] = make_int4((int)mflag, 4096, 0, mgain_bits);
+		}
+	}
+	__syncthreads();
+
+	// ---- (G) apply_gain (msvolume.c:440) in front of the in_resampler, whose history keeps the levelled samples
+	for (int item = t; item < mm * nw; item += BT) {
+		const int m = item / nw, j = item - m * nw;
+		const int4 par = s_par[m];
+		const int mode = par.x >> 8;
+		if (mode == 0 || j >= nw / s_rt[m]) continue;
+		const uint2 cur = rows[m * a.row_w + j];
+		int x[4] = {lo16(cur.x), hi16(cur.x), lo16(cur.y), hi16(cur.y)};
+		const int ig = par.y, dc = (mode == 2) ? par.z : 0;
+#pragma unroll
+		for (int k = 0; k < 4; ++k) x[k] = sat16(((x[k] - dc) * ig) / 4096);
+		rows[m * a.row_w + j] = make_uint2(pack16(x[0], x[1]), pack16(x[2], x[3]));
+	}
+	__syncthreads();
+
+	// ---- (U)
+	const int wave = t >> 6, lane = t & 63;
+	float *scr = reinterpret_cast<float *>(smem + ra.scratch_off + wave * ra.scratch_per_wave);
+	for (int m = wave; m < mm; m += BT / 64) {
+		const int den = s_rt[m];
+		if (den == 1 || !s_on[m] || !((unsigned)s_par[m].x & MI_MIX_LINKED)) continue;
+		rated_up(scr, reinterpret_cast<int16_t *>(rows + m * a.row_w), ra.hist_in + (size_t)(s0 + m) * RS_FILT, ra.tab + ra.tab_up[den], den,
+		         ns / den, lane);
+	}
+	__syncthreads();
+
+	// ---- (C) the gain is in the rows already
+	for (int item = t; item < a.nslice * nw; item += BT) {
+		const int r = item / nw, j = item - r * nw;
+		int sum[4] = {0, 0, 0, 0};
+		for (int m = r; m < mm; m += a.nslice) {
+			const int4 par = s_par[m];
+			const unsigned f = (unsigned)par.x & 0xffu;
+			uint2 o = make_uint2(0, 0);
+			if ((f & MI_MIX_LINKED) && (f & MI_MIX_ACTIVE)) {
+				const uint2 cur = rows[m * a.row_w + j];
+				int x[4] = {lo16(cur.x), hi16(cur.x), lo16(cur.y), hi16(cur.y)};
+				const float gn = __int_as_float(par.w);
+				if (gn != 1.0f) {
+#pragma unroll
+					for (int k = 0; k < 4; ++k) x[k] = sat16((int)(gn * (float)x[k]));
+				}
+#pragma unroll
+				for (int k = 0; k < 4; ++k) sum[k] += x[k];
+				o = make_uint2(pack16(x[0], x[1]), pack16(x[2], x[3]));
+			}
+			rows[m * a.row_w + j] = o;
+		}
+#pragma unroll
+		for (int k = 0; k < 4; ++k) atomicAdd(&s_sum[4 * j + k], sum[k]);
+	}
+	__syncthreads();
+
+	// ---- (D)
+	for (int item = t; item < mm * ng; item += BT) {
+		const int m = item / ng, g = item - m * ng;
+		if (!((unsigned)s_par[m].x & MI_MIX_OUTPUT)) continue;
+		const uint2 own0 = rows[m * a.row_w + 2 * g], own1 = rows[m * a.row_w + 2 * g + 1];
+		const int4 sa = *reinterpret_cast<const int4 *>(s_sum + 8 * g), sb = *reinterpret_cast<const int4 *>(s_sum + 8 * g + 4);
+		const int o[8] = {sat16(sa.x - lo16(own0.x)), sat16(sa.y - hi16(own0.x)), sat16(sa.z - lo16(own0.y)), sat16(sa.w - hi16(own0.y)),
+		                  sat16(sb.x - lo16(own1.x)), sat16(sb.y - hi16(own1.x)), sat16(sb.z - lo16(own1.y)), sat16(sb.w - hi16(own1.y))};
+		if (s_rt[m] != 1) { // the out_resampler's input
+			rows[m * a.row_w + 2 * g] = make_uint2(pack16(o[0], o[1]), pack16(o[2], o[3]));
+			rows[m * a.row_w + 2 * g + 1] = make_uint2(pack16(o[4], o[5]), pack16(o[6], o[7]));
+			continue;
+		}
+		const size_t at = (size_t)(s0 + m) * ra.pitch + 8 * g;
+		if (OUT == 0) {
+			*reinterpret_cast<uint4 *>(static_cast<int16_t *>(a.out) + at) =
+			    make_uint4(pack16(o[0], o[1]), pack16(o[2], o[3]), pack16(o[4], o[5]), pack16(o[6], o[7]));
+		} else {
+			uint32_t cw[2] = {0, 0};
+#pragma unroll
+			for (int k = 0; k < 8; ++k) cw[k >> 2] |= (OUT == 2 ? lin2ulaw(o[k]) : lin2alaw(o[k])) << (8 * (k & 3));
+			*reinterpret_cast<uint2 *>(static_cast<uint8_t *>(a.out) + at) = make_uint2(cw[0], cw[1]);
+		}
+	}
+	__syncthreads();
+
+	// ---- (W)
+	for (int m = wave; m < mm; m += BT / 64) {
+		const int num = s_rt[m];
+		if (num == 1 || !((unsigned)s_par[m].x & MI_MIX_OUTPUT)) continue;
+		rated_down<OUT>(scr, reinterpret_cast<const int16_t *>(rows + m * a.row_w), ra.hist_out + (size_t)(s0 + m) * ra.hout_stride,
+		                ra.tab + ra.tab_down[num], a.out, (size_t)(s0 + m) * ra.pitch, num, ns, lane);
+	}
+}
+
+template <int IN>
+void launch_rated_out(int out_kind, dim3 grid, size_t lds, hipStream_t st, const RatedArgs &a) {
+	if (out_kind == MI_SESSION_PCM16) hipLaunchKernelGGL((bridge_rated_kernel<IN, 0>), grid, dim3(BT), lds, st, a);
+	else if (out_kind == MI_SESSION_PCMA) hipLaunchKernelGGL((bridge_rated_kernel<IN, 1>), grid, dim3(BT), lds, st, a);
+	else hipLaunchKernelGGL((bridge_rated_kernel<IN, 2>), grid, dim3(BT), lds, st, a);
+}
+
 } // namespace
 
 struct mi_bridge {
@@ -249,6 +598,15 @@ struct mi_bridge {
 	int16_t *d_pcm = nullptr; // plc behind a decoder: the decoded rows the concealer edits
 	int32_t *d_evlen = nullptr;
 	mi::Roster roster;
+	// legs at their own rate (mi_bridge_create_rated); a same-rate bridge has none of it and pitch == len
+	bool rated = false;
+	int pitch = 0;                 // samples per row of the host buffers: the widest leg's tick
+	std::vector<int32_t> leg_rate; // [n], empty: every leg at cfg.rate
+	uint8_t *d_ratio = nullptr;
+	int16_t *d_hist_in = nullptr, *d_hist_out = nullptr;
+	float *d_tab = nullptr;
+	int tab_up[7] = {}, tab_down[7] = {};
+	int hout_stride = 0, scratch_off = 0, scratch_per_wave = 0;
 };
 
 namespace {
@@ -261,12 +619,12 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 	if (b->plc) { // MSAlawDec / MSUlawDec as a launch of its own, then MSGenericPLC on the PCM rows, in place
 		int16_t *rows = reinterpret_cast<int16_t *>(b->d_in[slot]);
 		if (cf.in_codec) {
-			if ((rc = mi_g711_decode(b->ctx, cf.in_codec == MI_SESSION_PCMA ? MI_LAW_PCMA : MI_LAW_PCMU, b->d_in[slot], (size_t)b->len, b->d_pcm,
-			                         (size_t)b->len, nullptr, b->len, (size_t)b->n)) != MI_OK)
+			if ((rc = mi_g711_decode(b->ctx, cf.in_codec == MI_SESSION_PCMA ? MI_LAW_PCMA : MI_LAW_PCMU, b->d_in[slot], (size_t)b->pitch, b->d_pcm,
+			                         (size_t)b->pitch, nullptr, b->pitch, (size_t)b->n)) != MI_OK)
 				return rc;
 			rows = b->d_pcm;
 		}
-		if ((rc = mi_plc_process(b->plc, rows, (size_t)b->len, b->d_evlen, b->d_ev[slot])) != MI_OK) return rc;
+		if ((rc = mi_plc_process(b->plc, rows, (size_t)b->pitch, b->d_evlen, b->d_ev[slot])) != MI_OK) return rc;
 		in = rows, in_kind = MI_SESSION_PCM16, present = nullptr; // a concealed leg counts as present
 	}
 	VolumeView vv;
@@ -280,10 +638,66 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 	a.mm = b->mm, a.ns = b->len, a.row_w = b->row_w, a.nslice = b->nslice, a.sum_off = b->sum_off;
 	a.sample_rate = cf.rate;
 	const dim3 grid((unsigned)b->nconf);
+	if (b->rated) {
+		RatedArgs ra;
+		ra.b = a;
+		ra.ratio = b->d_ratio, ra.hist_in = b->d_hist_in, ra.hist_out = b->d_hist_out, ra.tab = b->d_tab;
+		memcpy(ra.tab_up, b->tab_up, sizeof(ra.tab_up));
+		memcpy(ra.tab_down, b->tab_down, sizeof(ra.tab_down));
+		ra.pitch = b->pitch, ra.hout_stride = b->hout_stride;
+		ra.scratch_off = b->scratch_off, ra.scratch_per_wave = b->scratch_per_wave;
+		if (in_kind == MI_SESSION_PCM16) launch_rated_out<0>(cf.out_codec, grid, b->lds, b->ctx->stream, ra);
+		else if (in_kind == MI_SESSION_PCMA) launch_rated_out<1>(cf.out_codec, grid, b->lds, b->ctx->stream, ra);
+		else launch_rated_out<2>(cf.out_codec, grid, b->lds, b->ctx->stream, ra);
+		MI_LAUNCH_CHECK();
+		return MI_OK;
+	}
 	if (in_kind == MI_SESSION_PCM16) launch_out<0>(cf.out_codec, grid, b->lds, b->ctx->stream, a);
 	else if (in_kind == MI_SESSION_PCMA) launch_out<1>(cf.out_codec, grid, b->lds, b->ctx->stream, a);
 	else launch_out<2>(cf.out_codec, grid, b->lds, b->ctx->stream, a);
 	MI_LAUNCH_CHECK();
+	return MI_OK;
+}
+
+// ---- the resamplers' state, next to the meters' (conference.hpp): a NEW endpoint brings new resamplers, their histories
+// zero as speex_resampler_init leaves them.  On the context's stream, behind the ticks submitted.
+int reset_resamplers(mi_bridge *b, int first, int count) {
+	if (!b->rated || count == 0) return MI_OK;
+	if (b->ctx->activate() != MI_OK) return MI_ENODEV;
+	MI_HIP(hipMemsetAsync(b->d_hist_in + (size_t)first * RS_FILT, 0, (size_t)count * RS_FILT * sizeof(int16_t), b->ctx->stream));
+	MI_HIP(hipMemsetAsync(b->d_hist_out + (size_t)first * b->hout_stride, 0, (size_t)count * b->hout_stride * sizeof(int16_t), b->ctx->stream));
+	return MI_OK;
+}
+
+// the polyphase table of mi_resampler's own design code (quality 3, what msresample.c uses) for in_rate -> out_rate
+int design_table(mi_ctx *ctx, int in_rate, int out_rate, std::vector<float> &table) {
+	mi_resampler *r = nullptr;
+	int rc = mi_resampler_create(ctx, 1, (uint32_t)in_rate, (uint32_t)out_rate, 3, &r);
+	if (rc != MI_OK) return rc;
+	table.resize((size_t)mi_resampler_get_table(r, nullptr, 0));
+	mi_resampler_get_table(r, table.data(), (int)table.size());
+	mi_resampler_destroy(r);
+	return MI_OK;
+}
+
+// one table per distinct ratio and direction, built once: ratio r up [r][48] as designed, down [r][48] phase-major
+int build_tables(mi_bridge *b, const bool (&used)[7]) {
+	std::vector<float> all, t;
+	for (int r = 2; r < 7; ++r) {
+		if (!used[r]) continue;
+		int rc;
+		if ((rc = design_table(b->ctx, b->cfg.rate / r, b->cfg.rate, t)) != MI_OK) return rc;
+		if (t.size() != (size_t)r * RS_FILT) return MI_ENOTSUP;
+		b->tab_up[r] = (int)all.size();
+		all.insert(all.end(), t.begin(), t.end());
+		if ((rc = design_table(b->ctx, b->cfg.rate, b->cfg.rate / r, t)) != MI_OK) return rc;
+		if (t.size() != (size_t)r * RS_FILT) return MI_ENOTSUP;
+		b->tab_down[r] = (int)all.size();
+		for (int p = 0; p < r; ++p)
+			for (int i = 0; i < RS_FILT; ++i) all.push_back(t[(size_t)i * r + p]);
+	}
+	if (!(b->d_tab = (float *)mi_dev_alloc(b->ctx, all.size() * sizeof(float)))) return MI_ENOMEM;
+	MI_HIP(hipMemcpy(b->d_tab, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
 	return MI_OK;
 }
 
@@ -311,6 +725,8 @@ void mi_bridge_destroy(mi_bridge *b) {
 		for (uint8_t *p : {b->d_in[i], b->d_present[i], b->d_ev[i], b->d_out[i]})
 			if (p) mi_dev_free(c, p);
 	}
+	for (void *p : {(void *)b->d_ratio, (void *)b->d_hist_in, (void *)b->d_hist_out, (void *)b->d_tab})
+		if (p) mi_dev_free(c, p);
 	if (b->d_pcm) mi_dev_free(c, b->d_pcm);
 	if (b->d_evlen) mi_dev_free(c, b->d_evlen);
 	if (b->plc) mi_plc_destroy(b->plc);
@@ -320,7 +736,9 @@ void mi_bridge_destroy(mi_bridge *b) {
 	delete b;
 }
 
-int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) {
+int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) { return mi_bridge_create_rated(ctx, cfg, nullptr, out); }
+
+int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, mi_bridge **out) {
 	MI_CHECK_ARG(ctx && cfg && out);
 	*out = nullptr;
 	MI_CHECK_ARG(cfg->nstreams > 0 && cfg->members_per_conference > 0 && cfg->members_per_conference <= MI_MIXER_MAX_CHANNELS &&
@@ -334,12 +752,67 @@ int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) 
 	}
 	const int len = cfg->rate / 100, mm = cfg->members_per_conference;
 	const int row_w = (len >> 2) | 1; // 8-byte words per row, odd
-	const size_t sum_off = mi::round_up((size_t)mm * row_w * 8, 16), lds = sum_off + (size_t)len * 4;
-	if (lds > BRIDGE_LDS_MAX) {
+	// ---- the legs' rates: every refusal before anything is allocated
+	bool used[7] = {};
+	int widest = 0, common = 0, max_ratio = 1;
+	bool rated = false;
+	if (h_leg_rate) {
+		for (int s = 0; s < cfg->nstreams; ++s) {
+			const int lr = h_leg_rate[s];
+			MI_CHECK_ARG(lr > 0);
+			if (lr > cfg->rate) {
+				mi::set_error("mi_bridge_create_rated: leg %d at %d Hz is above its conference's %d Hz (only legs at or below the mix are resampled)",
+				              s, lr, cfg->rate);
+				return MI_ENOTSUP;
+			}
+			if (cfg->rate % lr != 0) {
+				mi::set_error("mi_bridge_create_rated: leg %d at %d Hz in a %d Hz conference is no whole ratio (%.3f); supported: 1, 2, 3, 6", s, lr,
+				              cfg->rate, (double)cfg->rate / lr);
+				return MI_ENOTSUP;
+			}
+			const int r = cfg->rate / lr;
+			if (r != 1 && r != 2 && r != 3 && r != 6) {
+				mi::set_error("mi_bridge_create_rated: leg %d at %d Hz in a %d Hz conference is ratio %d; supported: 1, 2, 3, 6", s, lr, cfg->rate, r);
+				return MI_ENOTSUP;
+			}
+			if (lr % 800 != 0) {
+				mi::set_error("mi_bridge_create_rated: leg %d's rate %d is no multiple of 800 (a 10 ms tick must be whole groups of 8 samples)", s, lr);
+				return MI_ENOTSUP;
+			}
+			if (cfg->plc && common && lr != common) {
+				mi::set_error("mi_bridge_create_rated: plc with legs at %d Hz and %d Hz: the concealer batch has one rate", common, lr);
+				return MI_ENOTSUP;
+			}
+			if (!common) common = lr;
+			used[r] = true;
+			widest = std::max(widest, lr);
+			max_ratio = std::max(max_ratio, r);
+		}
+		rated = max_ratio > 1;
+	}
+	const size_t sum_off = mi::round_up((size_t)mm * row_w * 8, 16);
+	size_t lds = sum_off + (size_t)len * 4, scratch_off = 0, scratch = 0;
+	if (rated) {
+		for (int r = 2; r < 7; ++r) {
+			if (!used[r]) continue;
+			const size_t up = (size_t)((RS_FILT - 1 + len / r + RS_R + 1 + 3) & ~3) * 4;
+			const size_t down = ((size_t)r * rated_plen(r, len) + (size_t)len) * 4;
+			scratch = std::max(scratch, mi::round_up(std::max(up, down), 16));
+		}
+		scratch_off = mi::round_up(lds, 16);
+		lds = scratch_off + (BT / 64) * scratch;
+		if (lds + RATED_STATIC_LDS > BRIDGE_LDS_MAX) {
+			mi::set_error("mi_bridge_create_rated: a conference's tick and its resamplers' scratch must fit %zu bytes of LDS (%d members x %d samples "
+			              "= %zu, + %d wavefronts x %zu for ratio %d, + %zu of the kernel's own: %zu)",
+			              BRIDGE_LDS_MAX, mm, len, scratch_off, BT / 64, scratch, max_ratio, RATED_STATIC_LDS, lds + RATED_STATIC_LDS);
+			return MI_ENOTSUP;
+		}
+	} else if (lds > BRIDGE_LDS_MAX) {
 		mi::set_error("mi_bridge_create: a conference's tick must fit %zu bytes of LDS (%d members x %d samples need %zu)", BRIDGE_LDS_MAX, mm,
 		              len, lds);
 		return MI_ENOTSUP;
 	}
+	const int pitch = rated ? widest / 100 : len;
 	if (ctx->activate() != MI_OK) return MI_ENODEV;
 	mi_bridge *b = new mi_bridge();
 	b->ctx = b->pipe.ctx = ctx;
@@ -352,8 +825,10 @@ int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) 
 	b->sum_off = (int)sum_off;
 	b->lds = lds;
 	b->nslice = std::max(1, std::min(mm, BT / (len >> 2)));
-	b->in_bytes = (size_t)len * (cfg->in_codec ? 1 : 2);
-	b->out_bytes = (size_t)len * (cfg->out_codec ? 1 : 2);
+	b->rated = rated, b->pitch = pitch;
+	b->in_bytes = (size_t)pitch * (cfg->in_codec ? 1 : 2);
+	b->out_bytes = (size_t)pitch * (cfg->out_codec ? 1 : 2);
+	if (h_leg_rate) b->leg_rate.assign(h_leg_rate, h_leg_rate + cfg->nstreams);
 	b->roster.init(b->n, mm);
 	int rc = MI_OK;
 	auto fail = [&](int code) {
@@ -376,12 +851,25 @@ int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) 
 		MI_HIP(hipMemsetAsync(b->d_out[i], 0, n * b->out_bytes, ctx->stream));
 		memset(b->h_out[i], 0, n * b->out_bytes);
 	}
-	if (cfg->plc) {
-		if ((rc = mi_plc_create(ctx, b->n, cfg->rate, len, &b->plc)) != MI_OK) return fail(rc);
-		std::vector<int32_t> lens(n, len);
+	if (rated) {
+		b->scratch_off = (int)scratch_off, b->scratch_per_wave = (int)scratch;
+		b->hout_stride = max_ratio * RS_FILT; // mi_resampler's round_up(filt_len - 1, 8) of the longest filter
+		std::vector<uint8_t> ratio(n);
+		for (size_t s = 0; s < n; ++s) ratio[s] = (uint8_t)(cfg->rate / h_leg_rate[s]);
+		b->d_ratio = (uint8_t *)mi_dev_alloc(ctx, n);
+		b->d_hist_in = (int16_t *)mi_dev_alloc(ctx, n * RS_FILT * sizeof(int16_t));
+		b->d_hist_out = (int16_t *)mi_dev_alloc(ctx, n * b->hout_stride * sizeof(int16_t));
+		if (!b->d_ratio || !b->d_hist_in || !b->d_hist_out) return fail(MI_ENOMEM);
+		if (hipMemcpy(b->d_ratio, ratio.data(), n, hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
+		if ((rc = reset_resamplers(b, 0, b->n)) != MI_OK) return fail(rc);
+		if ((rc = build_tables(b, used)) != MI_OK) return fail(rc);
+	}
+	if (cfg->plc) { // at the legs' one rate, on rows of the host buffers' pitch
+		if ((rc = mi_plc_create(ctx, b->n, rated ? common : cfg->rate, pitch, &b->plc)) != MI_OK) return fail(rc);
+		std::vector<int32_t> lens(n, pitch);
 		if (!(b->d_evlen = (int32_t *)mi_dev_alloc(ctx, n * 4))) return fail(MI_ENOMEM);
 		if (hipMemcpy(b->d_evlen, lens.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
-		if (cfg->in_codec && !(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * len * 2))) return fail(MI_ENOMEM);
+		if (cfg->in_codec && !(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * pitch * 2))) return fail(MI_ENOMEM);
 		for (int i = 0; i < SLOTS; ++i) {
 			b->h_ev[i] = (uint8_t *)mi_host_alloc(ctx, n);
 			b->d_ev[i] = (uint8_t *)mi_dev_alloc(ctx, n);
@@ -391,6 +879,11 @@ int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) 
 	if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(MI_ENODEV);
 	*out = b;
 	return MI_OK;
+}
+
+int mi_bridge_leg_rate(const mi_bridge *b, int stream) {
+	if (!b || stream < 0 || stream >= b->n) return MI_EINVAL;
+	return b->leg_rate.empty() ? b->cfg.rate : b->leg_rate[(size_t)stream];
 }
 
 int mi_bridge_tick_bytes(const mi_bridge *b, int *in_bytes, int *out_bytes) {
@@ -474,7 +967,7 @@ int mi_bridge_reset_streams(mi_bridge *b, int first, int count) {
 	int rc;
 	if ((rc = mi::reset_meters(b->vol, first, count)) != MI_OK) return rc;
 	if (b->plc && (rc = mi_plc_reset(b->plc, first, count)) != MI_OK) return rc;
-	return MI_OK;
+	return reset_resamplers(b, first, count);
 }
 
 int mi_bridge_add_member(mi_bridge *b, int stream) {
