@@ -22,11 +22,23 @@
  * leg's rate.  An absent leg gives its in_resampler no block and a pin without MI_MIX_OUTPUT gives its out_resampler
  * none: their histories stay as they are.
  *
+ * Legs with their own codec (mi_bridge_create_legs): plumb_to_conf hangs each endpoint's own decoder and encoder on its
+ * mixer pin, so a leg's codec pair -- A-law, mu-law or 16-bit PCM in, and any of the three out -- is data as its rate is:
+ * A-law and mu-law trunks in one narrowband mix, 8 kHz G.711 callers beside 16 kHz PCM members (whose codec the host
+ * decodes) in one wideband conference.  Still one launch per tick (bridge_legs_kernel, with or without the resamplers) and
+ * bit for bit the parts called one by one, mi_g711_decode / _encode once per law (tests/test_gpu_bridge_legs.py).  The
+ * host rows are then BYTE rows: the pitch is the widest leg's tick in bytes rounded up to 16, a leg fills or receives the
+ * first mi_bridge_leg_bytes of its row.  A bridge whose legs all name one pair is the one mi_bridge_create_rated builds:
+ * the same kernels, pitch and tick bytes.
+ *
  * Out of scope, on purpose:
  *   - legs ABOVE their conference's rate, ratios that are no whole number (44.1 kHz; 32 kHz in 48 kHz) and whole ratios
  *     other than 2, 3 and 6: refused with MI_ENOTSUP -- mi_session and the MSFilter plugin resample those;
  *   - jitter buffering and flow control: the host's, as with mi_session -- a leg whose packet is missing at the tick is
  *     flagged absent (or concealed, cfg.plc);
+ *   - cfg.plc on a bridge whose legs differ in codec: refused with MI_ENOTSUP -- the concealer batch sits behind ONE
+ *     decoder launch;
+ *   - codecs other than G.711 and 16-bit PCM (G.722, Opus): the host's -- such a leg is a PCM leg of the bridge;
  *   - the plugin's server legs (MSMI355XServer*) keep their own launches: the plugin is built against the same ABI
  *     as its host double, which knows msmi355x.h only.
  */
@@ -60,10 +72,26 @@ int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out);
  * batch has one: with one common leg rate it runs at that rate); a conference whose tick plus the resamplers' scratch
  * does not fit the 64 KB of LDS the kernel allows itself (48 kHz with 8 kHz legs: up to 41 members). */
 int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, mi_bridge **out);
+/* The same with every leg's codec pair its own as well.  cfg->rate is the conference's; cfg->in_codec and cfg->out_codec
+ * are not read.  Rates follow mi_bridge_create_rated's rules.  h_legs == NULL is mi_bridge_create exactly; legs that all
+ * name one pair give mi_bridge_create_rated's bridge with that pair.  MI_ENOTSUP, the message naming the leg and the
+ * value, before anything is allocated: a codec outside the three; cfg->plc with legs that do not all share one in_codec
+ * and one out_codec. */
+typedef struct mi_bridge_leg {
+	int32_t rate;      /* Hz */
+	int32_t in_codec;  /* MI_SESSION_PCM16 | MI_SESSION_PCMA | MI_SESSION_PCMU */
+	int32_t out_codec;
+} mi_bridge_leg;
+int mi_bridge_create_legs(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */, mi_bridge **out);
 void mi_bridge_destroy(mi_bridge *b);
 int mi_bridge_leg_rate(const mi_bridge *b, int stream); /* the leg's rate in Hz, or MI_EINVAL */
+/* the leg's codecs and its own tick in bytes (rate / 100 x 1 or 2), on any bridge; either pointer may be NULL.
+ * MI_EINVAL for a bad stream or a NULL bridge */
+int mi_bridge_leg_codec(const mi_bridge *b, int stream, int *in_codec, int *out_codec);
+int mi_bridge_leg_bytes(const mi_bridge *b, int stream, int *in_bytes, int *out_bytes);
 /* bytes per stream and tick of the two host buffers: the row pitch, which is the tick of the WIDEST leg of the bridge
- * (a bridge of 8 kHz G.711 legs in a 48 kHz conference moves 80-byte rows) */
+ * (a bridge of 8 kHz G.711 legs in a 48 kHz conference moves 80-byte rows); where the legs' codecs differ, the widest
+ * leg's tick in BYTES, in and out each, rounded up to 16 */
 int mi_bridge_tick_bytes(const mi_bridge *b, int *in_bytes, int *out_bytes);
 
 /* pinned staging of the NEXT tick, to be filled in place: h_in [nstreams][rate/100] uint8 code words or int16 PCM;
@@ -72,13 +100,15 @@ int mi_bridge_tick_bytes(const mi_bridge *b, int *in_bytes, int *out_bytes);
  * and the mixer reads silence for the pin (audiomixer.c:88).  With cfg.plc the leg is concealed instead (MI_PLC_CONCEAL)
  * and metered on what the concealer made.
  * With legs at their own rate the row pitch is mi_bridge_tick_bytes' (the widest leg's tick); a narrower leg fills the
- * first leg rate / 100 samples of its row and the rest is ignored. */
+ * first leg rate / 100 samples of its row and the rest is ignored.  With legs of differing codecs: byte rows, a leg fills
+ * the first mi_bridge_leg_bytes of its row. */
 int mi_bridge_acquire(mi_bridge *b, void **h_in, uint8_t **h_present);
 int mi_bridge_submit(mi_bridge *b);
 /* the OLDEST tick in flight: waits for its download, returns the pinned output [nstreams][rate/100] (uint8 code words
  * or int16 PCM; valid until three more ticks have been submitted).  Rows of pins without MI_MIX_OUTPUT are not written.
  * With legs at their own rate: rows at mi_bridge_tick_bytes' pitch, a narrower leg's mix in the first leg rate / 100
- * samples of its row, the rest of the row left as it is. */
+ * samples of its row, the rest of the row left as it is.  With legs of differing codecs: byte rows, a leg's mix in the
+ * first mi_bridge_leg_bytes of its row. */
 int mi_bridge_collect(mi_bridge *b, const void **h_out);
 int mi_bridge_in_flight(const mi_bridge *b); /* up to three */
 

@@ -886,9 +886,12 @@ class Bridge(_ConferenceBatch):
     _destroy, _prefix = "mi_bridge_destroy", "bridge"
 
     def __init__(self, ctx, nstreams, members=32, rate=8000, in_codec=MI_SESSION_PCMU, out_codec=MI_SESSION_PCMU, plc=False, device=0,
-                 leg_rates=None):
+                 leg_rates=None, legs=None):
         """leg_rates: the rate of every leg's code words or PCM [nstreams] (mi_bridge_create_rated: rate / leg rate in
-        {1, 2, 3, 6}); None: every leg at `rate`."""
+        {1, 2, 3, 6}); None: every leg at `rate`.
+        legs: every leg's (rate, in_codec, out_codec) [nstreams], a sequence of triples or a structured array with those
+        fields (mi_bridge_create_legs; in_codec, out_codec and leg_rates are not read).  The staging views are then byte
+        rows, uint8 [n, pitch]: leg_in / leg_out give a leg's own slice of one."""
         self._own_ctx = ctx is None
         self.ctx = ctx = Context(device) if ctx is None else ctx
         cfg = BridgeConfig()
@@ -896,7 +899,14 @@ class Bridge(_ConferenceBatch):
         cfg.nstreams, cfg.members_per_conference, cfg.rate = nstreams, members, rate
         cfg.in_codec, cfg.out_codec, cfg.plc = in_codec, out_codec, int(plc)
         h = C.c_void_p()
-        if leg_rates is None:
+        if legs is not None:
+            lg = np.asarray(legs)
+            if lg.dtype.names:
+                lg = np.stack([lg[k] for k in ("rate", "in_codec", "out_codec")], axis=-1)
+            lg = np.ascontiguousarray(lg, np.int32)
+            assert lg.shape == (nstreams, 3), "one (rate, in_codec, out_codec) per leg"
+            check(ctx.L.mi_bridge_create_legs(ctx.h, C.byref(cfg), lg.ctypes.data, C.byref(h)))
+        elif leg_rates is None:
             check(ctx.L.mi_bridge_create(ctx.h, C.byref(cfg), C.byref(h)))
         else:
             lr = np.ascontiguousarray(leg_rates, np.int32)
@@ -907,6 +917,10 @@ class Bridge(_ConferenceBatch):
         self.len = rate // 100 if leg_rates is None else int(max(leg_rates)) // 100  # the row pitch: the widest leg's tick
         self.in_dtype = C.c_uint8 if in_codec else C.c_int16
         self.out_dtype = C.c_uint8 if out_codec else C.c_int16
+        self.in_len = self.out_len = self.len
+        if legs is not None:  # byte rows at mi_bridge_tick_bytes' pitch
+            self.in_dtype = self.out_dtype = C.c_uint8
+            self.in_len, self.out_len = self.tick_bytes()
 
     def close(self):
         super().close()
@@ -932,14 +946,38 @@ class Bridge(_ConferenceBatch):
         len is the row pitch, the widest leg's tick; a narrower leg fills the first leg_rate / 100 samples of its row."""
         pi, pp = C.c_void_p(), C.c_void_p()
         check(self.ctx.L.mi_bridge_acquire(self.h, C.byref(pi), C.byref(pp)))
-        return self._view(pi, self.in_dtype, self.n, self.len), self._view(pp, C.c_uint8, self.n)
+        return self._view(pi, self.in_dtype, self.n, self.in_len), self._view(pp, C.c_uint8, self.n)
 
     def collect(self):
         """numpy view of the oldest in-flight tick's output [n, len] (pinned; valid for three more submits); len is the row
         pitch, a narrower leg's mix is the first leg_rate / 100 samples of its row and the rest is left as it is."""
         po = C.c_void_p()
         check(self.ctx.L.mi_bridge_collect(self.h, C.byref(po)))
-        return self._view(po, self.out_dtype, self.n, self.len)
+        return self._view(po, self.out_dtype, self.n, self.out_len)
+
+    def leg_codec(self, stream):
+        """(in_codec, out_codec) of a leg"""
+        a, b = C.c_int32(), C.c_int32()
+        check(self.ctx.L.mi_bridge_leg_codec(self.h, int(stream), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def leg_bytes(self, stream):
+        """(in, out) bytes of the leg's own tick: leg rate / 100 x 1 (G.711) or 2 (PCM)"""
+        a, b = C.c_int32(), C.c_int32()
+        check(self.ctx.L.mi_bridge_leg_bytes(self.h, int(stream), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def _leg(self, view, stream, side):
+        row = view[stream].view(np.uint8)[:self.leg_bytes(stream)[side]]
+        return row if self.leg_codec(stream)[side] else row.view(np.int16)
+
+    def leg_in(self, view, stream):
+        """the leg's own slice of its row of acquire()'s view: uint8 code words or int16 PCM, leg rate / 100 of them"""
+        return self._leg(view, stream, 0)
+
+    def leg_out(self, view, stream):
+        """the same of collect()'s view (or of a copy of it)"""
+        return self._leg(view, stream, 1)
 
     def set_volume_params(self, params, first=0):
         arr = (VolumeParams * len(params))(*params)

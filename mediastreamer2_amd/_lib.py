@@ -63,6 +63,7 @@ BRIDGE_EXPORTS = [
     "mi_bridge_add_member", "mi_bridge_remove_member", "mi_bridge_member_count",
     "mi_bridge_get_levels", "mi_bridge_active_speakers", "mi_bridge_get_volume_state", "mi_bridge_get_volume_max",
     "mi_bridge_create_rated", "mi_bridge_leg_rate",
+    "mi_bridge_create_legs", "mi_bridge_leg_codec", "mi_bridge_leg_bytes",
 ]
 
 
@@ -270,6 +271,9 @@ def load():
     L.mi_bridge_tick_bytes.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.mi_bridge_create_rated.argtypes = [vp, vp, C.POINTER(C.c_int32), pp]
     L.mi_bridge_leg_rate.argtypes = [vp, i32]
+    L.mi_bridge_create_legs.argtypes = [vp, vp, vp, pp]
+    L.mi_bridge_leg_codec.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.mi_bridge_leg_bytes.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.mi_bridge_set_volume_params.argtypes = [vp, i32, i32, C.POINTER(VolumeParams)]
     L.mi_bridge_get_volume_state.argtypes = [vp, i32, i32, C.POINTER(VolumeState)]
     L.mi_bridge_get_volume_max.argtypes = [vp, i32, i32, vp]

@@ -22,6 +22,8 @@
 //   (D) lane = (member, eight columns), for every pin with its output enabled: saturate(sum - own)
 //       (channel_process_out), stored as 16 bytes of PCM or encoded to 8 code words; consecutive lanes, consecutive bytes.
 // The members are sliced in (C) so that an 80-sample tick, 20 four-column words wide, still occupies 240 lanes.
+// bridge_rated_kernel (legs at their own rate) and bridge_legs_kernel (every leg's own codec, with or without the
+// resamplers) further down keep these phases; each says at its head what it adds.
 //
 // Geometry: an 8 kHz conference of 32 is 5.4 KB of LDS and four waves, so eight such workgroups share a CU (32 waves);
 // 1000 conferences are 1000 workgroups dealt over the 256 CUs, about four per CU = one wave per SIMD and conference
@@ -78,6 +80,44 @@ __device__ __forceinline__ uint4 load_group(const void *in, size_t row, int ns, 
 __device__ __forceinline__ int lo16(unsigned w) { return (int)(short)(w & 0xffffu); }
 __device__ __forceinline__ int hi16(unsigned w) { return (int)(short)(w >> 16); }
 __device__ __forceinline__ unsigned pack16(int lo, int hi) { return (unsigned)(lo & 0xffff) | ((unsigned)hi << 16); }
+
+// ---- a leg's codec as data (mi_bridge_create_legs): `row` is the leg's byte row, whose pitch is a multiple of 16.
+// load_group with the kind in a register, in two steps so that a lane's loads are all issued before the first is used:
+// one 16-byte load whatever the kind -- a PCM leg's group, or the aligned pair of 8-byte groups that holds a G.711
+// leg's --, then both laws' decodes of the 8 code bytes and selects.  No branch: the lanes of a wavefront hold up to
+// eight members, of all three kinds.
+__device__ __forceinline__ uint4 load_raw_leg(const uint8_t *row, int kind, int g) {
+	return *reinterpret_cast<const uint4 *>(row + 16 * (kind == MI_SESSION_PCM16 ? g : g >> 1));
+}
+
+__device__ __forceinline__ uint4 decode_group_leg(uint4 v, int kind, int g) {
+	const bool pcm = kind == MI_SESSION_PCM16, mu = kind == MI_SESSION_PCMU;
+	const uint32_t w[2] = {(g & 1) ? v.z : v.x, (g & 1) ? v.w : v.y};
+	uint32_t o[4];
+#pragma unroll
+	for (int k = 0; k < 2; ++k) {
+		const uint32_t lo = __builtin_amdgcn_perm(0u, w[k], 0x0c010c00u), hi = __builtin_amdgcn_perm(0u, w[k], 0x0c030c02u);
+		const uint32_t alo = alaw2lin_x2(lo), ahi = alaw2lin_x2(hi), ulo = ulaw2lin_x2(lo), uhi = ulaw2lin_x2(hi);
+		o[2 * k] = mu ? ulo : alo;
+		o[2 * k + 1] = mu ? uhi : ahi;
+	}
+	return make_uint4(pcm ? v.x : o[0], pcm ? v.y : o[1], pcm ? v.z : o[2], pcm ? v.w : o[3]);
+}
+
+// eight samples of the leg's mix: 16 bytes of PCM, or 8 code words at the leg's law
+__device__ __forceinline__ void store_group_leg(uint8_t *row, int kind, int g, const int (&o)[8]) {
+	if (kind == MI_SESSION_PCM16) {
+		*reinterpret_cast<uint4 *>(row + 16 * g) = make_uint4(pack16(o[0], o[1]), pack16(o[2], o[3]), pack16(o[4], o[5]), pack16(o[6], o[7]));
+		return;
+	}
+	uint32_t cw[2] = {0, 0};
+#pragma unroll
+	for (int k = 0; k < 8; ++k) { // both laws and a select: a wavefront of (D) holds legs of either
+		const uint32_t a = lin2alaw(o[k]), u = lin2ulaw(o[k]);
+		cw[k >> 2] |= (kind == MI_SESSION_PCMU ? u : a) << (8 * (k & 3));
+	}
+	*reinterpret_cast<uint2 *>(row + 8 * g) = make_uint2(cw[0], cw[1]);
+}
 
 template <int IN, int OUT>
 __global__ __launch_bounds__(BT) void bridge_tick_kernel(BridgeArgs a) {
@@ -310,10 +350,11 @@ __device__ __forceinline__ void rated_up(float *x, int16_t *row, int16_t *hist, 
 
 // One wavefront runs one member's out_resampler: resample_down_kernel's arithmetic in its order -- history ++ row split by
 // input phase, each phase's share of eight outputs through fir_tile, the shares added phase upward, rs_word2int --; the
-// leg-rate tick leaves as 16 bytes of PCM or 8 code words per lane.  xp: [num][plen] ++ [in_len] floats.
+// leg-rate tick leaves as 16 bytes of PCM or 8 code words per lane.  xp: [num][plen] ++ [in_len] floats.  OUT < 0: the
+// codec is `kind`, the same in every lane of the wave, and `at` is the byte offset of the leg's row.
 template <int OUT>
 __device__ __forceinline__ void rated_down(float *xp, const int16_t *row, int16_t *hist, const float *tab, void *out, size_t at, int num,
-                                           int in_len, int lane) {
+                                           int in_len, int lane, int kind = OUT) {
 	const int HIST = num * RS_FILT - 1, hq = (num * RS_FILT) >> 2, nq = hq + (in_len >> 2);
 	const int out_len = in_len / num, plen = rated_plen(num, in_len);
 	float *part = xp + num * plen; // [out_len][num] partial sums
@@ -357,7 +398,9 @@ __device__ __forceinline__ void rated_down(float *xp, const int16_t *row, int16_
 			for (int p = 0; p < num; ++p) sum += ps[k * num + p];
 			o[k] = rs_word2int(sum);
 		}
-		if (OUT == 0) {
+		if (OUT < 0) {
+			store_group_leg(static_cast<uint8_t *>(out) + at, kind, g, o);
+		} else if (OUT == 0) {
 			*reinterpret_cast<uint4 *>(static_cast<int16_t *>(out) + at + 8 * g) =
 			    make_uint4(pack16(o[0], o[1]), pack16(o[2], o[3]), pack16(o[4], o[5]), pack16(o[6], o[7]));
 		} else {
@@ -580,6 +623,216 @@ void launch_rated_out(int out_kind, dim3 grid, size_t lds, hipStream_t st, const
 	else hipLaunchKernelGGL((bridge_rated_kernel<IN, 2>), grid, dim3(BT), lds, st, a);
 }
 
+// ---- every leg's own codec (mi_bridge_create_legs): plumb_to_conf hangs each endpoint's own decoder and encoder on its
+// pin, so the pair is data like the ratio -- A-law and mu-law trunks, and PCM members, in one mix.  The host rows are byte
+// rows at one pitch (a multiple of 16); a leg's tick is the first rate / 100 x 1 or 2 bytes of its row.  Only a bridge
+// whose legs differ runs this kernel: a uniform one keeps the kernels above, whose codecs are compile-time.
+struct LegsArgs {
+	RatedArgs r;             // r.b.in / r.b.out: the byte rows; r.pitch is not read; !RATED reads r.b only
+	const uint8_t *codec;    // [nconf * mm] in_codec | out_codec << 2
+	int in_pitch, out_pitch; // bytes per row
+};
+
+// The phases of bridge_tick_kernel (RATED false: the gain in (C)) or of bridge_rated_kernel (RATED true: (G), (U), (W)),
+// their arithmetic word for word; what differs is where a codec is chosen:
+//   (0) the member's codec pair into LDS, next to its ratio;
+//   (A) the kind is uniform over a member's eight lanes: load_raw_leg straight-line as there, then decode_group_leg;
+//   (D) store_group_leg per member; (W) the same, uniform over the wave that runs the member's out_resampler.
+template <bool RATED>
+__global__ __launch_bounds__(BT) void bridge_legs_kernel(LegsArgs la) {
+	extern __shared__ __attribute__((aligned(16))) char smem[];
+	const RatedArgs &ra = la.r;
+	const BridgeArgs &a = ra.b;
+	uint2 *rows = reinterpret_cast<uint2 *>(smem);
+	int *s_sum = reinterpret_cast<int *>(smem + a.sum_off);
+	__shared__ int s_pk[BMAX], s_dc[BMAX];
+	__shared__ int4 s_par[BMAX];
+	__shared__ unsigned char s_rt[BMAX], s_on[BMAX], s_cd[BMAX]; // a member's ratio; whether it is here this tick; its codec pair
+	const int t = threadIdx.x, c = blockIdx.x, mm = a.mm, ns = a.ns, nw = ns >> 2, ng = ns >> 3;
+	const int s0 = c * mm;
+	const uint8_t *in = static_cast<const uint8_t *>(a.in);
+	uint8_t *out = static_cast<uint8_t *>(a.out);
+
+	// ---- (0)
+	mi_volume_params p;
+	mi_volume_state st;
+	float2 win = make_float2(0, 0);
+	unsigned mflag = 0;
+	int mgain_bits = 0, rt = 1;
+	bool here = false;
+	if (t < mm) {
+		const int s = s0 + t;
+		p = a.params[s];
+		st = a.state[s];
+		win = a.win[s];
+		mflag = a.flags[s];
+		mgain_bits = __float_as_int(a.gain[s]);
+		here = !a.present || a.present[s] != 0;
+		s_cd[t] = la.codec[s];
+		if (RATED) {
+			rt = ra.ratio[s];
+			s_rt[t] = (unsigned char)rt, s_on[t] = here;
+		}
+	}
+	for (int i = t; i < ns; i += BT) s_sum[i] = 0;
+
+	// ---- (A) the leg's own groups; the rest of the row is zeros
+	for (int mb = 0; mb < mm; mb += BT / 8) {
+		const int m = mb + (t >> 3), q = t & 7;
+		const bool valid = m < mm;
+		int pk = 0, dc = 0;
+		if (valid) {
+			const bool on = !a.present || a.present[s0 + m] != 0;
+			const int kind = la.codec[s0 + m] & 3;
+			const int ngl = RATED ? ng / ra.ratio[s0 + m] : ng;
+			const uint8_t *src = in + (size_t)(s0 + m) * la.in_pitch;
+			for (int g0 = q; g0 < ng; g0 += 32) {
+				uint4 v[4];
+#pragma unroll
+				for (int i = 0; i < 4; ++i) { // straight-line loads: all in flight at once
+					v[i] = make_uint4(0, 0, 0, 0);
+					if (on && g0 + 8 * i < ngl) v[i] = load_raw_leg(src, kind, g0 + 8 * i);
+				}
+#pragma unroll
+				for (int i = 0; i < 4; ++i) {
+					const int g = g0 + 8 * i;
+					if (g >= ng) continue;
+					const uint4 d = decode_group_leg(v[i], kind, g);
+					if (on && g < ngl) v[i] = d; // (code bytes of zero are not silence)
+					rows[m * a.row_w + 2 * g] = make_uint2(v[i].x, v[i].y);
+					rows[m * a.row_w + 2 * g + 1] = make_uint2(v[i].z, v[i].w);
+					const unsigned w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+#pragma unroll
+					for (int k = 0; k < 4; ++k) {
+						const int x0 = lo16(w[k]), x1 = hi16(w[k]);
+						pk = max(pk, max(x0 < 0 ? -x0 : x0, x1 < 0 ? -x1 : x1));
+						dc += x0 + x1;
+					}
+				}
+			}
+		}
+#pragma unroll
+		for (int off = 1; off < 8; off <<= 1) {
+			pk = max(pk, __shfl_xor(pk, off));
+			dc += __shfl_xor(dc, off);
+		}
+		if (valid && q == 0) s_pk[m] = pk, s_dc[m] = dc;
+	}
+	__syncthreads();
+
+	// ---- (B) over the leg's rate / 100 samples
+	if (t < mm) {
+		if (here) {
+			const uint2 *r = rows + t * a.row_w;
+			const int nwl = nw / rt;
+			float acc = 0;
+#pragma unroll 4
+			for (int i = 0; i < nwl; ++i) {
+				const uint2 w = r[i];
+				const int x0 = lo16(w.x), x1 = hi16(w.x), x2 = lo16(w.y), x3 = hi16(w.y);
+				acc += (float)(x0 * x0);
+				acc += (float)(x1 * x1);
+				acc += (float)(x2 * x2);
+				acc += (float)(x3 * x3);
+			}
+			const VolCtl o = volume_control(p, st, 0.f, acc, ns / rt, s_pk[t], s_dc[t], a.sample_rate / rt, win);
+			s_par[t] = make_int4((int)mflag | (o.mode << 8), o.intgain, o.dcoff, mgain_bits);
+			a.state[s0 + t] = st;
+			a.win[s0 + t] = win;
+		} else {
+			s_par[t] = make_int4((int)mflag, 4096, 0, mgain_bits);
+		}
+	}
+	__syncthreads();
+
+	const int wave = t >> 6, lane = t & 63;
+	float *scr = RATED ? reinterpret_cast<float *>(smem + ra.scratch_off + wave * ra.scratch_per_wave) : nullptr;
+	if (RATED) {
+		// ---- (G)
+		for (int item = t; item < mm * nw; item += BT) {
+			const int m = item / nw, j = item - m * nw;
+			const int4 par = s_par[m];
+			const int mode = par.x >> 8;
+			if (mode == 0 || j >= nw / s_rt[m]) continue;
+			const uint2 cur = rows[m * a.row_w + j];
+			int x[4] = {lo16(cur.x), hi16(cur.x), lo16(cur.y), hi16(cur.y)};
+			const int ig = par.y, dc = (mode == 2) ? par.z : 0;
+#pragma unroll
+			for (int k = 0; k < 4; ++k) x[k] = sat16(((x[k] - dc) * ig) / 4096);
+			rows[m * a.row_w + j] = make_uint2(pack16(x[0], x[1]), pack16(x[2], x[3]));
+		}
+		__syncthreads();
+
+		// ---- (U)
+		for (int m = wave; m < mm; m += BT / 64) {
+			const int den = s_rt[m];
+			if (den == 1 || !s_on[m] || !((unsigned)s_par[m].x & MI_MIX_LINKED)) continue;
+			rated_up(scr, reinterpret_cast<int16_t *>(rows + m * a.row_w), ra.hist_in + (size_t)(s0 + m) * RS_FILT, ra.tab + ra.tab_up[den],
+			         den, ns / den, lane);
+		}
+		__syncthreads();
+	}
+
+	// ---- (C) RATED: the gain is in the rows already
+	for (int item = t; item < a.nslice * nw; item += BT) {
+		const int r = item / nw, j = item - r * nw;
+		int sum[4] = {0, 0, 0, 0};
+		for (int m = r; m < mm; m += a.nslice) {
+			const int4 par = s_par[m];
+			const unsigned f = (unsigned)par.x & 0xffu;
+			uint2 o = make_uint2(0, 0);
+			if ((f & MI_MIX_LINKED) && (f & MI_MIX_ACTIVE)) {
+				const uint2 cur = rows[m * a.row_w + j];
+				int x[4] = {lo16(cur.x), hi16(cur.x), lo16(cur.y), hi16(cur.y)};
+				const int mode = par.x >> 8;
+				if (!RATED && mode != 0) { // apply_gain (msvolume.c:440)
+					const int ig = par.y, dc = (mode == 2) ? par.z : 0;
+#pragma unroll
+					for (int k = 0; k < 4; ++k) x[k] = sat16(((x[k] - dc) * ig) / 4096);
+				}
+				const float gn = __int_as_float(par.w);
+				if (gn != 1.0f) { // channel_process_in's input gain (audiomixer.c:46-51)
+#pragma unroll
+					for (int k = 0; k < 4; ++k) x[k] = sat16((int)(gn * (float)x[k]));
+				}
+#pragma unroll
+				for (int k = 0; k < 4; ++k) sum[k] += x[k];
+				o = make_uint2(pack16(x[0], x[1]), pack16(x[2], x[3]));
+			}
+			rows[m * a.row_w + j] = o;
+		}
+#pragma unroll
+		for (int k = 0; k < 4; ++k) atomicAdd(&s_sum[4 * j + k], sum[k]);
+	}
+	__syncthreads();
+
+	// ---- (D)
+	for (int item = t; item < mm * ng; item += BT) {
+		const int m = item / ng, g = item - m * ng;
+		if (!((unsigned)s_par[m].x & MI_MIX_OUTPUT)) continue;
+		const uint2 own0 = rows[m * a.row_w + 2 * g], own1 = rows[m * a.row_w + 2 * g + 1];
+		const int4 sa = *reinterpret_cast<const int4 *>(s_sum + 8 * g), sb = *reinterpret_cast<const int4 *>(s_sum + 8 * g + 4);
+		const int o[8] = {sat16(sa.x - lo16(own0.x)), sat16(sa.y - hi16(own0.x)), sat16(sa.z - lo16(own0.y)), sat16(sa.w - hi16(own0.y)),
+		                  sat16(sb.x - lo16(own1.x)), sat16(sb.y - hi16(own1.x)), sat16(sb.z - lo16(own1.y)), sat16(sb.w - hi16(own1.y))};
+		if (RATED && s_rt[m] != 1) { // the out_resampler's input
+			rows[m * a.row_w + 2 * g] = make_uint2(pack16(o[0], o[1]), pack16(o[2], o[3]));
+			rows[m * a.row_w + 2 * g + 1] = make_uint2(pack16(o[4], o[5]), pack16(o[6], o[7]));
+			continue;
+		}
+		store_group_leg(out + (size_t)(s0 + m) * la.out_pitch, s_cd[m] >> 2, g, o);
+	}
+	if (!RATED) return;
+	__syncthreads();
+
+	// ---- (W)
+	for (int m = wave; m < mm; m += BT / 64) {
+		const int num = s_rt[m];
+		if (num == 1 || !((unsigned)s_par[m].x & MI_MIX_OUTPUT)) continue;
+		rated_down<-1>(scr, reinterpret_cast<const int16_t *>(rows + m * a.row_w), ra.hist_out + (size_t)(s0 + m) * ra.hout_stride,
+		               ra.tab + ra.tab_down[num], out, (size_t)(s0 + m) * la.out_pitch, num, ns, lane, __builtin_amdgcn_readfirstlane(s_cd[m] >> 2));
+	}
+}
+
 } // namespace
 
 struct mi_bridge {
@@ -607,6 +860,9 @@ struct mi_bridge {
 	float *d_tab = nullptr;
 	int tab_up[7] = {}, tab_down[7] = {};
 	int hout_stride = 0, scratch_off = 0, scratch_per_wave = 0;
+	// every leg's own codec (mi_bridge_create_legs) where the legs differ: in_bytes / out_bytes are the byte rows' pitch
+	std::vector<uint8_t> leg_codec; // [n] in_codec | out_codec << 2; empty: cfg's pair on every leg
+	uint8_t *d_codec = nullptr;
 };
 
 namespace {
@@ -638,14 +894,25 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 	a.mm = b->mm, a.ns = b->len, a.row_w = b->row_w, a.nslice = b->nslice, a.sum_off = b->sum_off;
 	a.sample_rate = cf.rate;
 	const dim3 grid((unsigned)b->nconf);
+	RatedArgs ra = {};
 	if (b->rated) {
-		RatedArgs ra;
 		ra.b = a;
 		ra.ratio = b->d_ratio, ra.hist_in = b->d_hist_in, ra.hist_out = b->d_hist_out, ra.tab = b->d_tab;
 		memcpy(ra.tab_up, b->tab_up, sizeof(ra.tab_up));
 		memcpy(ra.tab_down, b->tab_down, sizeof(ra.tab_down));
 		ra.pitch = b->pitch, ra.hout_stride = b->hout_stride;
 		ra.scratch_off = b->scratch_off, ra.scratch_per_wave = b->scratch_per_wave;
+	}
+	if (b->d_codec) {
+		LegsArgs la;
+		la.r = ra, la.r.b = a;
+		la.codec = b->d_codec, la.in_pitch = (int)b->in_bytes, la.out_pitch = (int)b->out_bytes;
+		if (b->rated) hipLaunchKernelGGL((bridge_legs_kernel<true>), grid, dim3(BT), b->lds, b->ctx->stream, la);
+		else hipLaunchKernelGGL((bridge_legs_kernel<false>), grid, dim3(BT), b->lds, b->ctx->stream, la);
+		MI_LAUNCH_CHECK();
+		return MI_OK;
+	}
+	if (b->rated) {
 		if (in_kind == MI_SESSION_PCM16) launch_rated_out<0>(cf.out_codec, grid, b->lds, b->ctx->stream, ra);
 		else if (in_kind == MI_SESSION_PCMA) launch_rated_out<1>(cf.out_codec, grid, b->lds, b->ctx->stream, ra);
 		else launch_rated_out<2>(cf.out_codec, grid, b->lds, b->ctx->stream, ra);
@@ -725,7 +992,7 @@ void mi_bridge_destroy(mi_bridge *b) {
 		for (uint8_t *p : {b->d_in[i], b->d_present[i], b->d_ev[i], b->d_out[i]})
 			if (p) mi_dev_free(c, p);
 	}
-	for (void *p : {(void *)b->d_ratio, (void *)b->d_hist_in, (void *)b->d_hist_out, (void *)b->d_tab})
+	for (void *p : {(void *)b->d_ratio, (void *)b->d_hist_in, (void *)b->d_hist_out, (void *)b->d_tab, (void *)b->d_codec})
 		if (p) mi_dev_free(c, p);
 	if (b->d_pcm) mi_dev_free(c, b->d_pcm);
 	if (b->d_evlen) mi_dev_free(c, b->d_evlen);
@@ -738,7 +1005,8 @@ void mi_bridge_destroy(mi_bridge *b) {
 
 int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) { return mi_bridge_create_rated(ctx, cfg, nullptr, out); }
 
-int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, mi_bridge **out) {
+// h_codec [nstreams]: in_codec | out_codec << 2 of legs that differ (mi_bridge_create_legs, which has checked them), or null
+static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, const uint8_t *h_codec, mi_bridge **out) {
 	MI_CHECK_ARG(ctx && cfg && out);
 	*out = nullptr;
 	MI_CHECK_ARG(cfg->nstreams > 0 && cfg->members_per_conference > 0 && cfg->members_per_conference <= MI_MIXER_MAX_CHANNELS &&
@@ -813,6 +1081,16 @@ int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32
 		return MI_ENOTSUP;
 	}
 	const int pitch = rated ? widest / 100 : len;
+	size_t in_bytes = (size_t)pitch * (cfg->in_codec ? 1 : 2), out_bytes = (size_t)pitch * (cfg->out_codec ? 1 : 2);
+	if (h_codec) { // byte rows: the widest leg's tick in bytes, rounded up to the 16 bytes a lane loads
+		in_bytes = out_bytes = 0;
+		for (int s = 0; s < cfg->nstreams; ++s) {
+			const size_t ll = (size_t)(h_leg_rate ? h_leg_rate[s] : cfg->rate) / 100;
+			in_bytes = std::max(in_bytes, ll * ((h_codec[s] & 3) ? 1 : 2));
+			out_bytes = std::max(out_bytes, ll * ((h_codec[s] >> 2) ? 1 : 2));
+		}
+		in_bytes = mi::round_up(in_bytes, 16), out_bytes = mi::round_up(out_bytes, 16);
+	}
 	if (ctx->activate() != MI_OK) return MI_ENODEV;
 	mi_bridge *b = new mi_bridge();
 	b->ctx = b->pipe.ctx = ctx;
@@ -826,8 +1104,7 @@ int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32
 	b->lds = lds;
 	b->nslice = std::max(1, std::min(mm, BT / (len >> 2)));
 	b->rated = rated, b->pitch = pitch;
-	b->in_bytes = (size_t)pitch * (cfg->in_codec ? 1 : 2);
-	b->out_bytes = (size_t)pitch * (cfg->out_codec ? 1 : 2);
+	b->in_bytes = in_bytes, b->out_bytes = out_bytes;
 	if (h_leg_rate) b->leg_rate.assign(h_leg_rate, h_leg_rate + cfg->nstreams);
 	b->roster.init(b->n, mm);
 	int rc = MI_OK;
@@ -864,6 +1141,11 @@ int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32
 		if ((rc = reset_resamplers(b, 0, b->n)) != MI_OK) return fail(rc);
 		if ((rc = build_tables(b, used)) != MI_OK) return fail(rc);
 	}
+	if (h_codec) {
+		b->leg_codec.assign(h_codec, h_codec + n);
+		if (!(b->d_codec = (uint8_t *)mi_dev_alloc(ctx, n))) return fail(MI_ENOMEM);
+		if (hipMemcpy(b->d_codec, h_codec, n, hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
+	}
 	if (cfg->plc) { // at the legs' one rate, on rows of the host buffers' pitch
 		if ((rc = mi_plc_create(ctx, b->n, rated ? common : cfg->rate, pitch, &b->plc)) != MI_OK) return fail(rc);
 		std::vector<int32_t> lens(n, pitch);
@@ -878,6 +1160,59 @@ int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32
 	}
 	if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(MI_ENODEV);
 	*out = b;
+	return MI_OK;
+}
+
+int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, mi_bridge **out) {
+	return create_bridge(ctx, cfg, h_leg_rate, nullptr, out);
+}
+
+int mi_bridge_create_legs(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
+	if (!h_legs) return mi_bridge_create(ctx, cfg, out);
+	MI_CHECK_ARG(ctx && cfg && out);
+	*out = nullptr;
+	MI_CHECK_ARG(cfg->nstreams > 0);
+	const size_t n = (size_t)cfg->nstreams;
+	std::vector<int32_t> rate(n);
+	std::vector<uint8_t> codec(n);
+	int differs = -1; // the first leg whose pair is not leg 0's
+	for (size_t s = 0; s < n; ++s) {
+		const mi_bridge_leg &l = h_legs[s];
+		for (int v : {l.in_codec, l.out_codec})
+			if (v < MI_SESSION_PCM16 || v > MI_SESSION_PCMU) {
+				mi::set_error("mi_bridge_create_legs: leg %zu names codec %d; supported: MI_SESSION_PCM16 (0), MI_SESSION_PCMA (1), "
+				              "MI_SESSION_PCMU (2)", s, v);
+				return MI_ENOTSUP;
+			}
+		rate[s] = l.rate;
+		codec[s] = (uint8_t)(l.in_codec | l.out_codec << 2);
+		if (differs < 0 && codec[s] != codec[0]) differs = (int)s;
+	}
+	if (differs >= 0 && cfg->plc) {
+		mi::set_error("mi_bridge_create_legs: plc with leg %d's codecs (in %d, out %d) unlike leg 0's (in %d, out %d): the concealer batch "
+		              "sits behind one decoder", differs, h_legs[differs].in_codec, h_legs[differs].out_codec, h_legs[0].in_codec,
+		              h_legs[0].out_codec);
+		return MI_ENOTSUP;
+	}
+	mi_bridge_config c = *cfg; // a uniform bridge is mi_bridge_create_rated's, its one pair compile-time in the kernels
+	c.in_codec = h_legs[0].in_codec, c.out_codec = h_legs[0].out_codec;
+	return create_bridge(ctx, &c, rate.data(), differs >= 0 ? codec.data() : nullptr, out);
+}
+
+int mi_bridge_leg_codec(const mi_bridge *b, int stream, int *in_codec, int *out_codec) {
+	if (!b || stream < 0 || stream >= b->n) return MI_EINVAL;
+	const int pair = b->leg_codec.empty() ? b->cfg.in_codec | b->cfg.out_codec << 2 : b->leg_codec[(size_t)stream];
+	if (in_codec) *in_codec = pair & 3;
+	if (out_codec) *out_codec = pair >> 2;
+	return MI_OK;
+}
+
+int mi_bridge_leg_bytes(const mi_bridge *b, int stream, int *in_bytes, int *out_bytes) {
+	int in_codec, out_codec;
+	if (mi_bridge_leg_codec(b, stream, &in_codec, &out_codec) != MI_OK) return MI_EINVAL;
+	const int len = mi_bridge_leg_rate(b, stream) / 100;
+	if (in_bytes) *in_bytes = len * (in_codec ? 1 : 2);
+	if (out_bytes) *out_bytes = len * (out_codec ? 1 : 2);
 	return MI_OK;
 }
 
