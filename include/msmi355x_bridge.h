@@ -31,9 +31,19 @@
  * first mi_bridge_leg_bytes of its row.  A bridge whose legs all name one pair is the one mi_bridge_create_rated builds:
  * the same kernels, pitch and tick bytes.
  *
+ * Endpoints on either side of the mix (mi_bridge_create_endpoints): plumb_to_conf configures the two resamplers from the
+ * endpoint's rate and the conference's whichever is larger (msconference.h:91-93), so a member ABOVE the mix -- a 48 kHz
+ * PCM member, whose Opus decoder always hands out 48 kHz (msopus.c:88), in a 16 kHz room of G.711 trunks -- gets the
+ * down-sampler in front of its pin and the up-sampler behind it.  Leg rate / conference rate may be 2, 3 or 6 as well;
+ * legs below, at and above the mix share one conference and one launch per tick (bridge_updown_kernel, run only by a
+ * bridge with a leg above its mix), bit for bit the parts called one by one (tests/test_gpu_bridge_endpoints.py).  The
+ * rules are the rated bridge's: MSVolume in front of the in_resampler on the leg's rate / 100 samples at the leg's rate,
+ * no block for the in_resampler of an absent leg nor for the out_resampler of a pin without MI_MIX_OUTPUT.  Byte rows at
+ * one pitch as with mi_bridge_create_legs; the pitch, the widest leg's tick, may now exceed the conference's own.
+ *
  * Out of scope, on purpose:
- *   - legs ABOVE their conference's rate, ratios that are no whole number (44.1 kHz; 32 kHz in 48 kHz) and whole ratios
- *     other than 2, 3 and 6: refused with MI_ENOTSUP -- mi_session and the MSFilter plugin resample those;
+ *   - ratios that are no whole number (44.1 kHz; 32 kHz in 48 kHz) and whole ratios other than 2, 3 and 6, in either
+ *     direction: refused with MI_ENOTSUP -- mi_session and the MSFilter plugin resample those;
  *   - jitter buffering and flow control: the host's, as with mi_session -- a leg whose packet is missing at the tick is
  *     flagged absent (or concealed, cfg.plc);
  *   - cfg.plc on a bridge whose legs differ in codec: refused with MI_ENOTSUP -- the concealer batch sits behind ONE
@@ -83,6 +93,16 @@ typedef struct mi_bridge_leg {
 	int32_t out_codec;
 } mi_bridge_leg;
 int mi_bridge_create_legs(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */, mi_bridge **out);
+/* Every endpoint at the rate audioconference.c would plumb it with: below, at or ABOVE cfg->rate.  The arguments are
+ * mi_bridge_create_legs'; h_legs == NULL is mi_bridge_create, and with no leg above cfg->rate the bridge is the one
+ * mi_bridge_create_legs builds: the same kernels, pitch and tick bytes.  Supported: leg rate / cfg->rate or cfg->rate / leg
+ * rate in {1, 2, 3, 6}, leg rate % 800 == 0; a G.711 leg above the mix is legal (code words are samples at the leg's rate).
+ * With a leg above the mix the host rows are byte rows whether the codecs differ or not.  MI_ENOTSUP, the message naming
+ * the leg and the value, before anything is allocated: a ratio that is no whole number in either direction, or another
+ * one; a rate that is no multiple of 800; a codec outside the three; cfg->plc unless every leg shares one rate and one
+ * codec pair; a conference whose rows -- as wide as the widest leg of the bridge --, sum row and resampler scratch do not
+ * fit the 64 KB of LDS the kernel allows itself (48 kHz members in a 16 kHz conference: up to 45; in an 8 kHz one: 42). */
+int mi_bridge_create_endpoints(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */, mi_bridge **out);
 void mi_bridge_destroy(mi_bridge *b);
 int mi_bridge_leg_rate(const mi_bridge *b, int stream); /* the leg's rate in Hz, or MI_EINVAL */
 /* the leg's codecs and its own tick in bytes (rate / 100 x 1 or 2), on any bridge; either pointer may be NULL.
@@ -119,8 +139,8 @@ int mi_bridge_set_controls(mi_bridge *b, const uint8_t *h_flags, const float *h_
  * mi_volume_default_params (a meter at unity gain).  An echo-limiter peer (params.peer != -1) is MI_ENOTSUP: a bridge
  * has no far end to limit against. */
 int mi_bridge_set_volume_params(mi_bridge *b, int first, int count, const mi_volume_params *h_params);
-/* a leg was replaced: the meter (and concealer, and both resamplers' histories) of streams [first, first + count) start
- * over as new filters would */
+/* a leg was replaced: the meter (and concealer, and both resamplers' histories -- ratio x 48 - 1 samples on the wider side
+ * of the pin, 47 on the other) of streams [first, first + count) start over as new filters would */
 int mi_bridge_reset_streams(mi_bridge *b, int first, int count);
 /* MSAudioConference membership (audioconference.c:322-374), as mi_session_add_member / _remove_member: a bridge is
  * created full; remove unplumbs the pin and clears its output row, add plumbs it for a NEW endpoint (fresh meter) */

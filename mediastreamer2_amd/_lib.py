@@ -64,6 +64,7 @@ BRIDGE_EXPORTS = [
     "mi_bridge_get_levels", "mi_bridge_active_speakers", "mi_bridge_get_volume_state", "mi_bridge_get_volume_max",
     "mi_bridge_create_rated", "mi_bridge_leg_rate",
     "mi_bridge_create_legs", "mi_bridge_leg_codec", "mi_bridge_leg_bytes",
+    "mi_bridge_create_endpoints",
 ]
 
 
@@ -272,6 +273,7 @@ def load():
     L.mi_bridge_create_rated.argtypes = [vp, vp, C.POINTER(C.c_int32), pp]
     L.mi_bridge_leg_rate.argtypes = [vp, i32]
     L.mi_bridge_create_legs.argtypes = [vp, vp, vp, pp]
+    L.mi_bridge_create_endpoints.argtypes = [vp, vp, vp, pp]
     L.mi_bridge_leg_codec.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.mi_bridge_leg_bytes.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.mi_bridge_set_volume_params.argtypes = [vp, i32, i32, C.POINTER(VolumeParams)]

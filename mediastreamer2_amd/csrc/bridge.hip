@@ -22,8 +22,8 @@
 //   (D) lane = (member, eight columns), for every pin with its output enabled: saturate(sum - own)
 //       (channel_process_out), stored as 16 bytes of PCM or encoded to 8 code words; consecutive lanes, consecutive bytes.
 // The members are sliced in (C) so that an 80-sample tick, 20 four-column words wide, still occupies 240 lanes.
-// bridge_rated_kernel (legs at their own rate) and bridge_legs_kernel (every leg's own codec, with or without the
-// resamplers) further down keep these phases; each says at its head what it adds.
+// bridge_rated_kernel (legs at their own rate), bridge_legs_kernel (every leg's own codec, with or without the resamplers)
+// and bridge_updown_kernel (legs above the mix as well) further down keep these phases; each says at its head what it adds.
 //
 // Geometry: an 8 kHz conference of 32 is 5.4 KB of LDS and four waves, so eight such workgroups share a CU (32 waves);
 // 1000 conferences are 1000 workgroups dealt over the 256 CUs, about four per CU = one wave per SIMD and conference
@@ -833,6 +833,302 @@ __global__ __launch_bounds__(BT) void bridge_legs_kernel(LegsArgs la) {
 	}
 }
 
+// ---- endpoints on either side of the mix (mi_bridge_create_endpoints): plumb_to_conf configures both resamplers from the
+// endpoint's rate and the conference's whichever is larger, so a leg ABOVE the mix -- a 48 kHz PCM member of a 16 kHz room --
+// has the down-sampler in front of its pin and the up-sampler behind it.  The ratio byte of such a member carries UD_ABOVE.
+// Only a bridge with at least one such leg runs this kernel; its rows in LDS are as wide as the widest leg's tick.
+constexpr unsigned UD_ABOVE = 0x80;
+
+struct UpdownArgs {
+	LegsArgs l;         // l.r.b.ns, sum_off, sample_rate: the conference's; l.r.b.row_w: of a row of `wide` samples
+	int wide;           // samples per LDS row: the widest leg's tick (>= ns)
+	int hin_stride;     // samples per member of l.r.hist_in (l.r.hout_stride: of hist_out); either holds 47 or ratio * 48 - 1
+	int tab_down_in[7]; // a leg above by ratio k: its in_resampler's table (leg -> conference), phase-major [k][48]
+	int tab_up_out[7];  // and its out_resampler's (conference -> leg), polyphase rows [k][48]
+};
+
+// floats per phase array of the down-sampler in FRONT of a pin: rated_plen with plen / 4 odd.  Lane l of the tile FIR reads
+// 16 bytes at phase (l % num) * plen + 8 * (l / num): the tiles fall on the even 16-byte slots of the 256-byte bank row,
+// an odd plen / 4 puts the neighbouring phase on the odd ones (an even one -- 144, 224 -- stacks the phases on one slot).
+__host__ __device__ inline int updown_plen(int num, int in_len) { return rated_plen(num, in_len) | 4; }
+
+// rated_down with the row as its sink: one wavefront runs the in_resampler of one member above the mix --
+// resample_down_kernel's arithmetic in its order, history ++ the row's num * out_len leg-rate samples split by input phase,
+// each phase's share of eight outputs through fir_tile, the shares added phase upward, rs_word2int -- and writes the
+// out_len conference-rate samples over the head of the row.  xp: [num][plen] ++ [in_len] floats.
+__device__ __forceinline__ void updown_down(float *xp, int16_t *row, int16_t *hist, const float *tab, int num, int in_len, int lane) {
+	const int HIST = num * RS_FILT - 1, hq = (num * RS_FILT) >> 2, nq = hq + (in_len >> 2);
+	const int out_len = in_len / num, plen = updown_plen(num, in_len);
+	float *part = xp + num * plen; // [out_len][num] partial sums
+	for (int i = lane; i < num * plen; i += 64) xp[i] = 0.f;
+	wave_sync();
+	for (int q = lane; q < nq; q += 64) { // (a 287-sample history is more than one pass of the 64 lanes)
+		const bool h = q < hq;
+		const short4 v = h ? *reinterpret_cast<const short4 *>(hist + 4 * q) : *reinterpret_cast<const short4 *>(row + 4 * (q - hq));
+		const int b = h ? 4 * q : HIST + 4 * (q - hq); // index in history ++ row
+		const short e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+		for (int k = 0; k < 4; ++k) {
+			const int i = b + k;
+			if (!h || i < HIST) xp[(i % num) * plen + i / num] = (float)e[k];
+		}
+	}
+	wave_sync(); // the whole tick is staged before the first output lands on the row
+	const int nlanes = num * (out_len >> 3);
+	for (int base = 0; base < nlanes; base += 64) {
+		const int l = base + lane;
+		const bool on = l < nlanes;
+		const int tile = on ? l / num : 0, p = on ? l - tile * num : 0;
+		f2 t2[RS_FILT / 2], acc2[RS_R / 2];
+		load_taps(tab + p * RS_FILT, t2);
+#pragma unroll
+		for (int q = 0; q < RS_R / 2; ++q) acc2[q] = (f2){0.f, 0.f};
+		fir_tile<RS_FILT, RS_R>(xp + p * plen + tile * RS_R, t2, acc2);
+		if (on) {
+			float *d = part + (tile * RS_R) * num + p;
+#pragma unroll
+			for (int q = 0; q < RS_R / 2; ++q) d[(2 * q) * num] = acc2[q].x, d[(2 * q + 1) * num] = acc2[q].y;
+		}
+	}
+	wave_sync();
+	for (int g = lane; g < (out_len >> 3); g += 64) {
+		const float *ps = part + g * 8 * num;
+		int o[8];
+#pragma unroll
+		for (int k = 0; k < 8; ++k) {
+			float sum = 0.f;
+			for (int p = 0; p < num; ++p) sum += ps[k * num + p];
+			o[k] = rs_word2int(sum);
+		}
+		uint2 *d = reinterpret_cast<uint2 *>(row + 8 * g);
+		d[0] = make_uint2(pack16(o[0], o[1]), pack16(o[2], o[3])), d[1] = make_uint2(pack16(o[4], o[5]), pack16(o[6], o[7]));
+	}
+	// new history = the last HIST samples of history ++ tick; the pad slot takes a zero
+	for (int q = lane; q < hq; q += 64) {
+		short4 h;
+		short *hp = &h.x;
+#pragma unroll
+		for (int k = 0; k < 4; ++k) {
+			const int i = in_len + 4 * q + k;
+			hp[k] = (4 * q + k < HIST) ? (short)xp[(i % num) * plen + i / num] : (short)0;
+		}
+		*reinterpret_cast<short4 *>(hist + 4 * q) = h;
+	}
+	wave_sync(); // xp is read out before the wave's next member stages over it
+}
+
+// what rated_up left on the row of a member above the mix -- its out_resampler's `len` leg-rate samples -- through the
+// leg's store or encoder, 16 bytes of PCM or 8 code words per lane
+__device__ __forceinline__ void updown_store(const int16_t *row, uint8_t *out, int kind, int len, int lane) {
+	for (int g = lane; g < (len >> 3); g += 64) {
+		const uint2 *r = reinterpret_cast<const uint2 *>(row + 8 * g);
+		const uint2 w0 = r[0], w1 = r[1];
+		const int o[8] = {lo16(w0.x), hi16(w0.x), lo16(w0.y), hi16(w0.y), lo16(w1.x), hi16(w1.x), lo16(w1.y), hi16(w1.y)};
+		store_group_leg(out, kind, g, o);
+	}
+}
+
+// The phases of bridge_legs_kernel<true>, their arithmetic word for word, with the direction of a member's resamplers as
+// data next to its ratio and its codec pair:
+//   (0) (A) (B) (G) on the leg's own samples, ratio * ns of them for a leg above the mix: the row is `wide` samples;
+//   (U) one wavefront per member: rated_up for a leg below the mix, updown_down for one above it;
+//   (C) (D) at the conference's rate on the head of the rows;
+//   (W) one wavefront per member: rated_down for a leg below the mix; for one above it rated_up from the head of the row
+//       back over the row (which held the leg's input, so it is wide enough), then updown_store.
+__global__ __launch_bounds__(BT) void bridge_updown_kernel(UpdownArgs ua) {
+	extern __shared__ __attribute__((aligned(16))) char smem[];
+	const LegsArgs &la = ua.l;
+	const RatedArgs &ra = la.r;
+	const BridgeArgs &a = ra.b;
+	uint2 *rows = reinterpret_cast<uint2 *>(smem);
+	int *s_sum = reinterpret_cast<int *>(smem + a.sum_off);
+	__shared__ int s_pk[BMAX], s_dc[BMAX];
+	__shared__ int4 s_par[BMAX];
+	__shared__ unsigned char s_rt[BMAX], s_on[BMAX], s_cd[BMAX]; // a member's ratio | UD_ABOVE; whether it is here this tick; its codec pair
+	const int t = threadIdx.x, c = blockIdx.x, mm = a.mm, ns = a.ns, nw = ns >> 2, ng = ns >> 3;
+	const int s0 = c * mm;
+	const uint8_t *in = static_cast<const uint8_t *>(a.in);
+	uint8_t *out = static_cast<uint8_t *>(a.out);
+
+	// ---- (0)
+	mi_volume_params p;
+	mi_volume_state st;
+	float2 win = make_float2(0, 0);
+	unsigned mflag = 0;
+	int mgain_bits = 0, rt = 1;
+	bool here = false;
+	if (t < mm) {
+		const int s = s0 + t;
+		p = a.params[s];
+		st = a.state[s];
+		win = a.win[s];
+		mflag = a.flags[s];
+		mgain_bits = __float_as_int(a.gain[s]);
+		here = !a.present || a.present[s] != 0;
+		s_cd[t] = la.codec[s];
+		rt = ra.ratio[s];
+		s_rt[t] = (unsigned char)rt, s_on[t] = here;
+	}
+	for (int i = t; i < ns; i += BT) s_sum[i] = 0;
+
+	// ---- (A) the leg's own groups; the rest of the row is zeros as far as the conference's tick reaches
+	for (int mb = 0; mb < mm; mb += BT / 8) {
+		const int m = mb + (t >> 3), q = t & 7;
+		const bool valid = m < mm;
+		int pk = 0, dc = 0;
+		if (valid) {
+			const bool on = !a.present || a.present[s0 + m] != 0;
+			const int kind = la.codec[s0 + m] & 3, r = ra.ratio[s0 + m];
+			const int ngl = (r & UD_ABOVE) ? ng * (r & 7) : ng / r, nz = max(ng, ngl);
+			const uint8_t *src = in + (size_t)(s0 + m) * la.in_pitch;
+			for (int g0 = q; g0 < nz; g0 += 32) {
+				uint4 v[4];
+#pragma unroll
+				for (int i = 0; i < 4; ++i) { // straight-line loads: all in flight at once
+					v[i] = make_uint4(0, 0, 0, 0);
+					if (on && g0 + 8 * i < ngl) v[i] = load_raw_leg(src, kind, g0 + 8 * i);
+				}
+#pragma unroll
+				for (int i = 0; i < 4; ++i) {
+					const int g = g0 + 8 * i;
+					if (g >= nz) continue;
+					const uint4 d = decode_group_leg(v[i], kind, g);
+					if (on && g < ngl) v[i] = d; // (code bytes of zero are not silence)
+					rows[m * a.row_w + 2 * g] = make_uint2(v[i].x, v[i].y);
+					rows[m * a.row_w + 2 * g + 1] = make_uint2(v[i].z, v[i].w);
+					const unsigned w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+#pragma unroll
+					for (int k = 0; k < 4; ++k) {
+						const int x0 = lo16(w[k]), x1 = hi16(w[k]);
+						pk = max(pk, max(x0 < 0 ? -x0 : x0, x1 < 0 ? -x1 : x1));
+						dc += x0 + x1;
+					}
+				}
+			}
+		}
+#pragma unroll
+		for (int off = 1; off < 8; off <<= 1) {
+			pk = max(pk, __shfl_xor(pk, off));
+			dc += __shfl_xor(dc, off);
+		}
+		if (valid && q == 0) s_pk[m] = pk, s_dc[m] = dc;
+	}
+	__syncthreads();
+
+	// ---- (B) over the leg's rate / 100 samples, at the leg's rate
+	if (t < mm) {
+		if (here) {
+			const uint2 *r = rows + t * a.row_w;
+			const bool above = rt & UD_ABOVE;
+			const int k = rt & 7, nwl = above ? nw * k : nw / k;
+			float acc = 0;
+#pragma unroll 4
+			for (int i = 0; i < nwl; ++i) {
+				const uint2 w = r[i];
+				const int x0 = lo16(w.x), x1 = hi16(w.x), x2 = lo16(w.y), x3 = hi16(w.y);
+				acc += (float)(x0 * x0);
+				acc += (float)(x1 * x1);
+				acc += (float)(x2 * x2);
+				acc += (float)(x3 * x3);
+			}
+			const VolCtl o = volume_control(p, st, 0.f, acc, 4 * nwl, s_pk[t], s_dc[t], above ? a.sample_rate * k : a.sample_rate / k, win);
+			s_par[t] = make_int4((int)mflag | (o.mode << 8), o.intgain, o.dcoff, mgain_bits);
+			a.state[s0 + t] = st;
+			a.win[s0 + t] = win;
+		} else {
+			s_par[t] = make_int4((int)mflag, 4096, 0, mgain_bits);
+		}
+	}
+	__syncthreads();
+
+	// ---- (G) apply_gain (msvolume.c:440) in front of the in_resampler, on the leg-rate samples
+	const int nww = ua.wide >> 2;
+	for (int item = t; item < mm * nww; item += BT) {
+		const int m = item / nww, j = item - m * nww;
+		const int4 par = s_par[m];
+		const int mode = par.x >> 8, r = s_rt[m];
+		if (mode == 0 || j >= ((r & UD_ABOVE) ? nw * (r & 7) : nw / r)) continue;
+		const uint2 cur = rows[m * a.row_w + j];
+		int x[4] = {lo16(cur.x), hi16(cur.x), lo16(cur.y), hi16(cur.y)};
+		const int ig = par.y, dc = (mode == 2) ? par.z : 0;
+#pragma unroll
+		for (int k = 0; k < 4; ++k) x[k] = sat16(((x[k] - dc) * ig) / 4096);
+		rows[m * a.row_w + j] = make_uint2(pack16(x[0], x[1]), pack16(x[2], x[3]));
+	}
+	__syncthreads();
+
+	// ---- (U) the in_resampler of a present, plumbed leg; any other keeps its history
+	const int wave = t >> 6, lane = t & 63;
+	float *scr = reinterpret_cast<float *>(smem + ra.scratch_off + wave * ra.scratch_per_wave);
+	for (int m = wave; m < mm; m += BT / 64) {
+		const int r = __builtin_amdgcn_readfirstlane(s_rt[m]), k = r & 7;
+		if (r == 1 || !s_on[m] || !((unsigned)s_par[m].x & MI_MIX_LINKED)) continue;
+		int16_t *row = reinterpret_cast<int16_t *>(rows + m * a.row_w), *hist = ra.hist_in + (size_t)(s0 + m) * ua.hin_stride;
+		if (r & UD_ABOVE) updown_down(scr, row, hist, ra.tab + ua.tab_down_in[k], k, ns * k, lane);
+		else rated_up(scr, row, hist, ra.tab + ra.tab_up[k], k, ns / k, lane);
+	}
+	__syncthreads();
+
+	// ---- (C) the gain is in the rows already
+	for (int item = t; item < a.nslice * nw; item += BT) {
+		const int r = item / nw, j = item - r * nw;
+		int sum[4] = {0, 0, 0, 0};
+		for (int m = r; m < mm; m += a.nslice) {
+			const int4 par = s_par[m];
+			const unsigned f = (unsigned)par.x & 0xffu;
+			uint2 o = make_uint2(0, 0);
+			if ((f & MI_MIX_LINKED) && (f & MI_MIX_ACTIVE)) {
+				const uint2 cur = rows[m * a.row_w + j];
+				int x[4] = {lo16(cur.x), hi16(cur.x), lo16(cur.y), hi16(cur.y)};
+				const float gn = __int_as_float(par.w);
+				if (gn != 1.0f) { // channel_process_in's input gain (audiomixer.c:46-51)
+#pragma unroll
+					for (int k = 0; k < 4; ++k) x[k] = sat16((int)(gn * (float)x[k]));
+				}
+#pragma unroll
+				for (int k = 0; k < 4; ++k) sum[k] += x[k];
+				o = make_uint2(pack16(x[0], x[1]), pack16(x[2], x[3]));
+			}
+			rows[m * a.row_w + j] = o;
+		}
+#pragma unroll
+		for (int k = 0; k < 4; ++k) atomicAdd(&s_sum[4 * j + k], sum[k]);
+	}
+	__syncthreads();
+
+	// ---- (D)
+	for (int item = t; item < mm * ng; item += BT) {
+		const int m = item / ng, g = item - m * ng;
+		if (!((unsigned)s_par[m].x & MI_MIX_OUTPUT)) continue;
+		const uint2 own0 = rows[m * a.row_w + 2 * g], own1 = rows[m * a.row_w + 2 * g + 1];
+		const int4 sa = *reinterpret_cast<const int4 *>(s_sum + 8 * g), sb = *reinterpret_cast<const int4 *>(s_sum + 8 * g + 4);
+		const int o[8] = {sat16(sa.x - lo16(own0.x)), sat16(sa.y - hi16(own0.x)), sat16(sa.z - lo16(own0.y)), sat16(sa.w - hi16(own0.y)),
+		                  sat16(sb.x - lo16(own1.x)), sat16(sb.y - hi16(own1.x)), sat16(sb.z - lo16(own1.y)), sat16(sb.w - hi16(own1.y))};
+		if (s_rt[m] != 1) { // the out_resampler's input, either direction
+			rows[m * a.row_w + 2 * g] = make_uint2(pack16(o[0], o[1]), pack16(o[2], o[3]));
+			rows[m * a.row_w + 2 * g + 1] = make_uint2(pack16(o[4], o[5]), pack16(o[6], o[7]));
+			continue;
+		}
+		store_group_leg(out + (size_t)(s0 + m) * la.out_pitch, s_cd[m] >> 2, g, o);
+	}
+	__syncthreads();
+
+	// ---- (W) the out_resampler of a pin with its output on, then the leg's store / encoder
+	for (int m = wave; m < mm; m += BT / 64) {
+		const int r = __builtin_amdgcn_readfirstlane(s_rt[m]), k = r & 7;
+		if (r == 1 || !((unsigned)s_par[m].x & MI_MIX_OUTPUT)) continue;
+		int16_t *row = reinterpret_cast<int16_t *>(rows + m * a.row_w), *hist = ra.hist_out + (size_t)(s0 + m) * ra.hout_stride;
+		const int kind = __builtin_amdgcn_readfirstlane(s_cd[m] >> 2);
+		const size_t at = (size_t)(s0 + m) * la.out_pitch;
+		if (r & UD_ABOVE) {
+			rated_up(scr, row, hist, ra.tab + ua.tab_up_out[k], k, ns, lane);
+			updown_store(row, out + at, kind, ns * k, lane);
+		} else {
+			rated_down<-1>(scr, row, hist, ra.tab + ra.tab_down[k], out, at, k, ns, lane, kind);
+		}
+	}
+}
+
 } // namespace
 
 struct mi_bridge {
@@ -863,6 +1159,12 @@ struct mi_bridge {
 	// every leg's own codec (mi_bridge_create_legs) where the legs differ: in_bytes / out_bytes are the byte rows' pitch
 	std::vector<uint8_t> leg_codec; // [n] in_codec | out_codec << 2; empty: cfg's pair on every leg
 	uint8_t *d_codec = nullptr;
+	// endpoints on either side of the mix (mi_bridge_create_endpoints) with a leg ABOVE it: bridge_updown_kernel.  d_ratio then
+	// carries UD_ABOVE, d_codec is there whether the legs differ or not ([2][n] with plc: the second row names PCM in)
+	bool updown = false;
+	int wide = 0;                  // samples per LDS row: the widest leg's tick
+	int hin_stride = RS_FILT;      // samples per member of d_hist_in
+	int tab_down_in[7] = {}, tab_up_out[7] = {};
 };
 
 namespace {
@@ -875,7 +1177,7 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 	if (b->plc) { // MSAlawDec / MSUlawDec as a launch of its own, then MSGenericPLC on the PCM rows, in place
 		int16_t *rows = reinterpret_cast<int16_t *>(b->d_in[slot]);
 		if (cf.in_codec) {
-			if ((rc = mi_g711_decode(b->ctx, cf.in_codec == MI_SESSION_PCMA ? MI_LAW_PCMA : MI_LAW_PCMU, b->d_in[slot], (size_t)b->pitch, b->d_pcm,
+			if ((rc = mi_g711_decode(b->ctx, cf.in_codec == MI_SESSION_PCMA ? MI_LAW_PCMA : MI_LAW_PCMU, b->d_in[slot], b->in_bytes, b->d_pcm,
 			                         (size_t)b->pitch, nullptr, b->pitch, (size_t)b->n)) != MI_OK)
 				return rc;
 			rows = b->d_pcm;
@@ -902,6 +1204,19 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 		memcpy(ra.tab_down, b->tab_down, sizeof(ra.tab_down));
 		ra.pitch = b->pitch, ra.hout_stride = b->hout_stride;
 		ra.scratch_off = b->scratch_off, ra.scratch_per_wave = b->scratch_per_wave;
+	}
+	if (b->updown) {
+		UpdownArgs ua;
+		ua.l.r = ra;
+		// behind the concealer every leg's input is the PCM it worked on, at the pitch of its rows
+		ua.l.codec = b->plc ? b->d_codec + b->n : b->d_codec;
+		ua.l.in_pitch = b->plc ? b->pitch * 2 : (int)b->in_bytes, ua.l.out_pitch = (int)b->out_bytes;
+		ua.wide = b->wide, ua.hin_stride = b->hin_stride;
+		memcpy(ua.tab_down_in, b->tab_down_in, sizeof(ua.tab_down_in));
+		memcpy(ua.tab_up_out, b->tab_up_out, sizeof(ua.tab_up_out));
+		hipLaunchKernelGGL(bridge_updown_kernel, grid, dim3(BT), b->lds, b->ctx->stream, ua);
+		MI_LAUNCH_CHECK();
+		return MI_OK;
 	}
 	if (b->d_codec) {
 		LegsArgs la;
@@ -931,7 +1246,7 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 int reset_resamplers(mi_bridge *b, int first, int count) {
 	if (!b->rated || count == 0) return MI_OK;
 	if (b->ctx->activate() != MI_OK) return MI_ENODEV;
-	MI_HIP(hipMemsetAsync(b->d_hist_in + (size_t)first * RS_FILT, 0, (size_t)count * RS_FILT * sizeof(int16_t), b->ctx->stream));
+	MI_HIP(hipMemsetAsync(b->d_hist_in + (size_t)first * b->hin_stride, 0, (size_t)count * b->hin_stride * sizeof(int16_t), b->ctx->stream));
 	MI_HIP(hipMemsetAsync(b->d_hist_out + (size_t)first * b->hout_stride, 0, (size_t)count * b->hout_stride * sizeof(int16_t), b->ctx->stream));
 	return MI_OK;
 }
@@ -948,11 +1263,23 @@ int design_table(mi_ctx *ctx, int in_rate, int out_rate, std::vector<float> &tab
 }
 
 // one table per distinct ratio and direction, built once: ratio r up [r][48] as designed, down [r][48] phase-major
-int build_tables(mi_bridge *b, const bool (&used)[7]) {
+// (`above`: the ratios of legs above the mix, whose down-sampler is the in_resampler and runs from rate * r)
+int build_tables(mi_bridge *b, const bool (&used)[7], const bool (&above)[7]) {
 	std::vector<float> all, t;
 	for (int r = 2; r < 7; ++r) {
-		if (!used[r]) continue;
 		int rc;
+		if (above[r]) {
+			if ((rc = design_table(b->ctx, b->cfg.rate * r, b->cfg.rate, t)) != MI_OK) return rc;
+			if (t.size() != (size_t)r * RS_FILT) return MI_ENOTSUP;
+			b->tab_down_in[r] = (int)all.size();
+			for (int p = 0; p < r; ++p)
+				for (int i = 0; i < RS_FILT; ++i) all.push_back(t[(size_t)i * r + p]);
+			if ((rc = design_table(b->ctx, b->cfg.rate, b->cfg.rate * r, t)) != MI_OK) return rc;
+			if (t.size() != (size_t)r * RS_FILT) return MI_ENOTSUP;
+			b->tab_up_out[r] = (int)all.size();
+			all.insert(all.end(), t.begin(), t.end());
+		}
+		if (!used[r]) continue;
 		if ((rc = design_table(b->ctx, b->cfg.rate / r, b->cfg.rate, t)) != MI_OK) return rc;
 		if (t.size() != (size_t)r * RS_FILT) return MI_ENOTSUP;
 		b->tab_up[r] = (int)all.size();
@@ -1005,8 +1332,11 @@ void mi_bridge_destroy(mi_bridge *b) {
 
 int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) { return mi_bridge_create_rated(ctx, cfg, nullptr, out); }
 
-// h_codec [nstreams]: in_codec | out_codec << 2 of legs that differ (mi_bridge_create_legs, which has checked them), or null
-static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, const uint8_t *h_codec, mi_bridge **out) {
+// h_codec [nstreams]: in_codec | out_codec << 2 of legs that differ (mi_bridge_create_legs, which has checked them), or null.
+// endpoints: mi_bridge_create_endpoints' rules -- a leg may be above cfg->rate, and h_codec is there whenever one is
+static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, const uint8_t *h_codec, mi_bridge **out,
+                         bool endpoints = false) {
+	const char *fn = endpoints ? "mi_bridge_create_endpoints" : "mi_bridge_create_rated";
 	MI_CHECK_ARG(ctx && cfg && out);
 	*out = nullptr;
 	MI_CHECK_ARG(cfg->nstreams > 0 && cfg->members_per_conference > 0 && cfg->members_per_conference <= MI_MIXER_MAX_CHANNELS &&
@@ -1019,60 +1349,72 @@ static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t
 		return MI_ENOTSUP;
 	}
 	const int len = cfg->rate / 100, mm = cfg->members_per_conference;
-	const int row_w = (len >> 2) | 1; // 8-byte words per row, odd
 	// ---- the legs' rates: every refusal before anything is allocated
-	bool used[7] = {};
+	bool used[7] = {}, above[7] = {}; // the ratios of legs below the mix, and of legs above it
 	int widest = 0, common = 0, max_ratio = 1;
-	bool rated = false;
+	bool rated = false, updown = false;
 	if (h_leg_rate) {
 		for (int s = 0; s < cfg->nstreams; ++s) {
 			const int lr = h_leg_rate[s];
 			MI_CHECK_ARG(lr > 0);
-			if (lr > cfg->rate) {
+			const bool up = lr > cfg->rate;
+			if (up && !endpoints) {
 				mi::set_error("mi_bridge_create_rated: leg %d at %d Hz is above its conference's %d Hz (only legs at or below the mix are resampled)",
 				              s, lr, cfg->rate);
 				return MI_ENOTSUP;
 			}
-			if (cfg->rate % lr != 0) {
-				mi::set_error("mi_bridge_create_rated: leg %d at %d Hz in a %d Hz conference is no whole ratio (%.3f); supported: 1, 2, 3, 6", s, lr,
-				              cfg->rate, (double)cfg->rate / lr);
+			const int hi = up ? lr : cfg->rate, lo = up ? cfg->rate : lr;
+			if (hi % lo != 0) {
+				mi::set_error("%s: leg %d at %d Hz in a %d Hz conference is no whole ratio (%.3f); supported: 1, 2, 3, 6", fn, s, lr, cfg->rate,
+				              (double)hi / lo);
 				return MI_ENOTSUP;
 			}
-			const int r = cfg->rate / lr;
+			const int r = hi / lo;
 			if (r != 1 && r != 2 && r != 3 && r != 6) {
-				mi::set_error("mi_bridge_create_rated: leg %d at %d Hz in a %d Hz conference is ratio %d; supported: 1, 2, 3, 6", s, lr, cfg->rate, r);
+				mi::set_error("%s: leg %d at %d Hz in a %d Hz conference is ratio %d; supported: 1, 2, 3, 6", fn, s, lr, cfg->rate, r);
 				return MI_ENOTSUP;
 			}
 			if (lr % 800 != 0) {
-				mi::set_error("mi_bridge_create_rated: leg %d's rate %d is no multiple of 800 (a 10 ms tick must be whole groups of 8 samples)", s, lr);
+				mi::set_error("%s: leg %d's rate %d is no multiple of 800 (a 10 ms tick must be whole groups of 8 samples)", fn, s, lr);
 				return MI_ENOTSUP;
 			}
 			if (cfg->plc && common && lr != common) {
-				mi::set_error("mi_bridge_create_rated: plc with legs at %d Hz and %d Hz: the concealer batch has one rate", common, lr);
+				mi::set_error("%s: plc with legs at %d Hz and %d Hz: the concealer batch has one rate", fn, common, lr);
 				return MI_ENOTSUP;
 			}
 			if (!common) common = lr;
-			used[r] = true;
+			(up ? above : used)[r] = true;
+			updown |= up;
 			widest = std::max(widest, lr);
 			max_ratio = std::max(max_ratio, r);
 		}
 		rated = max_ratio > 1;
 	}
+	const int wide = updown ? widest / 100 : len;  // samples per row in LDS: the widest leg's tick where one is above the mix
+	const int row_w = (wide >> 2) | 1;             // 8-byte words per row, odd
 	const size_t sum_off = mi::round_up((size_t)mm * row_w * 8, 16);
 	size_t lds = sum_off + (size_t)len * 4, scratch_off = 0, scratch = 0;
 	if (rated) {
 		for (int r = 2; r < 7; ++r) {
-			if (!used[r]) continue;
-			const size_t up = (size_t)((RS_FILT - 1 + len / r + RS_R + 1 + 3) & ~3) * 4;
-			const size_t down = ((size_t)r * rated_plen(r, len) + (size_t)len) * 4;
+			// each wavefront's scratch: the larger of the forms per used ratio -- up-sampler and down-sampler of a leg below the
+			// mix (in front of the pin, behind it), down-sampler and up-sampler of a leg above it
+			size_t up = 0, down = 0;
+			if (used[r]) {
+				up = (size_t)((RS_FILT - 1 + len / r + RS_R + 1 + 3) & ~3) * 4;
+				down = ((size_t)r * rated_plen(r, len) + (size_t)len) * 4;
+			}
+			if (above[r]) {
+				up = std::max(up, (size_t)((RS_FILT - 1 + len + RS_R + 1 + 3) & ~3) * 4);
+				down = std::max(down, ((size_t)r * updown_plen(r, r * len) + (size_t)r * len) * 4);
+			}
 			scratch = std::max(scratch, mi::round_up(std::max(up, down), 16));
 		}
 		scratch_off = mi::round_up(lds, 16);
 		lds = scratch_off + (BT / 64) * scratch;
 		if (lds + RATED_STATIC_LDS > BRIDGE_LDS_MAX) {
-			mi::set_error("mi_bridge_create_rated: a conference's tick and its resamplers' scratch must fit %zu bytes of LDS (%d members x %d samples "
+			mi::set_error("%s: a conference's tick and its resamplers' scratch must fit %zu bytes of LDS (%d members x %d samples "
 			              "= %zu, + %d wavefronts x %zu for ratio %d, + %zu of the kernel's own: %zu)",
-			              BRIDGE_LDS_MAX, mm, len, scratch_off, BT / 64, scratch, max_ratio, RATED_STATIC_LDS, lds + RATED_STATIC_LDS);
+			              fn, BRIDGE_LDS_MAX, mm, wide, scratch_off, BT / 64, scratch, max_ratio, RATED_STATIC_LDS, lds + RATED_STATIC_LDS);
 			return MI_ENOTSUP;
 		}
 	} else if (lds > BRIDGE_LDS_MAX) {
@@ -1104,6 +1446,7 @@ static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t
 	b->lds = lds;
 	b->nslice = std::max(1, std::min(mm, BT / (len >> 2)));
 	b->rated = rated, b->pitch = pitch;
+	b->updown = updown, b->wide = wide;
 	b->in_bytes = in_bytes, b->out_bytes = out_bytes;
 	if (h_leg_rate) b->leg_rate.assign(h_leg_rate, h_leg_rate + cfg->nstreams);
 	b->roster.init(b->n, mm);
@@ -1131,20 +1474,25 @@ static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t
 	if (rated) {
 		b->scratch_off = (int)scratch_off, b->scratch_per_wave = (int)scratch;
 		b->hout_stride = max_ratio * RS_FILT; // mi_resampler's round_up(filt_len - 1, 8) of the longest filter
+		if (updown) b->hin_stride = b->hout_stride; // a down-sampler's history on either side of the pin
 		std::vector<uint8_t> ratio(n);
-		for (size_t s = 0; s < n; ++s) ratio[s] = (uint8_t)(cfg->rate / h_leg_rate[s]);
+		for (size_t s = 0; s < n; ++s)
+			ratio[s] = h_leg_rate[s] > cfg->rate ? (uint8_t)(UD_ABOVE | (unsigned)(h_leg_rate[s] / cfg->rate)) : (uint8_t)(cfg->rate / h_leg_rate[s]);
 		b->d_ratio = (uint8_t *)mi_dev_alloc(ctx, n);
-		b->d_hist_in = (int16_t *)mi_dev_alloc(ctx, n * RS_FILT * sizeof(int16_t));
+		b->d_hist_in = (int16_t *)mi_dev_alloc(ctx, n * b->hin_stride * sizeof(int16_t));
 		b->d_hist_out = (int16_t *)mi_dev_alloc(ctx, n * b->hout_stride * sizeof(int16_t));
 		if (!b->d_ratio || !b->d_hist_in || !b->d_hist_out) return fail(MI_ENOMEM);
 		if (hipMemcpy(b->d_ratio, ratio.data(), n, hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
 		if ((rc = reset_resamplers(b, 0, b->n)) != MI_OK) return fail(rc);
-		if ((rc = build_tables(b, used)) != MI_OK) return fail(rc);
+		if ((rc = build_tables(b, used, above)) != MI_OK) return fail(rc);
 	}
 	if (h_codec) {
 		b->leg_codec.assign(h_codec, h_codec + n);
-		if (!(b->d_codec = (uint8_t *)mi_dev_alloc(ctx, n))) return fail(MI_ENOMEM);
-		if (hipMemcpy(b->d_codec, h_codec, n, hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
+		if (cfg->plc) // (one pair on every leg) a second row for the kernel behind the concealer, whose input is PCM
+			for (size_t s = 0; s < n; ++s) b->leg_codec.push_back((uint8_t)(h_codec[s] & ~3u));
+		if (!(b->d_codec = (uint8_t *)mi_dev_alloc(ctx, b->leg_codec.size()))) return fail(MI_ENOMEM);
+		if (hipMemcpy(b->d_codec, b->leg_codec.data(), b->leg_codec.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
+		b->leg_codec.resize(n);
 	}
 	if (cfg->plc) { // at the legs' one rate, on rows of the host buffers' pitch
 		if ((rc = mi_plc_create(ctx, b->n, rated ? common : cfg->rate, pitch, &b->plc)) != MI_OK) return fail(rc);
@@ -1167,7 +1515,10 @@ int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32
 	return create_bridge(ctx, cfg, h_leg_rate, nullptr, out);
 }
 
-int mi_bridge_create_legs(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
+// mi_bridge_create_legs and mi_bridge_create_endpoints: the legs' codecs checked, then create_bridge with the first's rules on
+// rates or the second's
+static int create_from_legs(const char *fn, bool endpoints, mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs,
+                            mi_bridge **out) {
 	if (!h_legs) return mi_bridge_create(ctx, cfg, out);
 	MI_CHECK_ARG(ctx && cfg && out);
 	*out = nullptr;
@@ -1176,27 +1527,39 @@ int mi_bridge_create_legs(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bri
 	std::vector<int32_t> rate(n);
 	std::vector<uint8_t> codec(n);
 	int differs = -1; // the first leg whose pair is not leg 0's
+	bool above = false;
 	for (size_t s = 0; s < n; ++s) {
 		const mi_bridge_leg &l = h_legs[s];
 		for (int v : {l.in_codec, l.out_codec})
 			if (v < MI_SESSION_PCM16 || v > MI_SESSION_PCMU) {
-				mi::set_error("mi_bridge_create_legs: leg %zu names codec %d; supported: MI_SESSION_PCM16 (0), MI_SESSION_PCMA (1), "
-				              "MI_SESSION_PCMU (2)", s, v);
+				mi::set_error("%s: leg %zu names codec %d; supported: MI_SESSION_PCM16 (0), MI_SESSION_PCMA (1), "
+				              "MI_SESSION_PCMU (2)", fn, s, v);
 				return MI_ENOTSUP;
 			}
 		rate[s] = l.rate;
 		codec[s] = (uint8_t)(l.in_codec | l.out_codec << 2);
 		if (differs < 0 && codec[s] != codec[0]) differs = (int)s;
+		above |= l.rate > cfg->rate;
 	}
 	if (differs >= 0 && cfg->plc) {
-		mi::set_error("mi_bridge_create_legs: plc with leg %d's codecs (in %d, out %d) unlike leg 0's (in %d, out %d): the concealer batch "
-		              "sits behind one decoder", differs, h_legs[differs].in_codec, h_legs[differs].out_codec, h_legs[0].in_codec,
+		mi::set_error("%s: plc with leg %d's codecs (in %d, out %d) unlike leg 0's (in %d, out %d): the concealer batch "
+		              "sits behind one decoder", fn, differs, h_legs[differs].in_codec, h_legs[differs].out_codec, h_legs[0].in_codec,
 		              h_legs[0].out_codec);
 		return MI_ENOTSUP;
 	}
 	mi_bridge_config c = *cfg; // a uniform bridge is mi_bridge_create_rated's, its one pair compile-time in the kernels
 	c.in_codec = h_legs[0].in_codec, c.out_codec = h_legs[0].out_codec;
-	return create_bridge(ctx, &c, rate.data(), differs >= 0 ? codec.data() : nullptr, out);
+	// with a leg above the mix (endpoints; create_bridge refuses it otherwise) the codecs are the kernel's data whether they
+	// differ or not, and the host rows byte rows
+	return create_bridge(ctx, &c, rate.data(), differs >= 0 || (endpoints && above) ? codec.data() : nullptr, out, endpoints);
+}
+
+int mi_bridge_create_legs(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
+	return create_from_legs("mi_bridge_create_legs", false, ctx, cfg, h_legs, out);
+}
+
+int mi_bridge_create_endpoints(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
+	return create_from_legs("mi_bridge_create_endpoints", true, ctx, cfg, h_legs, out);
 }
 
 int mi_bridge_leg_codec(const mi_bridge *b, int stream, int *in_codec, int *out_codec) {
