@@ -41,13 +41,24 @@
  * no block for the in_resampler of an absent leg nor for the out_resampler of a pin without MI_MIX_OUTPUT.  Byte rows at
  * one pitch as with mi_bridge_create_legs; the pitch, the widest leg's tick, may now exceed the conference's own.
  *
+ * Loss concealment for legs of any rate and codec (mi_bridge_create_concealed): in the reference every G.711 and L16 leg has
+ * MSGenericPLC behind its own decoder.  The constructor takes mi_bridge_create_endpoints' arguments and rules and lets
+ * cfg.plc hold whatever the legs: where they differ in rate or codec the concealer is a batch PER LEG in front of the
+ * bridge's unchanged kernel -- its streams grouped into rate classes, at most the seven rates one bridge can hold, the
+ * decoders inside its RECEIVED pass (plc_legs_received_kernel, plc_legs_conceal_kernel, csrc/plc.hip) --: three launches and
+ * the bridge's one per tick, bit for bit mi_g711_decode per law -> mi_plc_process per rate -> the plc-less bridge
+ * (tests/test_gpu_bridge_concealed.py).  An absent leg (h_present[s] == 0) is concealed at its own rate / 100 samples, then
+ * counts as present and is metered on what the concealer made, at its rate, in front of its in_resampler.
+ *
  * Out of scope, on purpose:
  *   - ratios that are no whole number (44.1 kHz; 32 kHz in 48 kHz) and whole ratios other than 2, 3 and 6, in either
  *     direction: refused with MI_ENOTSUP -- mi_session and the MSFilter plugin resample those;
  *   - jitter buffering and flow control: the host's, as with mi_session -- a leg whose packet is missing at the tick is
  *     flagged absent (or concealed, cfg.plc);
- *   - cfg.plc on a bridge whose legs differ in codec: refused with MI_ENOTSUP -- the concealer batch sits behind ONE
- *     decoder launch;
+ *   - cfg.plc with legs that differ in rate or codec through the four older constructors: they keep refusing it with
+ *     MI_ENOTSUP, mi_bridge_create_concealed serves it; and through any constructor a leg the concealer cannot serve -- a
+ *     rate outside 8 - 48 kHz (a 96 kHz member of a 16 kHz room, legal without plc), or one whose 50 ms window has a prime
+ *     factor above 17 (46.4 kHz), which kiss_fft itself refuses;
  *   - codecs other than G.711 and 16-bit PCM (G.722, Opus): the host's -- such a leg is a PCM leg of the bridge;
  *   - the plugin's server legs (MSMI355XServer*) keep their own launches: the plugin is built against the same ABI
  *     as its host double, which knows msmi355x.h only.
@@ -103,6 +114,16 @@ int mi_bridge_create_legs(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bri
  * codec pair; a conference whose rows -- as wide as the widest leg of the bridge --, sum row and resampler scratch do not
  * fit the 64 KB of LDS the kernel allows itself (48 kHz members in a 16 kHz conference: up to 45; in an 8 kHz one: 42). */
 int mi_bridge_create_endpoints(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */, mi_bridge **out);
+/* The same with cfg->plc served for legs of any rate and codec.  The arguments and every rule are
+ * mi_bridge_create_endpoints'.  cfg->plc == 0, or h_legs == NULL: that constructor's bridge exactly.  cfg->plc == 1 and every
+ * leg naming one rate and one codec pair: the plc bridge the older constructors build, the same launches, pitch and tick
+ * bytes.  cfg->plc == 1 with legs that differ in rate, codec or both: a concealer per leg behind the leg's own decoder, in
+ * front of the bridge's kernel; byte rows as with mi_bridge_create_legs; the event bytes are the uniform plc bridge's
+ * (h_present[s] == 0: MI_PLC_CONCEAL at the leg's own length).  mi_bridge_reset_streams and mi_bridge_add_member start the
+ * leg's concealer over.  MI_ENOTSUP, the message naming the leg and the value, before anything is allocated: what
+ * mi_bridge_create_endpoints refuses but for plc; with cfg->plc a leg outside 8 - 48 kHz or one whose concealer needs a
+ * transform radix above 17. */
+int mi_bridge_create_concealed(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */, mi_bridge **out);
 void mi_bridge_destroy(mi_bridge *b);
 int mi_bridge_leg_rate(const mi_bridge *b, int stream); /* the leg's rate in Hz, or MI_EINVAL */
 /* the leg's codecs and its own tick in bytes (rate / 100 x 1 or 2), on any bridge; either pointer may be NULL.

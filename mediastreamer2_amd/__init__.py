@@ -886,14 +886,16 @@ class Bridge(_ConferenceBatch):
     _destroy, _prefix = "mi_bridge_destroy", "bridge"
 
     def __init__(self, ctx, nstreams, members=32, rate=8000, in_codec=MI_SESSION_PCMU, out_codec=MI_SESSION_PCMU, plc=False, device=0,
-                 leg_rates=None, legs=None, endpoints=None):
+                 leg_rates=None, legs=None, endpoints=None, concealed=None):
         """leg_rates: the rate of every leg's code words or PCM [nstreams] (mi_bridge_create_rated: rate / leg rate in
         {1, 2, 3, 6}); None: every leg at `rate`.
         legs: every leg's (rate, in_codec, out_codec) [nstreams], a sequence of triples or a structured array with those
         fields (mi_bridge_create_legs; in_codec, out_codec and leg_rates are not read).  The staging views are then byte
         rows, uint8 [n, pitch]: leg_in / leg_out give a leg's own slice of one.
         endpoints: the same triples for mi_bridge_create_endpoints, where a leg may also be ABOVE `rate` by 2, 3 or 6 (a
-        48 kHz member of a 16 kHz conference); byte rows as with legs=, the pitch the widest leg's tick."""
+        48 kHz member of a 16 kHz conference); byte rows as with legs=, the pitch the widest leg's tick.
+        concealed: the same triples for mi_bridge_create_concealed: endpoints= whose plc=True holds for legs of any rate and
+        codec (a concealer per leg behind its own decoder); plc is passed as given, geometry and views are endpoints='."""
         self._own_ctx = ctx is None
         self.ctx = ctx = Context(device) if ctx is None else ctx
         cfg = BridgeConfig()
@@ -901,10 +903,12 @@ class Bridge(_ConferenceBatch):
         cfg.nstreams, cfg.members_per_conference, cfg.rate = nstreams, members, rate
         cfg.in_codec, cfg.out_codec, cfg.plc = in_codec, out_codec, int(plc)
         h = C.c_void_p()
-        if legs is not None or endpoints is not None:
-            assert legs is None or endpoints is None, "legs= or endpoints=, not both"
-            create = ctx.L.mi_bridge_create_legs if endpoints is None else ctx.L.mi_bridge_create_endpoints
-            lg = np.asarray(legs if endpoints is None else endpoints)
+        given = [v for v in (legs, endpoints, concealed) if v is not None]
+        if given:
+            assert len(given) == 1, "one of legs=, endpoints= and concealed="
+            create = (ctx.L.mi_bridge_create_legs if legs is not None else
+                      ctx.L.mi_bridge_create_endpoints if endpoints is not None else ctx.L.mi_bridge_create_concealed)
+            lg = np.asarray(given[0])
             if lg.dtype.names:
                 lg = np.stack([lg[k] for k in ("rate", "in_codec", "out_codec")], axis=-1)
             lg = np.ascontiguousarray(lg, np.int32)
@@ -922,7 +926,7 @@ class Bridge(_ConferenceBatch):
         self.in_dtype = C.c_uint8 if in_codec else C.c_int16
         self.out_dtype = C.c_uint8 if out_codec else C.c_int16
         self.in_len = self.out_len = self.len
-        if legs is not None or endpoints is not None:  # byte rows at mi_bridge_tick_bytes' pitch
+        if given:  # byte rows at mi_bridge_tick_bytes' pitch
             self.in_dtype = self.out_dtype = C.c_uint8
             self.in_len, self.out_len = self.tick_bytes()
 

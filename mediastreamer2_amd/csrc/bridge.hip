@@ -81,29 +81,7 @@ __device__ __forceinline__ int lo16(unsigned w) { return (int)(short)(w & 0xffff
 __device__ __forceinline__ int hi16(unsigned w) { return (int)(short)(w >> 16); }
 __device__ __forceinline__ unsigned pack16(int lo, int hi) { return (unsigned)(lo & 0xffff) | ((unsigned)hi << 16); }
 
-// ---- a leg's codec as data (mi_bridge_create_legs): `row` is the leg's byte row, whose pitch is a multiple of 16.
-// load_group with the kind in a register, in two steps so that a lane's loads are all issued before the first is used:
-// one 16-byte load whatever the kind -- a PCM leg's group, or the aligned pair of 8-byte groups that holds a G.711
-// leg's --, then both laws' decodes of the 8 code bytes and selects.  No branch: the lanes of a wavefront hold up to
-// eight members, of all three kinds.
-__device__ __forceinline__ uint4 load_raw_leg(const uint8_t *row, int kind, int g) {
-	return *reinterpret_cast<const uint4 *>(row + 16 * (kind == MI_SESSION_PCM16 ? g : g >> 1));
-}
-
-__device__ __forceinline__ uint4 decode_group_leg(uint4 v, int kind, int g) {
-	const bool pcm = kind == MI_SESSION_PCM16, mu = kind == MI_SESSION_PCMU;
-	const uint32_t w[2] = {(g & 1) ? v.z : v.x, (g & 1) ? v.w : v.y};
-	uint32_t o[4];
-#pragma unroll
-	for (int k = 0; k < 2; ++k) {
-		const uint32_t lo = __builtin_amdgcn_perm(0u, w[k], 0x0c010c00u), hi = __builtin_amdgcn_perm(0u, w[k], 0x0c030c02u);
-		const uint32_t alo = alaw2lin_x2(lo), ahi = alaw2lin_x2(hi), ulo = ulaw2lin_x2(lo), uhi = ulaw2lin_x2(hi);
-		o[2 * k] = mu ? ulo : alo;
-		o[2 * k + 1] = mu ? uhi : ahi;
-	}
-	return make_uint4(pcm ? v.x : o[0], pcm ? v.y : o[1], pcm ? v.z : o[2], pcm ? v.w : o[3]);
-}
-
+// ---- a leg's codec as data (mi_bridge_create_legs): load_raw_leg / decode_group_leg (g711.hpp) read a leg's byte row
 // eight samples of the leg's mix: 16 bytes of PCM, or 8 code words at the leg's law
 __device__ __forceinline__ void store_group_leg(uint8_t *row, int kind, int g, const int (&o)[8]) {
 	if (kind == MI_SESSION_PCM16) {
@@ -1165,6 +1143,9 @@ struct mi_bridge {
 	int wide = 0;                  // samples per LDS row: the widest leg's tick
 	int hin_stride = RS_FILT;      // samples per member of d_hist_in
 	int tab_down_in[7] = {}, tab_up_out[7] = {};
+	// the per-leg concealer (mi_bridge_create_concealed where the legs differ): `plc` is mi_plc_create_legs' and has the
+	// decoders; d_pcm [n][pitch] is what it makes of d_in, d_codec is [2][n] as above
+	bool leg_plc = false;
 };
 
 namespace {
@@ -1174,7 +1155,10 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 	int rc, in_kind = cf.in_codec;
 	const void *in = b->d_in[slot];
 	const uint8_t *present = b->d_present[slot];
-	if (b->plc) { // MSAlawDec / MSUlawDec as a launch of its own, then MSGenericPLC on the PCM rows, in place
+	if (b->leg_plc) { // every leg's decoder and MSGenericPLC in the concealer's three launches: byte rows in, PCM rows out
+		if ((rc = mi_plc_process_legs(b->plc, b->d_in[slot], b->in_bytes, b->d_pcm, (size_t)b->pitch, b->d_ev[slot])) != MI_OK) return rc;
+		in = b->d_pcm, present = nullptr; // a concealed leg counts as present
+	} else if (b->plc) { // MSAlawDec / MSUlawDec as a launch of its own, then MSGenericPLC on the PCM rows, in place
 		int16_t *rows = reinterpret_cast<int16_t *>(b->d_in[slot]);
 		if (cf.in_codec) {
 			if ((rc = mi_g711_decode(b->ctx, cf.in_codec == MI_SESSION_PCMA ? MI_LAW_PCMA : MI_LAW_PCMU, b->d_in[slot], b->in_bytes, b->d_pcm,
@@ -1221,7 +1205,9 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 	if (b->d_codec) {
 		LegsArgs la;
 		la.r = ra, la.r.b = a;
-		la.codec = b->d_codec, la.in_pitch = (int)b->in_bytes, la.out_pitch = (int)b->out_bytes;
+		// behind the concealer, as above
+		la.codec = b->plc ? b->d_codec + b->n : b->d_codec;
+		la.in_pitch = b->plc ? b->pitch * 2 : (int)b->in_bytes, la.out_pitch = (int)b->out_bytes;
 		if (b->rated) hipLaunchKernelGGL((bridge_legs_kernel<true>), grid, dim3(BT), b->lds, b->ctx->stream, la);
 		else hipLaunchKernelGGL((bridge_legs_kernel<false>), grid, dim3(BT), b->lds, b->ctx->stream, la);
 		MI_LAUNCH_CHECK();
@@ -1334,9 +1320,10 @@ int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) 
 
 // h_codec [nstreams]: in_codec | out_codec << 2 of legs that differ (mi_bridge_create_legs, which has checked them), or null.
 // endpoints: mi_bridge_create_endpoints' rules -- a leg may be above cfg->rate, and h_codec is there whenever one is
+// leg_plc: mi_bridge_create_concealed with cfg->plc and legs that differ -- the concealer is the per-leg one (h_codec is there)
 static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, const uint8_t *h_codec, mi_bridge **out,
-                         bool endpoints = false) {
-	const char *fn = endpoints ? "mi_bridge_create_endpoints" : "mi_bridge_create_rated";
+                         bool endpoints = false, bool leg_plc = false) {
+	const char *fn = leg_plc ? "mi_bridge_create_concealed" : endpoints ? "mi_bridge_create_endpoints" : "mi_bridge_create_rated";
 	MI_CHECK_ARG(ctx && cfg && out);
 	*out = nullptr;
 	MI_CHECK_ARG(cfg->nstreams > 0 && cfg->members_per_conference > 0 && cfg->members_per_conference <= MI_MIXER_MAX_CHANNELS &&
@@ -1378,7 +1365,7 @@ static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t
 				mi::set_error("%s: leg %d's rate %d is no multiple of 800 (a 10 ms tick must be whole groups of 8 samples)", fn, s, lr);
 				return MI_ENOTSUP;
 			}
-			if (cfg->plc && common && lr != common) {
+			if (cfg->plc && !leg_plc && common && lr != common) {
 				mi::set_error("%s: plc with legs at %d Hz and %d Hz: the concealer batch has one rate", fn, common, lr);
 				return MI_ENOTSUP;
 			}
@@ -1494,12 +1481,21 @@ static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t
 		if (hipMemcpy(b->d_codec, b->leg_codec.data(), b->leg_codec.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
 		b->leg_codec.resize(n);
 	}
-	if (cfg->plc) { // at the legs' one rate, on rows of the host buffers' pitch
-		if ((rc = mi_plc_create(ctx, b->n, rated ? common : cfg->rate, pitch, &b->plc)) != MI_OK) return fail(rc);
-		std::vector<int32_t> lens(n, pitch);
-		if (!(b->d_evlen = (int32_t *)mi_dev_alloc(ctx, n * 4))) return fail(MI_ENOMEM);
-		if (hipMemcpy(b->d_evlen, lens.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
-		if (cfg->in_codec && !(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * pitch * 2))) return fail(MI_ENOMEM);
+	if (cfg->plc) {
+		if (leg_plc) { // at every leg's own rate behind its own decoder, into PCM rows of `pitch` samples
+			std::vector<uint8_t> kind(n);
+			for (size_t s = 0; s < n; ++s) kind[s] = h_codec[s] & 3;
+			b->leg_plc = true;
+			if ((rc = mi_plc_create_legs(ctx, b->n, h_leg_rate, kind.data(), pitch, &b->plc)) != MI_OK) return fail(rc);
+			if (!(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * pitch * 2))) return fail(MI_ENOMEM);
+			if (hipMemsetAsync(b->d_pcm, 0, n * pitch * 2, ctx->stream) != hipSuccess) return fail(MI_ENODEV);
+		} else { // at the legs' one rate, on rows of the host buffers' pitch
+			if ((rc = mi_plc_create(ctx, b->n, rated ? common : cfg->rate, pitch, &b->plc)) != MI_OK) return fail(rc);
+			std::vector<int32_t> lens(n, pitch);
+			if (!(b->d_evlen = (int32_t *)mi_dev_alloc(ctx, n * 4))) return fail(MI_ENOMEM);
+			if (hipMemcpy(b->d_evlen, lens.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
+			if (cfg->in_codec && !(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * pitch * 2))) return fail(MI_ENOMEM);
+		}
 		for (int i = 0; i < SLOTS; ++i) {
 			b->h_ev[i] = (uint8_t *)mi_host_alloc(ctx, n);
 			b->d_ev[i] = (uint8_t *)mi_dev_alloc(ctx, n);
@@ -1516,9 +1512,10 @@ int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32
 }
 
 // mi_bridge_create_legs and mi_bridge_create_endpoints: the legs' codecs checked, then create_bridge with the first's rules on
-// rates or the second's
+// rates or the second's.  concealed: mi_bridge_create_concealed -- the second's rules, and cfg->plc with legs that differ is
+// served by the per-leg concealer instead of refused
 static int create_from_legs(const char *fn, bool endpoints, mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs,
-                            mi_bridge **out) {
+                            mi_bridge **out, bool concealed = false) {
 	if (!h_legs) return mi_bridge_create(ctx, cfg, out);
 	MI_CHECK_ARG(ctx && cfg && out);
 	*out = nullptr;
@@ -1541,6 +1538,19 @@ static int create_from_legs(const char *fn, bool endpoints, mi_ctx *ctx, const m
 		if (differs < 0 && codec[s] != codec[0]) differs = (int)s;
 		above |= l.rate > cfg->rate;
 	}
+	if (concealed && cfg->plc) {
+		bool one_rate = true;
+		for (size_t s = 0; s < n; ++s) { // what the concealer cannot serve, before anything is allocated
+			const int rc = mi_plc_check_rate(fn, "leg", (int)s, rate[s]);
+			if (rc != MI_OK) return rc;
+			one_rate &= rate[s] == rate[0];
+		}
+		if (differs >= 0 || !one_rate) {
+			mi_bridge_config c = *cfg; // (its pair is not read: the codecs are the kernel's data)
+			c.in_codec = h_legs[0].in_codec, c.out_codec = h_legs[0].out_codec;
+			return create_bridge(ctx, &c, rate.data(), codec.data(), out, true, true);
+		}
+	}
 	if (differs >= 0 && cfg->plc) {
 		mi::set_error("%s: plc with leg %d's codecs (in %d, out %d) unlike leg 0's (in %d, out %d): the concealer batch "
 		              "sits behind one decoder", fn, differs, h_legs[differs].in_codec, h_legs[differs].out_codec, h_legs[0].in_codec,
@@ -1560,6 +1570,10 @@ int mi_bridge_create_legs(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bri
 
 int mi_bridge_create_endpoints(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
 	return create_from_legs("mi_bridge_create_endpoints", true, ctx, cfg, h_legs, out);
+}
+
+int mi_bridge_create_concealed(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
+	return create_from_legs("mi_bridge_create_concealed", true, ctx, cfg, h_legs, out, true);
 }
 
 int mi_bridge_leg_codec(const mi_bridge *b, int stream, int *in_codec, int *out_codec) {

@@ -125,6 +125,18 @@ struct VolumeView {
 };
 void mi_volume_view(const mi_volume *v, VolumeView *out);
 
+// The concealer batch whose streams each have a rate and a decoder of their own (plc.hip), for the bridge's legs:
+// h_rate [nstreams] in Hz (multiples of 800), h_kind [nstreams] MI_SESSION_PCM16 | PCMA | PCMU: what the stream's byte row
+// holds, pitch: samples per PCM row.  MI_ENOTSUP, stream and rate in the message: a rate outside 8 - 48 kHz, or one whose
+// transforms need a radix above 17 (mi_plc_check_rate says so for one rate, naming `what` `index`, without a device).
+// mi_plc_reset / _info / _destroy take the object as they take mi_plc_create's.
+// mi_plc_process_legs: a tick of rate / 100 samples for every stream -- d_in byte rows at in_pitch (a multiple of 16; a
+// stream fills the first rate / 100 x 1 or 2 bytes), d_pcm the int16 rows out at `pitch` samples, d_mode the MI_PLC_*
+// event bytes -- in three launches, the decoders inside the RECEIVED pass.
+int mi_plc_check_rate(const char *fn, const char *what, int index, int rate);
+int mi_plc_create_legs(mi_ctx *c, int nstreams, const int32_t *h_rate, const uint8_t *h_kind, int pitch, mi_plc **out);
+int mi_plc_process_legs(mi_plc *p, const uint8_t *d_in, size_t in_pitch, int16_t *d_pcm, size_t pitch, const uint8_t *d_mode);
+
 struct mi_ctx {
 	int device = 0;
 	hipStream_t stream = nullptr;

@@ -1,8 +1,11 @@
 // g711.hpp -- G.711 A-law / mu-law arithmetic on the device (Snack_* of the reference's g711.c), shared by the streaming
-// converters (codec.hip) and the bridge's fused tick (bridge.hip).  All integer, bit-exact.
+// converters (codec.hip), the bridge's fused tick (bridge.hip) and the per-leg concealer's RECEIVED pass (plc.hip).  All integer,
+// bit-exact.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+
+#include "../../include/msmi355x.h"
 
 namespace {
 
@@ -51,6 +54,29 @@ __device__ __forceinline__ uint32_t lin2ulaw(int pcm) {
 	const int seg = max(26 - __clz(v), 0); // bit_length - 6
 	const int code = seg >= 8 ? 0x7F : ((seg << 4) | ((v >> (seg + 1)) & 15));
 	return (uint32_t)(code ^ (0xFF ^ (sign & 0x80)));
+}
+
+// ---- a leg's codec as data (mi_bridge_create_legs): `row` is the leg's byte row, whose pitch is a multiple of 16.
+// bridge.hip's load_group with the kind in a register, in two steps so that a lane's loads are all issued before the first is used:
+// one 16-byte load whatever the kind -- a PCM leg's group, or the aligned pair of 8-byte groups that holds a G.711
+// leg's --, then both laws' decodes of the 8 code bytes and selects.  No branch: the lanes of a wavefront hold up to
+// eight members, of all three kinds.
+__device__ __forceinline__ uint4 load_raw_leg(const uint8_t *row, int kind, int g) {
+	return *reinterpret_cast<const uint4 *>(row + 16 * (kind == MI_SESSION_PCM16 ? g : g >> 1));
+}
+
+__device__ __forceinline__ uint4 decode_group_leg(uint4 v, int kind, int g) {
+	const bool pcm = kind == MI_SESSION_PCM16, mu = kind == MI_SESSION_PCMU;
+	const uint32_t w[2] = {(g & 1) ? v.z : v.x, (g & 1) ? v.w : v.y};
+	uint32_t o[4];
+#pragma unroll
+	for (int k = 0; k < 2; ++k) {
+		const uint32_t lo = __builtin_amdgcn_perm(0u, w[k], 0x0c010c00u), hi = __builtin_amdgcn_perm(0u, w[k], 0x0c030c02u);
+		const uint32_t alo = alaw2lin_x2(lo), ahi = alaw2lin_x2(hi), ulo = ulaw2lin_x2(lo), uhi = ulaw2lin_x2(hi);
+		o[2 * k] = mu ? ulo : alo;
+		o[2 * k + 1] = mu ? uhi : ahi;
+	}
+	return make_uint4(pcm ? v.x : o[0], pcm ? v.y : o[1], pcm ? v.z : o[2], pcm ? v.w : o[3]);
 }
 
 } // namespace

@@ -21,7 +21,9 @@
 // Concealment is rare (a stream only computes FFTs on the tick its packet went missing and every ~nb samples
 // thereafter); a RECEIVED tick costs one pass over the block.
 #include "common.hpp"
+#include "g711.hpp"
 
+#include <algorithm>
 #include <cmath>
 
 namespace {
@@ -77,8 +79,11 @@ __device__ void shuffle(float2 *dst, const float2 *src, const Factors &f, int la
 	}
 }
 
-// kf_work kiss_fft.c:320-408, stages from the innermost outwards, on shuffled data in LDS
-__device__ void cfft(float2 *buf, const Factors &f, const float2 *tw, bool inverse, int lane) {
+// kf_work kiss_fft.c:320-408, stages from the innermost outwards, on shuffled data in LDS.  SPARE: the generic butterfly's
+// copy of its inputs sits in `spare` ([radix][64] float2 of LDS, a lane's own column) instead of a private array, which
+// the compiler keeps in scratch memory
+template <bool SPARE>
+__device__ void cfft(float2 *buf, const Factors &f, const float2 *tw, bool inverse, int lane, float2 *spare) {
 #pragma unroll 1
 	for (int s = f.count - 1; s >= 0; --s) {
 		const int p = f.p[s], m = f.m[s], fs = f.fs[s], m2 = p * m;
@@ -133,17 +138,18 @@ __device__ void cfft(float2 *buf, const Factors &f, const float2 *tw, bool inver
 				F[2 * m] = cadd(s11, s12);
 				F[3 * m] = csub(s11, s12);
 			} else { // kf_bfly_generic :259-291 (radix 7, 11, 13, 17: the 44.1 kHz family has a factor 11); C_FIXDIV is a no-op
-				float2 sc[17]; // in floats; the twiddle index walks the FULL transform's table modulo its size
+				float2 sc_own[SPARE ? 1 : 17]; // in floats; the twiddle index walks the FULL transform's table modulo its size
+				auto sc = [&](int q) -> float2 & { return SPARE ? spare[q * 64 + lane] : sc_own[SPARE ? 0 : q]; };
 				const int norig = f.n;
-				for (int q = 0; q < p; ++q) sc[q] = F[q * m];
+				for (int q = 0; q < p; ++q) sc(q) = F[q * m];
 				int k = j;
 				for (int q1 = 0; q1 < p; ++q1) {
 					int twidx = 0;
-					float2 acc = sc[0];
+					float2 acc = sc(0);
 					for (int q = 1; q < p; ++q) {
 						twidx += fs * k;
 						if (twidx >= norig) twidx -= norig;
-						acc = cadd(acc, cmul(sc[q], tw[twidx]));
+						acc = cadd(acc, cmul(sc(q), tw[twidx]));
 					}
 					F[q1 * m] = acc;
 					k += m;
@@ -167,8 +173,10 @@ struct Lds {
 	int16_t *blk, *out; // cap each
 };
 
-// generic_plc_fftbf genericplc.c:83-121.  src(i): the nb input samples; result in L.gen[0 .. 2 nb).
-template <typename Src>
+// generic_plc_fftbf genericplc.c:83-121.  src(i): the nb input samples; result in L.gen[0 .. 2 nb).  SPARE: cfft's; the
+// spare LDS is the transform buffer a cfft does not work in -- A under the forward transform, whose input the shuffle has
+// moved to B, and B under the inverse one.  A generic radix p > 5 divides nb / 100, so 8 nb bytes hold its 512 p.
+template <bool SPARE, typename Src>
 __device__ void fftbf(const PlcArgs &a, const Lds &L, Src src, int lane) {
 	const int nb = a.nb, n1 = nb / 2, n2 = nb;
 	for (int i = lane; i < nb; i += 64) L.A[i] = (float)src(i) * a.window[i];
@@ -177,7 +185,7 @@ __device__ void fftbf(const PlcArgs &a, const Lds &L, Src src, int lane) {
 	float2 *tmp = reinterpret_cast<float2 *>(L.B);
 	shuffle(tmp, reinterpret_cast<const float2 *>(L.A), a.f1, lane);
 	wave_sync();
-	cfft(tmp, a.f1, a.tw1, false, lane);
+	cfft<SPARE>(tmp, a.f1, a.tw1, false, lane, reinterpret_cast<float2 *>(L.A));
 	const float scale = __fdiv_rn(1.f, (float)nb);
 	float *f = L.A;
 	for (int k = lane; k <= n1 / 2; k += 64) {
@@ -216,7 +224,7 @@ __device__ void fftbf(const PlcArgs &a, const Lds &L, Src src, int lane) {
 	float2 *t2 = reinterpret_cast<float2 *>(L.A);
 	shuffle(t2, tmp, a.f2, lane);
 	wave_sync();
-	cfft(t2, a.f2, a.tw2, true, lane);
+	cfft<SPARE>(t2, a.f2, a.tw2, true, lane, reinterpret_cast<float2 *>(L.B));
 	for (int i = lane; i < 2 * nb; i += 64) L.gen[i] = to_i16(L.A[i]);
 	wave_sync();
 }
@@ -238,8 +246,18 @@ __device__ void update_history(int16_t *hist, uint32_t &head, const int16_t *dat
 // 18 workgroups per CU for work that needs 1 KB: 48 us for 65 536 clean legs.)
 constexpr int PLC_LIGHT_WAVES = 4;
 
-template <bool CONCEAL>
-__device__ __forceinline__ void plc_stream(const PlcArgs &a, float *lds_f, int s, int mode, int len, uint4 meta, int lane) {
+// where plc_stream's RECEIVED pass takes its block from: the stream's row, as it arrived
+struct RowBlock {
+	__device__ __forceinline__ void operator()(int16_t *blk, const int16_t *row, int n, int lane) const {
+		for (int i = lane; i < n; i += 64) blk[i] = row[i];
+	}
+};
+
+// s: the stream's index in the state arrays; srow: its row of a.blocks (the same but for the per-leg form, whose state is
+// kept per rate class).  LEGS: the per-leg form's kernels (fftbf's SPARE).  Block: RowBlock, or what decodes the block.
+template <bool CONCEAL, bool LEGS = false, typename Block = RowBlock>
+__device__ __forceinline__ void plc_stream(const PlcArgs &a, float *lds_f, int s, int srow, int mode, int len, uint4 meta, int lane,
+                                           Block block = Block()) {
 	const int nb = a.nb, T = a.T;
 	Lds L;
 	if (CONCEAL) {
@@ -255,14 +273,14 @@ __device__ __forceinline__ void plc_stream(const PlcArgs &a, float *lds_f, int s
 	L.blk = L.cont + 2 * T;
 	L.out = L.blk + a.cap;
 	int16_t *g_cont = a.cont + (size_t)s * 2 * T, *g_hist = a.hist + (size_t)s * nb, *g_gen = a.gen + (size_t)s * 2 * nb;
-	int16_t *row = a.blocks + (size_t)s * a.stride;
+	int16_t *row = a.blocks + (size_t)srow * a.stride;
 	const int n = min(max(len, 0), a.cap);
 	uint32_t index = meta.x & 0xffffu, used = meta.y & 0xffffu, head = meta.z;
 	if (n == 0) return;
 	for (int i = lane; i < 2 * T; i += 64) L.cont[i] = g_cont[i];
 
 	if constexpr (!CONCEAL) { // ---- a block arrived: msgenericplc.c:63-116
-		for (int i = lane; i < n; i += 64) L.blk[i] = row[i];
+		block(L.blk, row, n, lane);
 		wave_sync();
 		update_history(g_hist, head, L.blk, n, nb, lane);
 		// generic_plc_update_continuity_buffer :212-231: the block leaves 5 ms late
@@ -299,7 +317,7 @@ __device__ __forceinline__ void plc_stream(const PlcArgs &a, float *lds_f, int s
 			bool gen_dirty = false;
 			if (used == 0) { // first missing packet :136-144
 				const uint32_t h = head;
-				fftbf(a, L, [&](int i) { return g_hist[(h + (uint32_t)i) % (uint32_t)nb]; }, lane);
+				fftbf<LEGS>(a, L, [&](int i) { return g_hist[(h + (uint32_t)i) % (uint32_t)nb]; }, lane);
 				for (int i = lane; i < T; i += 64) L.gen[i] = mix1(L.gen[i], L.cont[i], i, T);
 				wave_sync();
 				gen_dirty = true;
@@ -314,7 +332,7 @@ __device__ __forceinline__ void plc_stream(const PlcArgs &a, float *lds_f, int s
 				for (int i = lane; i < T; i += 64) L.cont[i] = L.gen[index + ready + i];
 				wave_sync();
 				const int16_t *g = L.gen;
-				fftbf(a, L, [&](int i) { return g[i]; }, lane);
+				fftbf<LEGS>(a, L, [&](int i) { return g[i]; }, lane);
 				for (int i = lane; i < T; i += 64) L.gen[i] = mix1(L.gen[i], L.cont[i], i, T);
 				wave_sync();
 				for (int i = lane; i < n - ready; i += 64) L.out[ready + i] = L.gen[i];
@@ -375,7 +393,7 @@ __global__ __launch_bounds__(64 * PLC_LIGHT_WAVES) void plc_received_kernel(PlcA
 	const int mode = a.mode[s], len = a.len[s];
 	const uint4 meta = reinterpret_cast<const uint4 *>(a.meta)[s];
 	if ((mode & 3) != 1) return;
-	plc_stream<false>(a, lds_all + (size_t)wave * a.light_floats, s, mode, len, meta, lane);
+	plc_stream<false>(a, lds_all + (size_t)wave * a.light_floats, s, s, mode, len, meta, lane);
 }
 
 __global__ __launch_bounds__(64) void plc_conceal_kernel(PlcArgs a) {
@@ -384,7 +402,60 @@ __global__ __launch_bounds__(64) void plc_conceal_kernel(PlcArgs a) {
 	const int count = *a.count;
 	for (int k = blockIdx.x; k < count; k += gridDim.x) {
 		const int s = a.list[k];
-		plc_stream<true>(a, lds_all, s, MI_PLC_CONCEAL, a.len[s], reinterpret_cast<const uint4 *>(a.meta)[s], lane);
+		plc_stream<true>(a, lds_all, s, s, MI_PLC_CONCEAL, a.len[s], reinterpret_cast<const uint4 *>(a.meta)[s], lane);
+		wave_sync(); // the next stream reuses the LDS
+	}
+}
+
+// ---- the per-leg form (mi_plc_create_legs): every stream belongs to a RATE CLASS -- at most seven in one bridge, the mix's rate
+// x {1, 2, 3, 6} and / {2, 3, 6} -- and sits behind a decoder of its own.  A class is what mi_plc_create builds for its one
+// rate, a whole PlcArgs record with its own state arrays; a stream's tag byte names its class (bits 0-2) and what its
+// row holds (MI_SESSION_* << 4), its rank is its index among the class's streams.  The tick is three launches as above:
+// plc_list_kernel as it is (the first record's nstreams, mode, len, count and list), then the two kernels below, which
+// pick the stream's record and run plc_stream on it.
+constexpr int PLC_MAX_CLASSES = 7;
+
+struct PlcLegsArgs {
+	PlcArgs cls[PLC_MAX_CLASSES]; // blocks / stride: the PCM rows out; nstreams, cap, len, mode, count, list: the same in each
+	const uint8_t *tag;
+	const int32_t *rank;
+	const uint8_t *in; // the byte rows as they arrived: code words or PCM
+	size_t in_pitch;   // bytes, a multiple of 16
+};
+static_assert(sizeof(PlcLegsArgs) <= 4096, "the records travel in the kernel arguments");
+
+// MSAlawDec / MSUlawDec in front of the RECEIVED pass: phase (A) of bridge_legs_kernel (bridge.hip) -- one 16-byte load
+// per eight samples whatever the kind, both laws decoded, selects --, the block straight into LDS
+struct LegBlock {
+	const uint8_t *in;
+	int kind;
+	__device__ __forceinline__ void operator()(int16_t *blk, const int16_t *, int n, int lane) const {
+		for (int g = lane; g < (n >> 3); g += 64) // (a leg's tick is whole groups of eight: its rate is a multiple of 800)
+			*reinterpret_cast<uint4 *>(blk + 8 * g) = decode_group_leg(load_raw_leg(in, kind, g), kind, g);
+	}
+};
+
+__global__ __launch_bounds__(64 * PLC_LIGHT_WAVES) void plc_legs_received_kernel(PlcLegsArgs la) {
+	extern __shared__ float lds_all[];
+	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const int s = __builtin_amdgcn_readfirstlane(blockIdx.x * PLC_LIGHT_WAVES + wave);
+	if (s >= la.cls[0].nstreams) return;
+	const int mode = la.cls[0].mode[s], len = la.cls[0].len[s], tag = la.tag[s], rank = la.rank[s];
+	if ((mode & 3) != 1) return;
+	const PlcArgs &a = la.cls[__builtin_amdgcn_readfirstlane(tag & 7)];
+	plc_stream<false, true>(a, lds_all + (size_t)wave * a.light_floats, rank, s, mode, len, reinterpret_cast<const uint4 *>(a.meta)[rank], lane,
+	                        LegBlock{la.in + (size_t)s * la.in_pitch, tag >> 4});
+}
+
+__global__ __launch_bounds__(64) void plc_legs_conceal_kernel(PlcLegsArgs la) {
+	extern __shared__ float lds_all[];
+	const int lane = threadIdx.x;
+	const int count = *la.cls[0].count;
+	for (int k = blockIdx.x; k < count; k += gridDim.x) {
+		const int s = __builtin_amdgcn_readfirstlane(la.cls[0].list[k]);
+		const int rank = la.rank[s];
+		const PlcArgs &a = la.cls[__builtin_amdgcn_readfirstlane(la.tag[s] & 7)];
+		plc_stream<true, true>(a, lds_all, rank, s, MI_PLC_CONCEAL, a.len[s], reinterpret_cast<const uint4 *>(a.meta)[rank], lane);
 		wave_sync(); // the next stream reuses the LDS
 	}
 }
@@ -430,17 +501,95 @@ void twiddles(int n, bool inverse, std::vector<float2> &tw, std::vector<float2> 
 
 } // namespace
 
-struct mi_plc {
-	mi_ctx *ctx = nullptr;
-	int nstreams = 0, rate = 0, nb = 0, T = 0, cap = 0;
+// one rate's concealer: what generic_plc_create_context derives from the rate, the tables, and the state of its streams
+struct PlcClass {
+	int rate = 0, nb = 0, T = 0, count = 0; // count: streams
 	Factors f1, f2;
-	int16_t *d_cont = nullptr, *d_hist = nullptr, *d_gen = nullptr;
+	int16_t *d_cont = nullptr, *d_hist = nullptr, *d_gen = nullptr; // [count][2T], [count][nb], [count][2 nb]
 	uint32_t *d_meta = nullptr;
 	float *d_window = nullptr;
 	float2 *d_tw1 = nullptr, *d_sup1 = nullptr, *d_tw2 = nullptr, *d_sup2 = nullptr;
-	size_t lds = 0, lds_light = 0;
-	int *d_count = nullptr, *d_list = nullptr;
 };
+
+struct mi_plc {
+	mi_ctx *ctx = nullptr;
+	int nstreams = 0, cap = 0;
+	std::vector<PlcClass> cls; // mi_plc_create: one, stream s at rank s; mi_plc_create_legs: one per distinct rate
+	size_t lds = 0, lds_light = 0; // of the largest class
+	int *d_count = nullptr, *d_list = nullptr;
+	// the per-leg form
+	bool legs = false;
+	std::vector<uint8_t> tag;  // [nstreams] class | MI_SESSION_* << 4
+	std::vector<int32_t> rank; // [nstreams] index among the class's streams
+	uint8_t *d_tag = nullptr;
+	int32_t *d_rank = nullptr, *d_len = nullptr; // d_len: rate / 100
+	size_t in_bytes = 0;                         // the widest leg's tick in bytes, rounded up to the 16 a lane loads
+};
+
+namespace {
+
+// false: kiss_fft refuses the transforms (or the sizes are none)
+bool class_sizes(int rate, PlcClass *k) {
+	k->rate = rate;
+	k->nb = ((rate * 2 / 40) / 100) * 100; // generic_plc_create_context genericplc.c:46-48 (PLC_BUFFER_LEN is the tokens 2 / 40)
+	k->T = rate * TRANSITION_DELAY / 1000;
+	return !(k->nb < 4 || (k->nb & 1) || k->T > 256 || !factorize(k->nb / 2, &k->f1) || !factorize(k->nb, &k->f2));
+}
+
+size_t class_lds(const PlcClass &k, int cap) {
+	return (sizeof(float) * 4 * (size_t)k.nb + sizeof(int16_t) * (2 * (size_t)k.nb + 2 * (size_t)k.T + 2 * (size_t)cap) + 15) & ~(size_t)15;
+}
+
+// state of k.count streams and the tables of a class whose sizes are set
+int class_alloc(PlcClass &k) {
+	const size_t n = (size_t)k.count;
+	if (hipMalloc(&k.d_cont, n * 2 * k.T * 2) != hipSuccess || hipMalloc(&k.d_hist, n * k.nb * 2) != hipSuccess ||
+	    hipMalloc(&k.d_gen, n * 2 * k.nb * 2) != hipSuccess || hipMalloc(&k.d_meta, n * 16) != hipSuccess ||
+	    hipMalloc(&k.d_window, sizeof(float) * k.nb) != hipSuccess || hipMalloc(&k.d_tw1, sizeof(float2) * (k.nb / 2)) != hipSuccess ||
+	    hipMalloc(&k.d_sup1, sizeof(float2) * (k.nb / 2)) != hipSuccess || hipMalloc(&k.d_tw2, sizeof(float2) * k.nb) != hipSuccess ||
+	    hipMalloc(&k.d_sup2, sizeof(float2) * k.nb) != hipSuccess) {
+		mi::set_error("mi_plc_create: out of device memory");
+		return MI_ENOMEM;
+	}
+	std::vector<float> win((size_t)k.nb);
+	for (int i = 0; i < k.nb; ++i) win[(size_t)i] = (float)(0.75 - 0.25 * std::cos(2 * 3.14159265 * i / (k.nb))); // genericplc.c:63-65
+	std::vector<float2> tw1, sup1, tw2, sup2;
+	twiddles(k.nb / 2, false, tw1, sup1);
+	twiddles(k.nb, true, tw2, sup2);
+	if (hipMemcpy(k.d_window, win.data(), sizeof(float) * win.size(), hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(k.d_tw1, tw1.data(), sizeof(float2) * tw1.size(), hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(k.d_sup1, sup1.data(), sizeof(float2) * sup1.size(), hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(k.d_tw2, tw2.data(), sizeof(float2) * tw2.size(), hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(k.d_sup2, sup2.data(), sizeof(float2) * sup2.size(), hipMemcpyHostToDevice) != hipSuccess) {
+		mi::set_error("mi_plc_create: table upload failed");
+		return MI_ENODEV;
+	}
+	return MI_OK;
+}
+
+// a fresh plc_context_t for `count` streams of a class from rank `first`: everything zero (ms_malloc0, genericplc.c:42-57)
+int class_reset(const PlcClass &k, int first, int count, hipStream_t st) {
+	MI_HIP(hipMemsetAsync(k.d_cont + (size_t)first * 2 * k.T, 0, (size_t)count * 2 * k.T * 2, st));
+	MI_HIP(hipMemsetAsync(k.d_hist + (size_t)first * k.nb, 0, (size_t)count * k.nb * 2, st));
+	MI_HIP(hipMemsetAsync(k.d_gen + (size_t)first * 2 * k.nb, 0, (size_t)count * 2 * k.nb * 2, st));
+	MI_HIP(hipMemsetAsync(k.d_meta + (size_t)first * 4, 0, (size_t)count * 16, st));
+	return MI_OK;
+}
+
+// a class's record for the kernels
+PlcArgs class_args(const mi_plc *p, const PlcClass &k, int16_t *d_blocks, size_t stride, const int32_t *d_len, const uint8_t *d_mode) {
+	PlcArgs a{};
+	a.cont = k.d_cont, a.hist = k.d_hist, a.gen = k.d_gen, a.meta = k.d_meta, a.window = k.d_window;
+	a.tw1 = k.d_tw1, a.sup1 = k.d_sup1, a.tw2 = k.d_tw2, a.sup2 = k.d_sup2;
+	a.f1 = k.f1, a.f2 = k.f2;
+	a.nb = k.nb, a.T = k.T, a.rate = k.rate, a.nstreams = p->nstreams, a.cap = (int)std::min<size_t>((size_t)p->cap, stride);
+	a.blocks = d_blocks, a.stride = stride, a.len = d_len, a.mode = d_mode;
+	a.light_floats = (int)(p->lds_light / sizeof(float));
+	a.count = p->d_count, a.list = p->d_list;
+	return a;
+}
+
+} // namespace
 
 extern "C" {
 
@@ -448,7 +597,12 @@ void mi_plc_destroy(mi_plc *p) {
 	if (!p) return;
 	if (p->ctx->activate() == MI_OK) {
 		(void)hipStreamSynchronize(p->ctx->stream);
-		void *dv[] = {p->d_cont, p->d_hist, p->d_gen, p->d_meta, p->d_window, p->d_tw1, p->d_sup1, p->d_tw2, p->d_sup2, p->d_count, p->d_list};
+		for (const PlcClass &k : p->cls) {
+			void *dv[] = {k.d_cont, k.d_hist, k.d_gen, k.d_meta, k.d_window, k.d_tw1, k.d_sup1, k.d_tw2, k.d_sup2};
+			for (void *v : dv)
+				if (v) (void)hipFree(v);
+		}
+		void *dv[] = {p->d_count, p->d_list, p->d_tag, p->d_rank, p->d_len};
 		for (void *v : dv)
 			if (v) (void)hipFree(v);
 	}
@@ -461,19 +615,18 @@ int mi_plc_create(mi_ctx *c, int nstreams, int rate, int max_block, mi_plc **out
 	int rc;
 	if ((rc = c->activate()) != MI_OK) return rc;
 	mi_plc *p = new mi_plc();
-	p->ctx = c, p->nstreams = nstreams, p->rate = rate, p->cap = max_block;
-	p->nb = ((rate * 2 / 40) / 100) * 100; // generic_plc_create_context genericplc.c:46-48 (PLC_BUFFER_LEN is the tokens 2 / 40)
-	p->T = rate * TRANSITION_DELAY / 1000;
-	if (p->nb < 4 || (p->nb & 1) || p->T > 256 || !factorize(p->nb / 2, &p->f1) || !factorize(p->nb, &p->f2)) {
+	p->ctx = c, p->nstreams = nstreams, p->cap = max_block;
+	p->cls.resize(1);
+	PlcClass &k = p->cls[0];
+	k.count = nstreams;
+	if (!class_sizes(rate, &k)) {
 		mi::set_error("mi_plc_create: %d Hz gives transforms of %d / %d points with a prime factor above 17 (kiss_fft itself refuses those)",
-		              rate, p->nb / 2, p->nb);
+		              rate, k.nb / 2, k.nb);
 		delete p;
 		return MI_ENOTSUP;
 	}
-	const size_t n = (size_t)nstreams;
-	p->lds = sizeof(float) * 4 * (size_t)p->nb + sizeof(int16_t) * (2 * (size_t)p->nb + 2 * (size_t)p->T + 2 * (size_t)p->cap);
-	p->lds = (p->lds + 15) & ~(size_t)15;
-	p->lds_light = (sizeof(int16_t) * (2 * (size_t)p->T + 2 * (size_t)p->cap) + 15) & ~(size_t)15;
+	p->lds = class_lds(k, p->cap);
+	p->lds_light = (sizeof(int16_t) * (2 * (size_t)k.T + 2 * (size_t)p->cap) + 15) & ~(size_t)15;
 	if (p->lds > 64 * 1024) {
 		mi::set_error("mi_plc_create: %zu bytes of LDS per stream (rate %d, blocks of %d) exceed 64 KB", p->lds, rate, max_block);
 		delete p;
@@ -483,27 +636,10 @@ int mi_plc_create(mi_ctx *c, int nstreams, int rate, int max_block, mi_plc **out
 		mi_plc_destroy(p);
 		return code;
 	};
-	if (hipMalloc(&p->d_cont, n * 2 * p->T * 2) != hipSuccess || hipMalloc(&p->d_hist, n * p->nb * 2) != hipSuccess ||
-	    hipMalloc(&p->d_gen, n * 2 * p->nb * 2) != hipSuccess || hipMalloc(&p->d_meta, n * 16) != hipSuccess ||
-	    hipMalloc(&p->d_window, sizeof(float) * p->nb) != hipSuccess || hipMalloc(&p->d_tw1, sizeof(float2) * (p->nb / 2)) != hipSuccess ||
-	    hipMalloc(&p->d_sup1, sizeof(float2) * (p->nb / 2)) != hipSuccess || hipMalloc(&p->d_tw2, sizeof(float2) * p->nb) != hipSuccess ||
-	    hipMalloc(&p->d_sup2, sizeof(float2) * p->nb) != hipSuccess || hipMalloc(&p->d_count, sizeof(int)) != hipSuccess ||
-	    hipMalloc(&p->d_list, sizeof(int) * n) != hipSuccess) {
+	if ((rc = class_alloc(k)) != MI_OK) return fail(rc);
+	if (hipMalloc(&p->d_count, sizeof(int)) != hipSuccess || hipMalloc(&p->d_list, sizeof(int) * (size_t)nstreams) != hipSuccess) {
 		mi::set_error("mi_plc_create: out of device memory");
 		return fail(MI_ENOMEM);
-	}
-	std::vector<float> win((size_t)p->nb);
-	for (int i = 0; i < p->nb; ++i) win[(size_t)i] = (float)(0.75 - 0.25 * std::cos(2 * 3.14159265 * i / (p->nb))); // genericplc.c:63-65
-	std::vector<float2> tw1, sup1, tw2, sup2;
-	twiddles(p->nb / 2, false, tw1, sup1);
-	twiddles(p->nb, true, tw2, sup2);
-	if (hipMemcpy(p->d_window, win.data(), sizeof(float) * win.size(), hipMemcpyHostToDevice) != hipSuccess ||
-	    hipMemcpy(p->d_tw1, tw1.data(), sizeof(float2) * tw1.size(), hipMemcpyHostToDevice) != hipSuccess ||
-	    hipMemcpy(p->d_sup1, sup1.data(), sizeof(float2) * sup1.size(), hipMemcpyHostToDevice) != hipSuccess ||
-	    hipMemcpy(p->d_tw2, tw2.data(), sizeof(float2) * tw2.size(), hipMemcpyHostToDevice) != hipSuccess ||
-	    hipMemcpy(p->d_sup2, sup2.data(), sizeof(float2) * sup2.size(), hipMemcpyHostToDevice) != hipSuccess) {
-		mi::set_error("mi_plc_create: table upload failed");
-		return fail(MI_ENODEV);
 	}
 	if ((rc = mi_plc_reset(p, 0, nstreams)) != MI_OK) return fail(rc);
 	*out = p;
@@ -516,25 +652,26 @@ int mi_plc_reset(mi_plc *p, int first, int count) { // a fresh plc_context_t: ev
 	int rc;
 	if ((rc = p->ctx->activate()) != MI_OK) return rc;
 	hipStream_t st = p->ctx->stream;
-	MI_HIP(hipMemsetAsync(p->d_cont + (size_t)first * 2 * p->T, 0, (size_t)count * 2 * p->T * 2, st));
-	MI_HIP(hipMemsetAsync(p->d_hist + (size_t)first * p->nb, 0, (size_t)count * p->nb * 2, st));
-	MI_HIP(hipMemsetAsync(p->d_gen + (size_t)first * 2 * p->nb, 0, (size_t)count * 2 * p->nb * 2, st));
-	MI_HIP(hipMemsetAsync(p->d_meta + (size_t)first * 4, 0, (size_t)count * 16, st));
+	if (!p->legs) return class_reset(p->cls[0], first, count, st);
+	if (count == p->nstreams) {
+		for (const PlcClass &k : p->cls)
+			if ((rc = class_reset(k, 0, k.count, st)) != MI_OK) return rc;
+		return MI_OK;
+	}
+	for (int s = first; s < first + count; ++s) // (a replaced leg: one stream, or a few)
+		if ((rc = class_reset(p->cls[p->tag[(size_t)s] & 7], p->rank[(size_t)s], 1, st)) != MI_OK) return rc;
 	return MI_OK;
 }
 
 int mi_plc_process(mi_plc *p, int16_t *d_blocks, size_t stride, const int32_t *d_len, const uint8_t *d_mode) {
 	MI_CHECK_ARG(p && d_blocks && d_len && d_mode && stride > 0);
+	if (p->legs) {
+		mi::set_error("mi_plc_process: a per-leg concealer takes byte rows (mi_plc_process_legs)");
+		return MI_EINVAL;
+	}
 	int rc;
 	if ((rc = p->ctx->activate()) != MI_OK) return rc;
-	PlcArgs a{};
-	a.cont = p->d_cont, a.hist = p->d_hist, a.gen = p->d_gen, a.meta = p->d_meta, a.window = p->d_window;
-	a.tw1 = p->d_tw1, a.sup1 = p->d_sup1, a.tw2 = p->d_tw2, a.sup2 = p->d_sup2;
-	a.f1 = p->f1, a.f2 = p->f2;
-	a.nb = p->nb, a.T = p->T, a.rate = p->rate, a.nstreams = p->nstreams, a.cap = (int)std::min<size_t>((size_t)p->cap, stride);
-	a.blocks = d_blocks, a.stride = stride, a.len = d_len, a.mode = d_mode;
-	a.light_floats = (int)(p->lds_light / sizeof(float));
-	a.count = p->d_count, a.list = p->d_list;
+	const PlcArgs a = class_args(p, p->cls[0], d_blocks, stride, d_len, d_mode);
 	MI_HIP(hipMemsetAsync(p->d_count, 0, sizeof(int), p->ctx->stream));
 	hipLaunchKernelGGL(plc_list_kernel, dim3((p->nstreams + 255) / 256), dim3(256), 0, p->ctx->stream, a);
 	MI_LAUNCH_CHECK();
@@ -551,14 +688,115 @@ int mi_plc_info(mi_plc *p, int stream, int32_t out3[3]) {
 	MI_CHECK_ARG(p && out3 && stream >= 0 && stream < p->nstreams);
 	int rc;
 	if ((rc = p->ctx->activate()) != MI_OK) return rc;
+	const PlcClass &k = p->cls[p->legs ? p->tag[(size_t)stream] & 7 : 0];
+	const size_t at = p->legs ? (size_t)p->rank[(size_t)stream] : (size_t)stream;
 	uint32_t m[4];
-	MI_HIP(hipMemcpyAsync(m, p->d_meta + (size_t)stream * 4, 16, hipMemcpyDeviceToHost, p->ctx->stream));
+	MI_HIP(hipMemcpyAsync(m, k.d_meta + at * 4, 16, hipMemcpyDeviceToHost, p->ctx->stream));
 	MI_HIP(hipStreamSynchronize(p->ctx->stream));
-	out3[0] = p->nb, out3[1] = (int32_t)m[0], out3[2] = (int32_t)m[1];
+	out3[0] = k.nb, out3[1] = (int32_t)m[0], out3[2] = (int32_t)m[1];
 	return MI_OK;
 }
 
 } // extern "C"
+
+// ---- the per-leg form's entry points (common.hpp): reached through the bridge, no symbol of msmi355x.h
+int mi_plc_check_rate(const char *fn, const char *what, int index, int rate) {
+	PlcClass k;
+	if (rate < 8000 || rate > 48000) {
+		mi::set_error("%s: %s %d at %d Hz: the concealer serves 8000 to 48000 Hz", fn, what, index, rate);
+		return MI_ENOTSUP;
+	}
+	if (!class_sizes(rate, &k)) {
+		mi::set_error("%s: %s %d: %d Hz gives transforms of %d / %d points with a prime factor above 17 (kiss_fft itself refuses those)", fn,
+		              what, index, rate, k.nb / 2, k.nb);
+		return MI_ENOTSUP;
+	}
+	return MI_OK;
+}
+
+int mi_plc_create_legs(mi_ctx *c, int nstreams, const int32_t *h_rate, const uint8_t *h_kind, int pitch, mi_plc **out) {
+	MI_CHECK_ARG(c && out && nstreams > 0 && h_rate && h_kind && pitch > 0 && pitch <= 4096 && pitch % 8 == 0);
+	*out = nullptr;
+	int rc;
+	for (int s = 0; s < nstreams; ++s) {
+		if ((rc = mi_plc_check_rate("mi_plc_create", "stream", s, h_rate[s])) != MI_OK) return rc;
+		// a tick is whole 16-byte groups of PCM inside the row, and the row holds one of the three kinds
+		MI_CHECK_ARG(h_rate[s] % 800 == 0 && h_rate[s] / 100 <= pitch && h_kind[s] <= MI_SESSION_PCMU);
+	}
+	if ((rc = c->activate()) != MI_OK) return rc;
+	mi_plc *p = new mi_plc();
+	p->ctx = c, p->nstreams = nstreams, p->cap = pitch, p->legs = true;
+	p->tag.resize((size_t)nstreams), p->rank.resize((size_t)nstreams);
+	std::vector<int32_t> len((size_t)nstreams);
+	for (int s = 0; s < nstreams; ++s) {
+		size_t k = 0;
+		while (k < p->cls.size() && p->cls[k].rate != h_rate[s]) ++k;
+		if (k == p->cls.size()) {
+			if (k == PLC_MAX_CLASSES) {
+				mi::set_error("mi_plc_create: stream %d at %d Hz brings an eighth rate (a bridge's ratios allow seven)", s, h_rate[s]);
+				delete p;
+				return MI_ENOTSUP;
+			}
+			p->cls.emplace_back();
+			class_sizes(h_rate[s], &p->cls[k]);
+		}
+		p->tag[(size_t)s] = (uint8_t)(k | (size_t)h_kind[s] << 4);
+		p->rank[(size_t)s] = p->cls[k].count++;
+		len[(size_t)s] = h_rate[s] / 100;
+		p->in_bytes = std::max(p->in_bytes, mi::round_up((size_t)len[(size_t)s] * (h_kind[s] ? 1 : 2), 16));
+	}
+	for (const PlcClass &k : p->cls) { // the launches are sized for the largest class present
+		p->lds = std::max(p->lds, class_lds(k, p->cap));
+		p->lds_light = std::max(p->lds_light, (sizeof(int16_t) * (2 * (size_t)k.T + 2 * (size_t)p->cap) + 15) & ~(size_t)15);
+	}
+	if (p->lds > 64 * 1024) {
+		mi::set_error("mi_plc_create: %zu bytes of LDS per stream (rows of %d) exceed 64 KB", p->lds, pitch);
+		delete p;
+		return MI_ENOTSUP;
+	}
+	auto fail = [&](int code) {
+		mi_plc_destroy(p);
+		return code;
+	};
+	for (PlcClass &k : p->cls)
+		if ((rc = class_alloc(k)) != MI_OK) return fail(rc);
+	const size_t n = (size_t)nstreams;
+	if (hipMalloc(&p->d_count, sizeof(int)) != hipSuccess || hipMalloc(&p->d_list, sizeof(int) * n) != hipSuccess ||
+	    hipMalloc(&p->d_tag, n) != hipSuccess || hipMalloc(&p->d_rank, 4 * n) != hipSuccess || hipMalloc(&p->d_len, 4 * n) != hipSuccess) {
+		mi::set_error("mi_plc_create: out of device memory");
+		return fail(MI_ENOMEM);
+	}
+	if (hipMemcpy(p->d_tag, p->tag.data(), n, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(p->d_rank, p->rank.data(), 4 * n, hipMemcpyHostToDevice) != hipSuccess ||
+	    hipMemcpy(p->d_len, len.data(), 4 * n, hipMemcpyHostToDevice) != hipSuccess) {
+		mi::set_error("mi_plc_create: table upload failed");
+		return fail(MI_ENODEV);
+	}
+	if ((rc = mi_plc_reset(p, 0, nstreams)) != MI_OK) return fail(rc);
+	*out = p;
+	return MI_OK;
+}
+
+int mi_plc_process_legs(mi_plc *p, const uint8_t *d_in, size_t in_pitch, int16_t *d_pcm, size_t pitch, const uint8_t *d_mode) {
+	MI_CHECK_ARG(p && p->legs && d_in && d_pcm && d_mode);
+	// every load and store of a leg's tick stays inside its row
+	MI_CHECK_ARG(in_pitch % 16 == 0 && in_pitch >= p->in_bytes && pitch % 8 == 0 && pitch >= (size_t)p->cap);
+	int rc;
+	if ((rc = p->ctx->activate()) != MI_OK) return rc;
+	PlcLegsArgs la{};
+	for (size_t k = 0; k < p->cls.size(); ++k) la.cls[k] = class_args(p, p->cls[k], d_pcm, pitch, p->d_len, d_mode);
+	la.tag = p->d_tag, la.rank = p->d_rank, la.in = d_in, la.in_pitch = in_pitch;
+	MI_HIP(hipMemsetAsync(p->d_count, 0, sizeof(int), p->ctx->stream));
+	hipLaunchKernelGGL(plc_list_kernel, dim3((p->nstreams + 255) / 256), dim3(256), 0, p->ctx->stream, la.cls[0]);
+	MI_LAUNCH_CHECK();
+	hipLaunchKernelGGL(plc_legs_received_kernel, dim3((p->nstreams + PLC_LIGHT_WAVES - 1) / PLC_LIGHT_WAVES), dim3(64 * PLC_LIGHT_WAVES),
+	                   p->lds_light * PLC_LIGHT_WAVES, p->ctx->stream, la);
+	MI_LAUNCH_CHECK();
+	const int grid = std::min(p->nstreams, (p->ctx->cu_count > 0 ? p->ctx->cu_count : 256) * 16);
+	hipLaunchKernelGGL(plc_legs_conceal_kernel, dim3(grid), dim3(64), p->lds, p->ctx->stream, la);
+	MI_LAUNCH_CHECK();
+	return MI_OK;
+}
 
 // (mi_warmup, ctx.hip: this unit's code object is loaded when the library is, not under a tick's first launch)
 static const mi::WarmEntry g_warm_plc(reinterpret_cast<const void *>(&plc_list_kernel));
