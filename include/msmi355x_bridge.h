@@ -50,9 +50,20 @@
  * (tests/test_gpu_bridge_concealed.py).  An absent leg (h_present[s] == 0) is concealed at its own rate / 100 samples, then
  * counts as present and is metered on what the concealer made, at its rate, in front of its in_resampler.
  *
+ * Legs at 3/2 and 2/3 of the mix's rate (mi_bridge_create_rational): Speex ultra-wideband and AAC-ELD run at 32 kHz
+ * (msspeex.c:133, aac-eld.c:69), SILK and Opus with a capped playback rate hand out 12 and 24 kHz (msopus.c:434-436), and
+ * plumb_to_conf resamples such a member without asking.  The constructor takes mi_bridge_create_concealed's arguments and
+ * rules, and leg rate : conference rate may also be 3 : 2 or 2 : 3 -- a 32 kHz member of a 48 kHz room, a 24 kHz member of a
+ * 16 kHz one, 12 kHz in 8 kHz.  Legs at 1, 2, 3 or 6 below or above the mix and at 3/2 or 2/3 share one conference and one
+ * launch per tick (bridge_rational_kernel, run only by a bridge with such a leg): the resampler's 3/2 and 2/3 tile-FIR
+ * kernels at quality 3 inside the tick, bit for bit mi_resampler_process_masked in front of and behind mi_mixer_process
+ * (tests/test_gpu_bridge_rational.py).  Rows, MSVolume, absent legs and pins without MI_MIX_OUTPUT as with
+ * mi_bridge_create_endpoints; cfg.plc as with mi_bridge_create_concealed.
+ *
  * Out of scope, on purpose:
- *   - ratios that are no whole number (44.1 kHz; 32 kHz in 48 kHz) and whole ratios other than 2, 3 and 6, in either
- *     direction: refused with MI_ENOTSUP -- mi_session and the MSFilter plugin resample those;
+ *   - ratios that are no whole number other than 3/2 and 2/3 (44.1 kHz; 4/3: 32 kHz in 24 kHz) and whole ratios other than
+ *     2, 3 and 6 (4: 32 kHz in 8 kHz), in either direction: refused with MI_ENOTSUP -- mi_session and the MSFilter plugin
+ *     resample those; 3/2 and 2/3 through the five older constructors, which keep refusing them;
  *   - jitter buffering and flow control: the host's, as with mi_session -- a leg whose packet is missing at the tick is
  *     flagged absent (or concealed, cfg.plc);
  *   - cfg.plc with legs that differ in rate or codec through the four older constructors: they keep refusing it with
@@ -124,6 +135,17 @@ int mi_bridge_create_endpoints(mi_ctx *ctx, const mi_bridge_config *cfg, const m
  * mi_bridge_create_endpoints refuses but for plc; with cfg->plc a leg outside 8 - 48 kHz or one whose concealer needs a
  * transform radix above 17. */
 int mi_bridge_create_concealed(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */, mi_bridge **out);
+/* The same with legs at 3/2 or 2/3 of the mix's rate as well.  The arguments and every rule are mi_bridge_create_concealed's,
+ * and a leg may also have 2 * leg rate == 3 * cfg->rate or 3 * leg rate == 2 * cfg->rate (both rates multiples of 800, as
+ * ever).  h_legs == NULL, or no leg at 3/2 or 2/3: that constructor's bridge exactly, the same kernels, pitch and tick bytes.
+ * With such a leg the host rows are byte rows whether the codecs differ or not, and mi_bridge_reset_streams and
+ * mi_bridge_add_member zero both its resamplers' histories: the 71 samples of the one that runs x 2/3 and the 47 of the one
+ * that runs x 3/2, on whichever side of the pin each sits.  MI_ENOTSUP, the message naming the leg and the value, before
+ * anything is allocated: what mi_bridge_create_concealed refuses but for the two ratios; a ratio that is no whole number and
+ * not 3/2 or 2/3 (44.1 kHz; 4/3); a whole ratio other than 2, 3 and 6; a conference whose rows, sum row and resampler scratch
+ * do not fit the 64 KB of LDS the kernel allows itself (32 kHz legs in a 48 kHz conference: up to 43 members; 24 kHz legs in
+ * a 16 kHz room that also holds 48 kHz members: up to 45). */
+int mi_bridge_create_rational(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */, mi_bridge **out);
 void mi_bridge_destroy(mi_bridge *b);
 int mi_bridge_leg_rate(const mi_bridge *b, int stream); /* the leg's rate in Hz, or MI_EINVAL */
 /* the leg's codecs and its own tick in bytes (rate / 100 x 1 or 2), on any bridge; either pointer may be NULL.
@@ -161,7 +183,7 @@ int mi_bridge_set_controls(mi_bridge *b, const uint8_t *h_flags, const float *h_
  * has no far end to limit against. */
 int mi_bridge_set_volume_params(mi_bridge *b, int first, int count, const mi_volume_params *h_params);
 /* a leg was replaced: the meter (and concealer, and both resamplers' histories -- ratio x 48 - 1 samples on the wider side
- * of the pin, 47 on the other) of streams [first, first + count) start over as new filters would */
+ * of the pin, 47 on the other; 71 and 47 for a leg at 3/2 or 2/3 of the mix) of streams [first, first + count) start over as new filters would */
 int mi_bridge_reset_streams(mi_bridge *b, int first, int count);
 /* MSAudioConference membership (audioconference.c:322-374), as mi_session_add_member / _remove_member: a bridge is
  * created full; remove unplumbs the pin and clears its output row, add plumbs it for a NEW endpoint (fresh meter) */

@@ -886,7 +886,7 @@ class Bridge(_ConferenceBatch):
     _destroy, _prefix = "mi_bridge_destroy", "bridge"
 
     def __init__(self, ctx, nstreams, members=32, rate=8000, in_codec=MI_SESSION_PCMU, out_codec=MI_SESSION_PCMU, plc=False, device=0,
-                 leg_rates=None, legs=None, endpoints=None, concealed=None):
+                 leg_rates=None, legs=None, endpoints=None, concealed=None, rational=None):
         """leg_rates: the rate of every leg's code words or PCM [nstreams] (mi_bridge_create_rated: rate / leg rate in
         {1, 2, 3, 6}); None: every leg at `rate`.
         legs: every leg's (rate, in_codec, out_codec) [nstreams], a sequence of triples or a structured array with those
@@ -895,7 +895,9 @@ class Bridge(_ConferenceBatch):
         endpoints: the same triples for mi_bridge_create_endpoints, where a leg may also be ABOVE `rate` by 2, 3 or 6 (a
         48 kHz member of a 16 kHz conference); byte rows as with legs=, the pitch the widest leg's tick.
         concealed: the same triples for mi_bridge_create_concealed: endpoints= whose plc=True holds for legs of any rate and
-        codec (a concealer per leg behind its own decoder); plc is passed as given, geometry and views are endpoints='."""
+        codec (a concealer per leg behind its own decoder); plc is passed as given, geometry and views are endpoints='.
+        rational: the same triples for mi_bridge_create_rational: concealed= where a leg may also be at 3/2 or 2/3 of `rate`
+        (a 32 kHz member of a 48 kHz conference, a 24 kHz member of a 16 kHz one); geometry and views are endpoints='."""
         self._own_ctx = ctx is None
         self.ctx = ctx = Context(device) if ctx is None else ctx
         cfg = BridgeConfig()
@@ -903,11 +905,12 @@ class Bridge(_ConferenceBatch):
         cfg.nstreams, cfg.members_per_conference, cfg.rate = nstreams, members, rate
         cfg.in_codec, cfg.out_codec, cfg.plc = in_codec, out_codec, int(plc)
         h = C.c_void_p()
-        given = [v for v in (legs, endpoints, concealed) if v is not None]
+        given = [v for v in (legs, endpoints, concealed, rational) if v is not None]
         if given:
-            assert len(given) == 1, "one of legs=, endpoints= and concealed="
+            assert len(given) == 1, "one of legs=, endpoints=, concealed= and rational="
             create = (ctx.L.mi_bridge_create_legs if legs is not None else
-                      ctx.L.mi_bridge_create_endpoints if endpoints is not None else ctx.L.mi_bridge_create_concealed)
+                      ctx.L.mi_bridge_create_endpoints if endpoints is not None else
+                      ctx.L.mi_bridge_create_concealed if concealed is not None else ctx.L.mi_bridge_create_rational)
             lg = np.asarray(given[0])
             if lg.dtype.names:
                 lg = np.stack([lg[k] for k in ("rate", "in_codec", "out_codec")], axis=-1)

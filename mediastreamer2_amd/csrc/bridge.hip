@@ -22,8 +22,9 @@
 //   (D) lane = (member, eight columns), for every pin with its output enabled: saturate(sum - own)
 //       (channel_process_out), stored as 16 bytes of PCM or encoded to 8 code words; consecutive lanes, consecutive bytes.
 // The members are sliced in (C) so that an 80-sample tick, 20 four-column words wide, still occupies 240 lanes.
-// bridge_rated_kernel (legs at their own rate), bridge_legs_kernel (every leg's own codec, with or without the resamplers)
-// and bridge_updown_kernel (legs above the mix as well) further down keep these phases; each says at its head what it adds.
+// bridge_rated_kernel (legs at their own rate), bridge_legs_kernel (every leg's own codec, with or without the resamplers),
+// bridge_updown_kernel (legs above the mix as well) and bridge_rational_kernel (legs at 3/2 and 2/3 of the mix as well) further
+// down keep these phases; each says at its head what it adds.
 //
 // Geometry: an 8 kHz conference of 32 is 5.4 KB of LDS and four waves, so eight such workgroups share a CU (32 waves);
 // 1000 conferences are 1000 workgroups dealt over the 256 CUs, about four per CU = one wave per SIMD and conference
@@ -1107,6 +1108,328 @@ __global__ __launch_bounds__(BT) void bridge_updown_kernel(UpdownArgs ua) {
 	}
 }
 
+// ---- legs at 3/2 and 2/3 of the mix's rate (mi_bridge_create_rational): 32 kHz members of a 48 kHz room, 24 kHz members of
+// a 16 kHz one.  The ratio byte of such a member carries UD_R32 -- "x 3/2" -- with UD_ABOVE still giving the direction: the
+// leg is at 3/2 of the mix with it, at 2/3 without.  Only a bridge with at least one such leg runs this kernel.
+constexpr unsigned UD_R32 = 0x40;
+constexpr int RQ_FT = 24; // taps per lane of the rational resamplers: filt_len / M, 48 / 2 and 72 / 3
+
+struct RationalArgs {
+	UpdownArgs u;
+	// the four rational resamplers' taps, rearranged per (r, p') [L * M][24] (build_tables): of a leg ABOVE the mix the
+	// in_resampler's (x 2/3) and the out_resampler's (x 3/2), of a leg below it the in_resampler's (x 3/2) and the
+	// out_resampler's (x 2/3)
+	int tab_above_in, tab_above_out, tab_below_in, tab_below_out;
+};
+
+// a member's own tick in samples and its rate, from its ratio byte and the conference's
+__host__ __device__ inline int rational_leg(int r, int conf) {
+	if (r & UD_R32) return (r & UD_ABOVE) ? conf / 2 * 3 : conf / 3 * 2;
+	return (r & UD_ABOVE) ? conf * (r & 7) : conf / (r & 7);
+}
+
+// floats per phase array copy of a rational resampler: resample_ratio_kernel's length (history ++ tick split by input phase,
+// + the tile FIR's look-ahead) with plen / 4 odd, as updown_plen and for its reason: lanes (tile, r) and (tile, r + 1) read
+// neighbouring arrays at one offset
+__host__ __device__ inline int rational_plen(int m, int in_len) { return (((RQ_FT * m - 1 + in_len + m - 1) / m + RS_R + 8 + 3) & ~3) | 4; }
+// bytes of a wavefront's scratch for it: two copies of M phase arrays
+__host__ __device__ inline size_t rational_scratch(int m, int in_len) { return (size_t)2 * m * rational_plen(m, in_len) * sizeof(float); }
+
+// One wavefront runs one member's rational resampler, L / M = 3/2 or 2/3: resample_ratio_kernel's arithmetic in its order
+// (resample.hip).  Output n = q * L + r is the sum of M shares p' = 0 .. M - 1 added upward from 0.f, each share fir_tile<24, 8>
+// from a zero accumulator over taps table[(r * M) % L][k * M + p'] -- rearranged on the host: tab [r * M + p'][24] -- and the
+// window X_{u % M}[q + k + u / M], u = (r * M) / L + p', of the input split into M phases and staged twice, the second copy
+// one float early (u / M is 0 or 1 and a window starts on 16 bytes); then rs_word2int.  Lane (tile, r) computes the M shares
+// of its eight outputs one after the other into accumulators of their own and adds them in that order: the bits of the
+// batch kernel's partial-sum array without the array.  The in_len samples at the head of `row` are the input, the
+// in_len / M * L outputs are written back over the row once the whole tick is staged -- the in_resampler in front of a pin
+// as it stands, the out_resampler behind it with updown_store after it.  xp: [2][M][plen] floats.
+template <int L, int M>
+__device__ __forceinline__ void rational_run(float *xp, int16_t *row, int16_t *hist, const float *tab, int in_len, int lane) {
+	constexpr int NT = RQ_FT * M, HIST = NT - 1, HQ = NT / 4;
+	static_assert((L - 1) * M / L + M - 1 < 2 * M, "u / M is 0 or 1: two copies of the phase arrays");
+	const int plen = rational_plen(M, in_len), periods = in_len / M;
+	for (int i = lane; i < 2 * M * plen; i += 64) xp[i] = 0.f;
+	wave_sync();
+	for (int q = lane; q < HQ + (in_len >> 2); q += 64) {
+		const bool h = q < HQ;
+		const short4 v = h ? *reinterpret_cast<const short4 *>(hist + 4 * q) : *reinterpret_cast<const short4 *>(row + 4 * (q - HQ));
+		const int b = h ? 4 * q : HIST + 4 * (q - HQ); // index in history ++ tick
+		const short e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+		for (int k = 0; k < 4; ++k) {
+			const int i = b + k;
+			if (!h || i < HIST) { // the history row's pad slot is not a sample
+				const int ph = i % M, m = i / M;
+				const float f = (float)e[k];
+				xp[ph * plen + m] = f;                       // copy 0
+				if (m >= 1) xp[(M + ph) * plen + m - 1] = f; // copy 1: X_p[m] at m - 1
+			}
+		}
+	}
+	wave_sync(); // the whole tick is staged before the first output lands on the row
+	const int nlanes = L * (periods >> 3);
+	for (int base = 0; base < nlanes; base += 64) {
+		const int l = base + lane;
+		const bool on = l < nlanes;
+		const int tile = on ? l / L : 0, r = on ? l - tile * L : 0;
+		f2 acc2[M][RS_R / 2];
+#pragma unroll
+		for (int pp = 0; pp < M; ++pp) {
+			const int u = (r * M) / L + pp; // copy u / M, phase u % M: array u
+			f2 t2[RQ_FT / 2];
+			const float4 *tp = reinterpret_cast<const float4 *>(tab + (r * M + pp) * RQ_FT);
+#pragma unroll
+			for (int j = 0; j < RQ_FT / 4; ++j) {
+				const float4 w = tp[j];
+				t2[2 * j] = (f2){w.x, w.y}, t2[2 * j + 1] = (f2){w.z, w.w};
+			}
+#pragma unroll
+			for (int q = 0; q < RS_R / 2; ++q) acc2[pp][q] = (f2){0.f, 0.f};
+			fir_tile<RQ_FT, RS_R>(xp + u * plen + tile * RS_R, t2, acc2[pp]);
+		}
+		if (on) {
+#pragma unroll
+			for (int q = 0; q < RS_R / 2; ++q) {
+				float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+				for (int pp = 0; pp < M; ++pp) s0 += acc2[pp][q].x, s1 += acc2[pp][q].y;
+				row[(tile * RS_R + 2 * q) * L + r] = rs_word2int(s0);
+				row[(tile * RS_R + 2 * q + 1) * L + r] = rs_word2int(s1);
+			}
+		}
+	}
+	// new history = the last 24 * M - 1 samples of history ++ tick; the pad slot takes a zero
+	if (lane < HQ) {
+		short4 h;
+		short *hp = &h.x;
+#pragma unroll
+		for (int k = 0; k < 4; ++k) {
+			const int i = in_len + 4 * lane + k;
+			hp[k] = (4 * lane + k < HIST) ? (short)xp[(i % M) * plen + i / M] : (short)0;
+		}
+		*reinterpret_cast<short4 *>(hist + 4 * lane) = h;
+	}
+	wave_sync(); // xp is read out before the wave's next member stages over it
+}
+
+// The phases of bridge_updown_kernel, their arithmetic word for word, with one more flag in a member's ratio byte:
+//   (0) (A) (B) (G) on the leg's own rate / 100 samples at the leg's rate (rational_leg), the row `wide` samples;
+//   (U) one wavefront per member: rated_up / updown_down as there, or for UD_R32 rational_run -- x 2/3 for a leg above the
+//       mix, x 3/2 for one below it -- from the head of the row back over it;
+//   (C) (D) at the conference's rate on the head of the rows;
+//   (W) one wavefront per member: as there, or for UD_R32 rational_run the other way from the head of the row back over the
+//       row (which held the leg's input, so it is wide enough), then updown_store.
+__global__ __launch_bounds__(BT) void bridge_rational_kernel(RationalArgs qa) {
+	extern __shared__ __attribute__((aligned(16))) char smem[];
+	const UpdownArgs &ua = qa.u;
+	const LegsArgs &la = ua.l;
+	const RatedArgs &ra = la.r;
+	const BridgeArgs &a = ra.b;
+	uint2 *rows = reinterpret_cast<uint2 *>(smem);
+	int *s_sum = reinterpret_cast<int *>(smem + a.sum_off);
+	__shared__ int s_pk[BMAX], s_dc[BMAX];
+	__shared__ int4 s_par[BMAX];
+	__shared__ unsigned char s_rt[BMAX], s_on[BMAX], s_cd[BMAX]; // a member's ratio | UD_ABOVE | UD_R32; whether it is here this tick; its codec pair
+	const int t = threadIdx.x, c = blockIdx.x, mm = a.mm, ns = a.ns, nw = ns >> 2, ng = ns >> 3;
+	const int s0 = c * mm;
+	const uint8_t *in = static_cast<const uint8_t *>(a.in);
+	uint8_t *out = static_cast<uint8_t *>(a.out);
+
+	// ---- (0)
+	mi_volume_params p;
+	mi_volume_state st;
+	float2 win = make_float2(0, 0);
+	unsigned mflag = 0;
+	int mgain_bits = 0, rt = 1;
+	bool here = false;
+	if (t < mm) {
+		const int s = s0 + t;
+		p = a.params[s];
+		st = a.state[s];
+		win = a.win[s];
+		mflag = a.flags[s];
+		mgain_bits = __float_as_int(a.gain[s]);
+		here = !a.present || a.present[s] != 0;
+		s_cd[t] = la.codec[s];
+		rt = ra.ratio[s];
+		s_rt[t] = (unsigned char)rt, s_on[t] = here;
+	}
+	for (int i = t; i < ns; i += BT) s_sum[i] = 0;
+
+	// ---- (A) the leg's own groups; the rest of the row is zeros as far as the conference's tick reaches
+	for (int mb = 0; mb < mm; mb += BT / 8) {
+		const int m = mb + (t >> 3), q = t & 7;
+		const bool valid = m < mm;
+		int pk = 0, dc = 0;
+		if (valid) {
+			const bool on = !a.present || a.present[s0 + m] != 0;
+			const int kind = la.codec[s0 + m] & 3, r = ra.ratio[s0 + m];
+			const int ngl = rational_leg(r, ng), nz = max(ng, ngl);
+			const uint8_t *src = in + (size_t)(s0 + m) * la.in_pitch;
+			for (int g0 = q; g0 < nz; g0 += 32) {
+				uint4 v[4];
+#pragma unroll
+				for (int i = 0; i < 4; ++i) { // straight-line loads: all in flight at once
+					v[i] = make_uint4(0, 0, 0, 0);
+					if (on && g0 + 8 * i < ngl) v[i] = load_raw_leg(src, kind, g0 + 8 * i);
+				}
+#pragma unroll
+				for (int i = 0; i < 4; ++i) {
+					const int g = g0 + 8 * i;
+					if (g >= nz) continue;
+					const uint4 d = decode_group_leg(v[i], kind, g);
+					if (on && g < ngl) v[i] = d; // (code bytes of zero are not silence)
+					rows[m * a.row_w + 2 * g] = make_uint2(v[i].x, v[i].y);
+					rows[m * a.row_w + 2 * g + 1] = make_uint2(v[i].z, v[i].w);
+					const unsigned w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+#pragma unroll
+					for (int k = 0; k < 4; ++k) {
+						const int x0 = lo16(w[k]), x1 = hi16(w[k]);
+						pk = max(pk, max(x0 < 0 ? -x0 : x0, x1 < 0 ? -x1 : x1));
+						dc += x0 + x1;
+					}
+				}
+			}
+		}
+#pragma unroll
+		for (int off = 1; off < 8; off <<= 1) {
+			pk = max(pk, __shfl_xor(pk, off));
+			dc += __shfl_xor(dc, off);
+		}
+		if (valid && q == 0) s_pk[m] = pk, s_dc[m] = dc;
+	}
+	__syncthreads();
+
+	// ---- (B) over the leg's rate / 100 samples, at the leg's rate
+	if (t < mm) {
+		if (here) {
+			const uint2 *r = rows + t * a.row_w;
+			const int nwl = rational_leg(rt, nw);
+			float acc = 0;
+#pragma unroll 4
+			for (int i = 0; i < nwl; ++i) {
+				const uint2 w = r[i];
+				const int x0 = lo16(w.x), x1 = hi16(w.x), x2 = lo16(w.y), x3 = hi16(w.y);
+				acc += (float)(x0 * x0);
+				acc += (float)(x1 * x1);
+				acc += (float)(x2 * x2);
+				acc += (float)(x3 * x3);
+			}
+			const VolCtl o = volume_control(p, st, 0.f, acc, 4 * nwl, s_pk[t], s_dc[t], rational_leg(rt, a.sample_rate), win);
+			s_par[t] = make_int4((int)mflag | (o.mode << 8), o.intgain, o.dcoff, mgain_bits);
+			a.state[s0 + t] = st;
+			a.win[s0 + t] = win;
+		} else {
+			s_par[t] = make_int4((int)mflag, 4096, 0, mgain_bits);
+		}
+	}
+	__syncthreads();
+
+	// ---- (G) apply_gain (msvolume.c:440) in front of the in_resampler, on the leg-rate samples
+	const int nww = ua.wide >> 2;
+	for (int item = t; item < mm * nww; item += BT) {
+		const int m = item / nww, j = item - m * nww;
+		const int4 par = s_par[m];
+		const int mode = par.x >> 8;
+		if (mode == 0 || j >= rational_leg(s_rt[m], nw)) continue;
+		const uint2 cur = rows[m * a.row_w + j];
+		int x[4] = {lo16(cur.x), hi16(cur.x), lo16(cur.y), hi16(cur.y)};
+		const int ig = par.y, dc = (mode == 2) ? par.z : 0;
+#pragma unroll
+		for (int k = 0; k < 4; ++k) x[k] = sat16(((x[k] - dc) * ig) / 4096);
+		rows[m * a.row_w + j] = make_uint2(pack16(x[0], x[1]), pack16(x[2], x[3]));
+	}
+	__syncthreads();
+
+	// ---- (U) the in_resampler of a present, plumbed leg; any other keeps its history
+	const int wave = t >> 6, lane = t & 63;
+	float *scr = reinterpret_cast<float *>(smem + ra.scratch_off + wave * ra.scratch_per_wave);
+	for (int m = wave; m < mm; m += BT / 64) {
+		const int r = __builtin_amdgcn_readfirstlane(s_rt[m]), k = r & 7;
+		if (r == 1 || (r & UD_R32) || !s_on[m] || !((unsigned)s_par[m].x & MI_MIX_LINKED)) continue;
+		int16_t *row = reinterpret_cast<int16_t *>(rows + m * a.row_w), *hist = ra.hist_in + (size_t)(s0 + m) * ua.hin_stride;
+		if (r & UD_ABOVE) updown_down(scr, row, hist, ra.tab + ua.tab_down_in[k], k, ns * k, lane);
+		else rated_up(scr, row, hist, ra.tab + ra.tab_up[k], k, ns / k, lane);
+	}
+	// (the legs at 3/2 and 2/3 in a loop of their own: what a helper keeps per lane stays live over its own loop only)
+	for (int m = wave; m < mm; m += BT / 64) {
+		const int r = __builtin_amdgcn_readfirstlane(s_rt[m]);
+		if (!(r & UD_R32) || !s_on[m] || !((unsigned)s_par[m].x & MI_MIX_LINKED)) continue;
+		int16_t *row = reinterpret_cast<int16_t *>(rows + m * a.row_w), *hist = ra.hist_in + (size_t)(s0 + m) * ua.hin_stride;
+		if (r & UD_ABOVE) rational_run<2, 3>(scr, row, hist, ra.tab + qa.tab_above_in, ns / 2 * 3, lane);
+		else rational_run<3, 2>(scr, row, hist, ra.tab + qa.tab_below_in, ns / 3 * 2, lane);
+	}
+	__syncthreads();
+
+	// ---- (C) the gain is in the rows already
+	for (int item = t; item < a.nslice * nw; item += BT) {
+		const int r = item / nw, j = item - r * nw;
+		int sum[4] = {0, 0, 0, 0};
+		for (int m = r; m < mm; m += a.nslice) {
+			const int4 par = s_par[m];
+			const unsigned f = (unsigned)par.x & 0xffu;
+			uint2 o = make_uint2(0, 0);
+			if ((f & MI_MIX_LINKED) && (f & MI_MIX_ACTIVE)) {
+				const uint2 cur = rows[m * a.row_w + j];
+				int x[4] = {lo16(cur.x), hi16(cur.x), lo16(cur.y), hi16(cur.y)};
+				const float gn = __int_as_float(par.w);
+				if (gn != 1.0f) { // channel_process_in's input gain (audiomixer.c:46-51)
+#pragma unroll
+					for (int k = 0; k < 4; ++k) x[k] = sat16((int)(gn * (float)x[k]));
+				}
+#pragma unroll
+				for (int k = 0; k < 4; ++k) sum[k] += x[k];
+				o = make_uint2(pack16(x[0], x[1]), pack16(x[2], x[3]));
+			}
+			rows[m * a.row_w + j] = o;
+		}
+#pragma unroll
+		for (int k = 0; k < 4; ++k) atomicAdd(&s_sum[4 * j + k], sum[k]);
+	}
+	__syncthreads();
+
+	// ---- (D)
+	for (int item = t; item < mm * ng; item += BT) {
+		const int m = item / ng, g = item - m * ng;
+		if (!((unsigned)s_par[m].x & MI_MIX_OUTPUT)) continue;
+		const uint2 own0 = rows[m * a.row_w + 2 * g], own1 = rows[m * a.row_w + 2 * g + 1];
+		const int4 sa = *reinterpret_cast<const int4 *>(s_sum + 8 * g), sb = *reinterpret_cast<const int4 *>(s_sum + 8 * g + 4);
+		const int o[8] = {sat16(sa.x - lo16(own0.x)), sat16(sa.y - hi16(own0.x)), sat16(sa.z - lo16(own0.y)), sat16(sa.w - hi16(own0.y)),
+		                  sat16(sb.x - lo16(own1.x)), sat16(sb.y - hi16(own1.x)), sat16(sb.z - lo16(own1.y)), sat16(sb.w - hi16(own1.y))};
+		if (s_rt[m] != 1) { // the out_resampler's input, either direction
+			rows[m * a.row_w + 2 * g] = make_uint2(pack16(o[0], o[1]), pack16(o[2], o[3]));
+			rows[m * a.row_w + 2 * g + 1] = make_uint2(pack16(o[4], o[5]), pack16(o[6], o[7]));
+			continue;
+		}
+		store_group_leg(out + (size_t)(s0 + m) * la.out_pitch, s_cd[m] >> 2, g, o);
+	}
+	__syncthreads();
+
+	// ---- (W) the out_resampler of a pin with its output on, then the leg's store / encoder
+	for (int m = wave; m < mm; m += BT / 64) {
+		const int r = __builtin_amdgcn_readfirstlane(s_rt[m]), k = r & 7;
+		if (r == 1 || (r & UD_R32) || !((unsigned)s_par[m].x & MI_MIX_OUTPUT)) continue;
+		int16_t *row = reinterpret_cast<int16_t *>(rows + m * a.row_w), *hist = ra.hist_out + (size_t)(s0 + m) * ra.hout_stride;
+		const int kind = __builtin_amdgcn_readfirstlane(s_cd[m] >> 2);
+		const size_t at = (size_t)(s0 + m) * la.out_pitch;
+		if (r & UD_ABOVE) {
+			rated_up(scr, row, hist, ra.tab + ua.tab_up_out[k], k, ns, lane);
+			updown_store(row, out + at, kind, ns * k, lane);
+		} else {
+			rated_down<-1>(scr, row, hist, ra.tab + ra.tab_down[k], out, at, k, ns, lane, kind);
+		}
+	}
+	for (int m = wave; m < mm; m += BT / 64) { // the legs at 3/2 and 2/3, in a loop of their own as in (U)
+		const int r = __builtin_amdgcn_readfirstlane(s_rt[m]);
+		if (!(r & UD_R32) || !((unsigned)s_par[m].x & MI_MIX_OUTPUT)) continue;
+		int16_t *row = reinterpret_cast<int16_t *>(rows + m * a.row_w), *hist = ra.hist_out + (size_t)(s0 + m) * ra.hout_stride;
+		if (r & UD_ABOVE) rational_run<3, 2>(scr, row, hist, ra.tab + qa.tab_above_out, ns, lane);
+		else rational_run<2, 3>(scr, row, hist, ra.tab + qa.tab_below_out, ns, lane);
+		updown_store(row, out + (size_t)(s0 + m) * la.out_pitch, __builtin_amdgcn_readfirstlane(s_cd[m] >> 2), rational_leg(r, ns), lane);
+	}
+}
+
 } // namespace
 
 struct mi_bridge {
@@ -1146,6 +1469,10 @@ struct mi_bridge {
 	// the per-leg concealer (mi_bridge_create_concealed where the legs differ): `plc` is mi_plc_create_legs' and has the
 	// decoders; d_pcm [n][pitch] is what it makes of d_in, d_codec is [2][n] as above
 	bool leg_plc = false;
+	// legs at 3/2 or 2/3 of the mix (mi_bridge_create_rational) where there is one: bridge_rational_kernel.  d_ratio then carries
+	// UD_R32, everything else is held as for `updown`: d_codec always there, rows `wide` samples, both histories one stride
+	bool rational = false;
+	int tab_above_in = 0, tab_above_out = 0, tab_below_in = 0, tab_below_out = 0;
 };
 
 namespace {
@@ -1189,7 +1516,7 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 		ra.pitch = b->pitch, ra.hout_stride = b->hout_stride;
 		ra.scratch_off = b->scratch_off, ra.scratch_per_wave = b->scratch_per_wave;
 	}
-	if (b->updown) {
+	if (b->updown || b->rational) {
 		UpdownArgs ua;
 		ua.l.r = ra;
 		// behind the concealer every leg's input is the PCM it worked on, at the pitch of its rows
@@ -1198,6 +1525,15 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 		ua.wide = b->wide, ua.hin_stride = b->hin_stride;
 		memcpy(ua.tab_down_in, b->tab_down_in, sizeof(ua.tab_down_in));
 		memcpy(ua.tab_up_out, b->tab_up_out, sizeof(ua.tab_up_out));
+		if (b->rational) {
+			RationalArgs qa;
+			qa.u = ua;
+			qa.tab_above_in = b->tab_above_in, qa.tab_above_out = b->tab_above_out;
+			qa.tab_below_in = b->tab_below_in, qa.tab_below_out = b->tab_below_out;
+			hipLaunchKernelGGL(bridge_rational_kernel, grid, dim3(BT), b->lds, b->ctx->stream, qa);
+			MI_LAUNCH_CHECK();
+			return MI_OK;
+		}
 		hipLaunchKernelGGL(bridge_updown_kernel, grid, dim3(BT), b->lds, b->ctx->stream, ua);
 		MI_LAUNCH_CHECK();
 		return MI_OK;
@@ -1250,8 +1586,30 @@ int design_table(mi_ctx *ctx, int in_rate, int out_rate, std::vector<float> &tab
 
 // one table per distinct ratio and direction, built once: ratio r up [r][48] as designed, down [r][48] phase-major
 // (`above`: the ratios of legs above the mix, whose down-sampler is the in_resampler and runs from rate * r)
-int build_tables(mi_bridge *b, const bool (&used)[7], const bool (&above)[7]) {
+// (`r32_above`, `r32_below`: a leg at 3/2 or at 2/3 of the mix; their tables [L][24 * M] rearranged into the rows
+// rational_run's lanes read, [r * M + p'][k] = table[(r * M) % L][k * M + p'])
+int build_tables(mi_bridge *b, const bool (&used)[7], const bool (&above)[7], bool r32_above = false, bool r32_below = false) {
 	std::vector<float> all, t;
+	auto rational = [&](int in_rate, int out_rate, int L, int M, int *off) {
+		const int rc = design_table(b->ctx, in_rate, out_rate, t);
+		if (rc != MI_OK) return rc;
+		if (t.size() != (size_t)L * M * RQ_FT) return (int)MI_ENOTSUP;
+		*off = (int)all.size();
+		for (int r = 0; r < L; ++r)
+			for (int pp = 0; pp < M; ++pp)
+				for (int k = 0; k < RQ_FT; ++k) all.push_back(t[(size_t)((r * M) % L) * RQ_FT * M + (size_t)k * M + pp]);
+		return (int)MI_OK;
+	};
+	const int conf = b->cfg.rate;
+	int qrc;
+	if (r32_above) {
+		if ((qrc = rational(conf / 2 * 3, conf, 2, 3, &b->tab_above_in)) != MI_OK) return qrc;
+		if ((qrc = rational(conf, conf / 2 * 3, 3, 2, &b->tab_above_out)) != MI_OK) return qrc;
+	}
+	if (r32_below) {
+		if ((qrc = rational(conf / 3 * 2, conf, 3, 2, &b->tab_below_in)) != MI_OK) return qrc;
+		if ((qrc = rational(conf, conf / 3 * 2, 2, 3, &b->tab_below_out)) != MI_OK) return qrc;
+	}
 	for (int r = 2; r < 7; ++r) {
 		int rc;
 		if (above[r]) {
@@ -1321,9 +1679,13 @@ int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) 
 // h_codec [nstreams]: in_codec | out_codec << 2 of legs that differ (mi_bridge_create_legs, which has checked them), or null.
 // endpoints: mi_bridge_create_endpoints' rules -- a leg may be above cfg->rate, and h_codec is there whenever one is
 // leg_plc: mi_bridge_create_concealed with cfg->plc and legs that differ -- the concealer is the per-leg one (h_codec is there)
+// rational: mi_bridge_create_rational with a leg at 3/2 or 2/3 of cfg->rate (endpoints' rules besides; h_codec is there)
 static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, const uint8_t *h_codec, mi_bridge **out,
-                         bool endpoints = false, bool leg_plc = false) {
-	const char *fn = leg_plc ? "mi_bridge_create_concealed" : endpoints ? "mi_bridge_create_endpoints" : "mi_bridge_create_rated";
+                         bool endpoints = false, bool leg_plc = false, bool rational = false) {
+	const char *fn = rational ? "mi_bridge_create_rational"
+	                 : leg_plc ? "mi_bridge_create_concealed"
+	                 : endpoints ? "mi_bridge_create_endpoints"
+	                             : "mi_bridge_create_rated";
 	MI_CHECK_ARG(ctx && cfg && out);
 	*out = nullptr;
 	MI_CHECK_ARG(cfg->nstreams > 0 && cfg->members_per_conference > 0 && cfg->members_per_conference <= MI_MIXER_MAX_CHANNELS &&
@@ -1339,12 +1701,28 @@ static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t
 	// ---- the legs' rates: every refusal before anything is allocated
 	bool used[7] = {}, above[7] = {}; // the ratios of legs below the mix, and of legs above it
 	int widest = 0, common = 0, max_ratio = 1;
-	bool rated = false, updown = false;
+	bool rated = false, updown = false, r32_above = false, r32_below = false;
 	if (h_leg_rate) {
 		for (int s = 0; s < cfg->nstreams; ++s) {
 			const int lr = h_leg_rate[s];
 			MI_CHECK_ARG(lr > 0);
 			const bool up = lr > cfg->rate;
+			// 3/2 or 2/3, both rates multiples of 800: leg and mix are 2400 k and 1600 k Hz, their ticks 24 k and 16 k samples --
+			// 8 k periods of 3 samples against 2: whole periods and whole eight-period tiles, eight-sample groups, both ways
+			if (rational && ((int64_t)2 * lr == (int64_t)3 * cfg->rate || (int64_t)3 * lr == (int64_t)2 * cfg->rate)) {
+				if (lr % 800 != 0) {
+					mi::set_error("%s: leg %d's rate %d is no multiple of 800 (a 10 ms tick must be whole groups of 8 samples)", fn, s, lr);
+					return MI_ENOTSUP;
+				}
+				if (cfg->plc && !leg_plc && common && lr != common) {
+					mi::set_error("%s: plc with legs at %d Hz and %d Hz: the concealer batch has one rate", fn, common, lr);
+					return MI_ENOTSUP;
+				}
+				if (!common) common = lr;
+				(up ? r32_above : r32_below) = true;
+				widest = std::max(widest, lr);
+				continue;
+			}
 			if (up && !endpoints) {
 				mi::set_error("mi_bridge_create_rated: leg %d at %d Hz is above its conference's %d Hz (only legs at or below the mix are resampled)",
 				              s, lr, cfg->rate);
@@ -1352,13 +1730,14 @@ static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t
 			}
 			const int hi = up ? lr : cfg->rate, lo = up ? cfg->rate : lr;
 			if (hi % lo != 0) {
-				mi::set_error("%s: leg %d at %d Hz in a %d Hz conference is no whole ratio (%.3f); supported: 1, 2, 3, 6", fn, s, lr, cfg->rate,
-				              (double)hi / lo);
+				mi::set_error("%s: leg %d at %d Hz in a %d Hz conference is no whole ratio (%.3f); supported: 1, 2, 3, 6%s", fn, s, lr, cfg->rate,
+				              (double)hi / lo, rational ? ", and 3/2 either way" : "");
 				return MI_ENOTSUP;
 			}
 			const int r = hi / lo;
 			if (r != 1 && r != 2 && r != 3 && r != 6) {
-				mi::set_error("%s: leg %d at %d Hz in a %d Hz conference is ratio %d; supported: 1, 2, 3, 6", fn, s, lr, cfg->rate, r);
+				mi::set_error("%s: leg %d at %d Hz in a %d Hz conference is ratio %d; supported: 1, 2, 3, 6%s", fn, s, lr, cfg->rate, r,
+				              rational ? ", and 3/2 either way" : "");
 				return MI_ENOTSUP;
 			}
 			if (lr % 800 != 0) {
@@ -1375,9 +1754,11 @@ static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t
 			widest = std::max(widest, lr);
 			max_ratio = std::max(max_ratio, r);
 		}
-		rated = max_ratio > 1;
+		rated = max_ratio > 1 || r32_above || r32_below;
 	}
-	const int wide = updown ? widest / 100 : len;  // samples per row in LDS: the widest leg's tick where one is above the mix
+	rational = r32_above || r32_below; // without such a leg: mi_bridge_create_concealed's bridge exactly
+	// samples per row in LDS: the widest leg's tick where one is above the mix
+	const int wide = updown ? widest / 100 : rational ? std::max(len, widest / 100) : len;
 	const int row_w = (wide >> 2) | 1;             // 8-byte words per row, odd
 	const size_t sum_off = mi::round_up((size_t)mm * row_w * 8, 16);
 	size_t lds = sum_off + (size_t)len * 4, scratch_off = 0, scratch = 0;
@@ -1396,12 +1777,17 @@ static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t
 			}
 			scratch = std::max(scratch, mi::round_up(std::max(up, down), 16));
 		}
+		// a leg at 3/2 of the mix: x 2/3 from its tick in front of the pin, x 3/2 from the mix's behind it; one at 2/3: x 3/2 from
+		// its tick, x 2/3 from the mix's
+		if (r32_above) scratch = std::max(scratch, std::max(rational_scratch(3, len / 2 * 3), rational_scratch(2, len)));
+		if (r32_below) scratch = std::max(scratch, std::max(rational_scratch(2, len / 3 * 2), rational_scratch(3, len)));
 		scratch_off = mi::round_up(lds, 16);
 		lds = scratch_off + (BT / 64) * scratch;
 		if (lds + RATED_STATIC_LDS > BRIDGE_LDS_MAX) {
 			mi::set_error("%s: a conference's tick and its resamplers' scratch must fit %zu bytes of LDS (%d members x %d samples "
-			              "= %zu, + %d wavefronts x %zu for ratio %d, + %zu of the kernel's own: %zu)",
-			              fn, BRIDGE_LDS_MAX, mm, wide, scratch_off, BT / 64, scratch, max_ratio, RATED_STATIC_LDS, lds + RATED_STATIC_LDS);
+			              "= %zu, + %d wavefronts x %zu for ratio %d%s, + %zu of the kernel's own: %zu)",
+			              fn, BRIDGE_LDS_MAX, mm, wide, scratch_off, BT / 64, scratch, max_ratio, rational ? " and 3/2" : "", RATED_STATIC_LDS,
+			              lds + RATED_STATIC_LDS);
 			return MI_ENOTSUP;
 		}
 	} else if (lds > BRIDGE_LDS_MAX) {
@@ -1434,6 +1820,7 @@ static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t
 	b->nslice = std::max(1, std::min(mm, BT / (len >> 2)));
 	b->rated = rated, b->pitch = pitch;
 	b->updown = updown, b->wide = wide;
+	b->rational = rational;
 	b->in_bytes = in_bytes, b->out_bytes = out_bytes;
 	if (h_leg_rate) b->leg_rate.assign(h_leg_rate, h_leg_rate + cfg->nstreams);
 	b->roster.init(b->n, mm);
@@ -1461,17 +1848,21 @@ static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t
 	if (rated) {
 		b->scratch_off = (int)scratch_off, b->scratch_per_wave = (int)scratch;
 		b->hout_stride = max_ratio * RS_FILT; // mi_resampler's round_up(filt_len - 1, 8) of the longest filter
-		if (updown) b->hin_stride = b->hout_stride; // a down-sampler's history on either side of the pin
+		if (rational) b->hout_stride = std::max(b->hout_stride, 3 * RQ_FT); // x 2/3 keeps 71 samples (x 3/2: 47)
+		if (updown || rational) b->hin_stride = b->hout_stride; // a down-sampler's history on either side of the pin
 		std::vector<uint8_t> ratio(n);
-		for (size_t s = 0; s < n; ++s)
-			ratio[s] = h_leg_rate[s] > cfg->rate ? (uint8_t)(UD_ABOVE | (unsigned)(h_leg_rate[s] / cfg->rate)) : (uint8_t)(cfg->rate / h_leg_rate[s]);
+		for (size_t s = 0; s < n; ++s) {
+			const int lr = h_leg_rate[s];
+			ratio[s] = lr > cfg->rate ? (uint8_t)(UD_ABOVE | (unsigned)(lr / cfg->rate)) : (uint8_t)(cfg->rate / lr);
+			if ((int64_t)2 * lr == (int64_t)3 * cfg->rate || (int64_t)3 * lr == (int64_t)2 * cfg->rate) ratio[s] |= UD_R32; // (the whole part: 1)
+		}
 		b->d_ratio = (uint8_t *)mi_dev_alloc(ctx, n);
 		b->d_hist_in = (int16_t *)mi_dev_alloc(ctx, n * b->hin_stride * sizeof(int16_t));
 		b->d_hist_out = (int16_t *)mi_dev_alloc(ctx, n * b->hout_stride * sizeof(int16_t));
 		if (!b->d_ratio || !b->d_hist_in || !b->d_hist_out) return fail(MI_ENOMEM);
 		if (hipMemcpy(b->d_ratio, ratio.data(), n, hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
 		if ((rc = reset_resamplers(b, 0, b->n)) != MI_OK) return fail(rc);
-		if ((rc = build_tables(b, used, above)) != MI_OK) return fail(rc);
+		if ((rc = build_tables(b, used, above, r32_above, r32_below)) != MI_OK) return fail(rc);
 	}
 	if (h_codec) {
 		b->leg_codec.assign(h_codec, h_codec + n);
@@ -1513,9 +1904,10 @@ int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32
 
 // mi_bridge_create_legs and mi_bridge_create_endpoints: the legs' codecs checked, then create_bridge with the first's rules on
 // rates or the second's.  concealed: mi_bridge_create_concealed -- the second's rules, and cfg->plc with legs that differ is
-// served by the per-leg concealer instead of refused
+// served by the per-leg concealer instead of refused.  rational: mi_bridge_create_rational -- the third's rules, and a leg may
+// be at 3/2 or 2/3 of cfg->rate
 static int create_from_legs(const char *fn, bool endpoints, mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs,
-                            mi_bridge **out, bool concealed = false) {
+                            mi_bridge **out, bool concealed = false, bool rational = false) {
 	if (!h_legs) return mi_bridge_create(ctx, cfg, out);
 	MI_CHECK_ARG(ctx && cfg && out);
 	*out = nullptr;
@@ -1537,6 +1929,8 @@ static int create_from_legs(const char *fn, bool endpoints, mi_ctx *ctx, const m
 		codec[s] = (uint8_t)(l.in_codec | l.out_codec << 2);
 		if (differs < 0 && codec[s] != codec[0]) differs = (int)s;
 		above |= l.rate > cfg->rate;
+		// (such a leg brings the codecs as data and byte rows, as one above the mix does)
+		if (rational) above |= (int64_t)3 * l.rate == (int64_t)2 * cfg->rate;
 	}
 	if (concealed && cfg->plc) {
 		bool one_rate = true;
@@ -1548,7 +1942,7 @@ static int create_from_legs(const char *fn, bool endpoints, mi_ctx *ctx, const m
 		if (differs >= 0 || !one_rate) {
 			mi_bridge_config c = *cfg; // (its pair is not read: the codecs are the kernel's data)
 			c.in_codec = h_legs[0].in_codec, c.out_codec = h_legs[0].out_codec;
-			return create_bridge(ctx, &c, rate.data(), codec.data(), out, true, true);
+			return create_bridge(ctx, &c, rate.data(), codec.data(), out, true, true, rational);
 		}
 	}
 	if (differs >= 0 && cfg->plc) {
@@ -1561,7 +1955,7 @@ static int create_from_legs(const char *fn, bool endpoints, mi_ctx *ctx, const m
 	c.in_codec = h_legs[0].in_codec, c.out_codec = h_legs[0].out_codec;
 	// with a leg above the mix (endpoints; create_bridge refuses it otherwise) the codecs are the kernel's data whether they
 	// differ or not, and the host rows byte rows
-	return create_bridge(ctx, &c, rate.data(), differs >= 0 || (endpoints && above) ? codec.data() : nullptr, out, endpoints);
+	return create_bridge(ctx, &c, rate.data(), differs >= 0 || (endpoints && above) ? codec.data() : nullptr, out, endpoints, false, rational);
 }
 
 int mi_bridge_create_legs(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
@@ -1574,6 +1968,10 @@ int mi_bridge_create_endpoints(mi_ctx *ctx, const mi_bridge_config *cfg, const m
 
 int mi_bridge_create_concealed(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
 	return create_from_legs("mi_bridge_create_concealed", true, ctx, cfg, h_legs, out, true);
+}
+
+int mi_bridge_create_rational(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
+	return create_from_legs("mi_bridge_create_rational", true, ctx, cfg, h_legs, out, true, true);
 }
 
 int mi_bridge_leg_codec(const mi_bridge *b, int stream, int *in_codec, int *out_codec) {
