@@ -905,13 +905,12 @@ class Bridge(_ConferenceBatch):
         cfg.nstreams, cfg.members_per_conference, cfg.rate = nstreams, members, rate
         cfg.in_codec, cfg.out_codec, cfg.plc = in_codec, out_codec, int(plc)
         h = C.c_void_p()
-        given = [v for v in (legs, endpoints, concealed, rational) if v is not None]
+        by_leg = {"mi_bridge_create_legs": legs, "mi_bridge_create_endpoints": endpoints, "mi_bridge_create_concealed": concealed,
+                  "mi_bridge_create_rational": rational}
+        given = [(getattr(ctx.L, entry), v) for entry, v in by_leg.items() if v is not None]
         if given:
             assert len(given) == 1, "one of legs=, endpoints=, concealed= and rational="
-            create = (ctx.L.mi_bridge_create_legs if legs is not None else
-                      ctx.L.mi_bridge_create_endpoints if endpoints is not None else
-                      ctx.L.mi_bridge_create_concealed if concealed is not None else ctx.L.mi_bridge_create_rational)
-            lg = np.asarray(given[0])
+            create, lg = given[0][0], np.asarray(given[0][1])
             if lg.dtype.names:
                 lg = np.stack([lg[k] for k in ("rate", "in_codec", "out_codec")], axis=-1)
             lg = np.ascontiguousarray(lg, np.int32)

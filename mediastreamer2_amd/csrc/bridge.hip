@@ -47,8 +47,6 @@
 namespace {
 
 constexpr int SLOTS = 3; // upload | compute | download can each hold a different tick
-constexpr size_t BRIDGE_LDS_MAX = 64 * 1024;
-constexpr size_t RATED_STATIC_LDS = 2048; // bound on a kernel's static LDS (tests/test_bridge_rates_cpu.py holds it)
 
 // every leg at the conference's rate, one compile-time codec pair (mi_bridge_create): (0) (A) (B) (C) with the gain (D).
 // (0) (A) (B) stand written out here, word for word load_member / stage_rows / meter at F_SAME with FixedSrc<IN>: composed from
@@ -284,47 +282,27 @@ __global__ __launch_bounds__(BT) void bridge_rational_kernel(RationalArgs qa) {
 
 } // namespace
 
+// The host side is plan / build / tick: plan_bridge (bridge_plan.hpp, no HIP in it) decides everything from the configuration
+// or refuses; build_bridge allocates what the plan says and fills the kernels' arguments; a tick sets three pointers and
+// launches the plan's kernel family.
 struct mi_bridge {
 	mi_ctx *ctx = nullptr;
-	mi_bridge_config cfg;
-	int n = 0, nconf = 0, mm = 0, len = 0;
-	size_t in_bytes = 0, out_bytes = 0; // per stream and tick, on the host side
-	int row_w = 0, nslice = 0, sum_off = 0;
-	size_t lds = 0;
+	Plan plan;              // what creation decided: geometry, family, the legs' rates, codecs and ratio bytes
+	RationalArgs args = {}; // the widest kernel's arguments, filled at creation (fill_args, build_tables) but for in, present, out
 	mi_volume *vol = nullptr; // the meters: parameters, state, one-second windows
 	mi_mixer *mix = nullptr;  // the pins' controls
-	mi_plc *plc = nullptr;
+	mi_plc *plc = nullptr;    // plan.leg_plc: mi_plc_create_legs', with the decoders; else mi_plc_create's at the legs' one rate
 	mi::TickPipe pipe;
 	uint8_t *h_in[SLOTS] = {}, *h_present[SLOTS] = {}, *h_ev[SLOTS] = {}, *h_out[SLOTS] = {};
 	uint8_t *d_in[SLOTS] = {}, *d_present[SLOTS] = {}, *d_ev[SLOTS] = {}, *d_out[SLOTS] = {};
-	int16_t *d_pcm = nullptr; // plc behind a decoder: the decoded rows the concealer edits
+	int16_t *d_pcm = nullptr; // plc behind a decoder: the decoded rows [n][pitch] the concealer edits
 	int32_t *d_evlen = nullptr;
 	mi::Roster roster;
-	// legs at their own rate (mi_bridge_create_rated); a same-rate bridge has none of it and pitch == len
-	bool rated = false;
-	int pitch = 0;                 // samples per row of the host buffers: the widest leg's tick
-	std::vector<int32_t> leg_rate; // [n], empty: every leg at cfg.rate
+	// with resamplers (plan.rated): the ratio bytes, both histories at the plan's strides, every table back to back
 	uint8_t *d_ratio = nullptr;
 	int16_t *d_hist_in = nullptr, *d_hist_out = nullptr;
 	float *d_tab = nullptr;
-	int tab_up[7] = {}, tab_down[7] = {};
-	int hout_stride = 0, scratch_off = 0, scratch_per_wave = 0;
-	// every leg's own codec (mi_bridge_create_legs) where the legs differ: in_bytes / out_bytes are the byte rows' pitch
-	std::vector<uint8_t> leg_codec; // [n] in_codec | out_codec << 2; empty: cfg's pair on every leg
-	uint8_t *d_codec = nullptr;
-	// endpoints on either side of the mix (mi_bridge_create_endpoints) with a leg ABOVE it: bridge_updown_kernel.  d_ratio then
-	// carries UD_ABOVE, d_codec is there whether the legs differ or not ([2][n] with plc: the second row names PCM in)
-	bool updown = false;
-	int wide = 0;                  // samples per LDS row: the widest leg's tick
-	int hin_stride = RS_FILT;      // samples per member of d_hist_in
-	int tab_down_in[7] = {}, tab_up_out[7] = {};
-	// the per-leg concealer (mi_bridge_create_concealed where the legs differ): `plc` is mi_plc_create_legs' and has the
-	// decoders; d_pcm [n][pitch] is what it makes of d_in, d_codec is [2][n] as above
-	bool leg_plc = false;
-	// legs at 3/2 or 2/3 of the mix (mi_bridge_create_rational) where there is one: bridge_rational_kernel.  d_ratio then carries
-	// UD_R32, everything else is held as for `updown`: d_codec always there, rows `wide` samples, both histories one stride
-	bool rational = false;
-	int tab_above_in = 0, tab_above_out = 0, tab_below_in = 0, tab_below_out = 0;
+	uint8_t *d_codec = nullptr; // the codecs as data ([n]; [2][n] with plc: the second row names PCM in, behind the concealer)
 };
 
 namespace {
@@ -335,69 +313,60 @@ void (*const TICK_KERNELS[3][3])(BridgeArgs) = CODEC_TABLE(bridge_tick_kernel);
 void (*const RATED_KERNELS[3][3])(RatedArgs) = CODEC_TABLE(bridge_rated_kernel);
 #undef CODEC_TABLE
 
-// a tick's arguments: what a bridge does not have (no resamplers, no codec rows) stays zero and is not read by its kernel
-RationalArgs tick_args(const mi_bridge *b, int slot, const void *in, const uint8_t *present) {
-	RationalArgs qa = {};
-	UpdownArgs &ua = qa.u;
-	LegsArgs &la = ua.l;
+// every argument that holds from creation on; what a bridge does not have (no resamplers, no codec rows) stays zero and is not
+// read by its kernel.  The meters' and the pins' pointers are among them: mi_volume_view and mi_mixer_view hand out arrays that
+// mi_volume_create / mi_mixer_create allocate and only their destroy frees; no setter reallocates them.
+void fill_args(mi_bridge *b) {
+	const Plan &pl = b->plan;
+	LegsArgs &la = b->args.u.l;
 	RatedArgs &ra = la.r;
 	BridgeArgs &a = ra.b;
 	VolumeView vv;
 	MixerView mv;
 	mi_volume_view(b->vol, &vv);
 	mi_mixer_view(b->mix, &mv);
-	a.in = in, a.present = present, a.out = b->d_out[slot];
 	a.params = vv.params, a.state = vv.state, a.win = vv.win;
 	a.flags = mv.flags, a.gain = mv.gain;
-	a.mm = b->mm, a.ns = b->len, a.row_w = b->row_w, a.nslice = b->nslice, a.sum_off = b->sum_off;
-	a.sample_rate = b->cfg.rate;
+	a.mm = pl.mm, a.ns = pl.len, a.row_w = pl.row_w, a.nslice = pl.nslice, a.sum_off = pl.sum_off, a.sample_rate = pl.cfg.rate;
 	ra.ratio = b->d_ratio, ra.hist_in = b->d_hist_in, ra.hist_out = b->d_hist_out, ra.tab = b->d_tab;
-	memcpy(ra.tab_up, b->tab_up, sizeof(ra.tab_up));
-	memcpy(ra.tab_down, b->tab_down, sizeof(ra.tab_down));
-	ra.pitch = b->pitch, ra.hout_stride = b->hout_stride;
-	ra.scratch_off = b->scratch_off, ra.scratch_per_wave = b->scratch_per_wave;
+	ra.pitch = pl.pitch, ra.hout_stride = pl.hout_stride, ra.scratch_off = pl.scratch_off, ra.scratch_per_wave = pl.scratch_per_wave;
 	if (b->d_codec) { // behind the concealer every leg's input is the PCM it worked on, at the pitch of its rows
-		la.codec = b->plc ? b->d_codec + b->n : b->d_codec;
-		la.in_pitch = b->plc ? b->pitch * 2 : (int)b->in_bytes, la.out_pitch = (int)b->out_bytes;
+		la.codec = b->plc ? b->d_codec + pl.n : b->d_codec;
+		la.in_pitch = b->plc ? pl.pitch * 2 : (int)pl.in_bytes, la.out_pitch = (int)pl.out_bytes;
 	}
-	ua.wide = b->wide, ua.hin_stride = b->hin_stride;
-	memcpy(ua.tab_down_in, b->tab_down_in, sizeof(ua.tab_down_in));
-	memcpy(ua.tab_up_out, b->tab_up_out, sizeof(ua.tab_up_out));
-	qa.tab_above_in = b->tab_above_in, qa.tab_above_out = b->tab_above_out;
-	qa.tab_below_in = b->tab_below_in, qa.tab_below_out = b->tab_below_out;
-	return qa;
+	b->args.u.wide = pl.wide, b->args.u.hin_stride = pl.hin_stride;
 }
 
 int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's stream
-	const mi_bridge_config &cf = b->cfg;
+	const Plan &pl = b->plan;
+	const mi_bridge_config &cf = pl.cfg;
 	int rc, in_kind = cf.in_codec;
-	const void *in = b->d_in[slot];
-	const uint8_t *present = b->d_present[slot];
-	if (b->leg_plc) { // every leg's decoder and MSGenericPLC in the concealer's three launches: byte rows in, PCM rows out
-		if ((rc = mi_plc_process_legs(b->plc, b->d_in[slot], b->in_bytes, b->d_pcm, (size_t)b->pitch, b->d_ev[slot])) != MI_OK) return rc;
-		in = b->d_pcm, present = nullptr; // a concealed leg counts as present
+	RationalArgs qa = b->args; // each kernel is passed the part that is its own
+	BridgeArgs &a = qa.u.l.r.b;
+	a.in = b->d_in[slot], a.present = b->d_present[slot], a.out = b->d_out[slot];
+	if (pl.leg_plc) { // every leg's decoder and MSGenericPLC in the concealer's three launches: byte rows in, PCM rows out
+		if ((rc = mi_plc_process_legs(b->plc, b->d_in[slot], pl.in_bytes, b->d_pcm, (size_t)pl.pitch, b->d_ev[slot])) != MI_OK) return rc;
+		a.in = b->d_pcm, a.present = nullptr; // a concealed leg counts as present
 	} else if (b->plc) { // MSAlawDec / MSUlawDec as a launch of its own, then MSGenericPLC on the PCM rows, in place
 		int16_t *rows = reinterpret_cast<int16_t *>(b->d_in[slot]);
 		if (cf.in_codec) {
-			if ((rc = mi_g711_decode(b->ctx, cf.in_codec == MI_SESSION_PCMA ? MI_LAW_PCMA : MI_LAW_PCMU, b->d_in[slot], b->in_bytes, b->d_pcm,
-			                         (size_t)b->pitch, nullptr, b->pitch, (size_t)b->n)) != MI_OK)
+			if ((rc = mi_g711_decode(b->ctx, cf.in_codec == MI_SESSION_PCMA ? MI_LAW_PCMA : MI_LAW_PCMU, b->d_in[slot], pl.in_bytes, b->d_pcm,
+			                         (size_t)pl.pitch, nullptr, pl.pitch, (size_t)pl.n)) != MI_OK)
 				return rc;
 			rows = b->d_pcm;
 		}
-		if ((rc = mi_plc_process(b->plc, rows, (size_t)b->pitch, b->d_evlen, b->d_ev[slot])) != MI_OK) return rc;
-		in = rows, in_kind = MI_SESSION_PCM16, present = nullptr; // a concealed leg counts as present
+		if ((rc = mi_plc_process(b->plc, rows, (size_t)pl.pitch, b->d_evlen, b->d_ev[slot])) != MI_OK) return rc;
+		a.in = rows, in_kind = MI_SESSION_PCM16, a.present = nullptr; // a concealed leg counts as present
 	}
-	// the widest kernel's arguments, filled once; each kernel is passed the part that is its own
-	const RationalArgs qa = tick_args(b, slot, in, present);
-	const UpdownArgs &ua = qa.u;
-	const LegsArgs &la = ua.l;
-	const RatedArgs &ra = la.r;
-	auto launch = [&](auto kernel, const auto &args) { hipLaunchKernelGGL(kernel, dim3((unsigned)b->nconf), dim3(BT), b->lds, b->ctx->stream, args); };
-	if (b->rational) launch(bridge_rational_kernel, qa);
-	else if (b->updown) launch(bridge_updown_kernel, ua);
-	else if (b->d_codec) launch(b->rated ? bridge_legs_kernel<true> : bridge_legs_kernel<false>, la);
-	else if (b->rated) launch(RATED_KERNELS[in_kind][cf.out_codec], ra);
-	else launch(TICK_KERNELS[in_kind][cf.out_codec], ra.b);
+	auto launch = [&](auto kernel, const auto &args) { hipLaunchKernelGGL(kernel, dim3((unsigned)pl.nconf), dim3(BT), pl.lds, b->ctx->stream, args); };
+	switch (pl.family) {
+	case Plan::RATIONAL: launch(bridge_rational_kernel, qa); break;
+	case Plan::UPDOWN: launch(bridge_updown_kernel, qa.u); break;
+	case Plan::LEGS_RATED: launch(bridge_legs_kernel<true>, qa.u.l); break;
+	case Plan::LEGS: launch(bridge_legs_kernel<false>, qa.u.l); break;
+	case Plan::RATED: launch(RATED_KERNELS[in_kind][cf.out_codec], qa.u.l.r); break;
+	case Plan::TICK: launch(TICK_KERNELS[in_kind][cf.out_codec], a); break;
+	}
 	MI_LAUNCH_CHECK();
 	return MI_OK;
 }
@@ -405,10 +374,11 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 // ---- the resamplers' state, next to the meters' (conference.hpp): a NEW endpoint brings new resamplers, their histories
 // zero as speex_resampler_init leaves them.  On the context's stream, behind the ticks submitted.
 int reset_resamplers(mi_bridge *b, int first, int count) {
-	if (!b->rated || count == 0) return MI_OK;
+	const Plan &pl = b->plan;
+	if (!pl.rated || count == 0) return MI_OK;
 	if (b->ctx->activate() != MI_OK) return MI_ENODEV;
-	MI_HIP(hipMemsetAsync(b->d_hist_in + (size_t)first * b->hin_stride, 0, (size_t)count * b->hin_stride * sizeof(int16_t), b->ctx->stream));
-	MI_HIP(hipMemsetAsync(b->d_hist_out + (size_t)first * b->hout_stride, 0, (size_t)count * b->hout_stride * sizeof(int16_t), b->ctx->stream));
+	MI_HIP(hipMemsetAsync(b->d_hist_in + (size_t)first * pl.hin_stride, 0, (size_t)count * pl.hin_stride * sizeof(int16_t), b->ctx->stream));
+	MI_HIP(hipMemsetAsync(b->d_hist_out + (size_t)first * pl.hout_stride, 0, (size_t)count * pl.hout_stride * sizeof(int16_t), b->ctx->stream));
 	return MI_OK;
 }
 
@@ -423,55 +393,55 @@ int design_table(mi_ctx *ctx, int in_rate, int out_rate, std::vector<float> &tab
 	return MI_OK;
 }
 
-// one table per distinct ratio and direction, built once: ratio r up [r][48] as designed, down [r][48] phase-major
-// (`above`: the ratios of legs above the mix, whose down-sampler is the in_resampler and runs from rate * r)
-// (`r32_above`, `r32_below`: a leg at 3/2 or at 2/3 of the mix; their tables [L][24 * M] rearranged into the rows
-// rational_run's lanes read, [r * M + p'][k] = table[(r * M) % L][k * M + p'])
-int build_tables(mi_bridge *b, const bool (&used)[7], const bool (&above)[7], bool r32_above = false, bool r32_below = false) {
-	std::vector<float> all, t;
-	auto rational = [&](int in_rate, int out_rate, int L, int M, int *off) {
-		const int rc = design_table(b->ctx, in_rate, out_rate, t);
-		if (rc != MI_OK) return rc;
-		if (t.size() != (size_t)L * M * RQ_FT) return (int)MI_ENOTSUP;
-		*off = (int)all.size();
-		for (int r = 0; r < L; ++r)
-			for (int pp = 0; pp < M; ++pp)
-				for (int k = 0; k < RQ_FT; ++k) all.push_back(t[(size_t)((r * M) % L) * RQ_FT * M + (size_t)k * M + pp]);
-		return (int)MI_OK;
-	};
-	const int conf = b->cfg.rate;
-	int qrc;
-	if (r32_above) {
-		if ((qrc = rational(conf / 2 * 3, conf, 2, 3, &b->tab_above_in)) != MI_OK) return qrc;
-		if ((qrc = rational(conf, conf / 2 * 3, 3, 2, &b->tab_above_out)) != MI_OK) return qrc;
+// one table per distinct ratio and direction, built once and back to back in d_tab, its float offset noted in b->args.  A table
+// is designed as [L][taps] polyphase rows for in_rate : out_rate = M : L and laid out as its reader wants it: AS_DESIGNED, an
+// up-sampler by r: [r][48]; PHASE_MAJOR, a down-sampler by r: tap r * i + p at [p][i]; REARRANGED, x 3/2 and x 2/3: [L][24 * M]
+// into the rows rational_run's lanes read, [r * M + p'][k] = table[(r * M) % L][k * M + p'].  size: the floats mi_resampler
+// designs; anything else is a design this unit was not written for
+enum Layout { AS_DESIGNED, PHASE_MAJOR, REARRANGED };
+struct Table { int in_rate, out_rate; size_t size; Layout layout; int *offset; };
+
+int build_tables(mi_bridge *b) {
+	const Plan &pl = b->plan;
+	UpdownArgs &ua = b->args.u;
+	RatedArgs &ra = ua.l.r;
+	const int conf = pl.cfg.rate;
+	std::vector<Table> want;
+	if (pl.r32_above) { // the in_resampler's, then the out_resampler's
+		want.push_back({conf / 2 * 3, conf, 6 * RQ_FT, REARRANGED, &b->args.tab_above_in});
+		want.push_back({conf, conf / 2 * 3, 6 * RQ_FT, REARRANGED, &b->args.tab_above_out});
 	}
-	if (r32_below) {
-		if ((qrc = rational(conf / 3 * 2, conf, 3, 2, &b->tab_below_in)) != MI_OK) return qrc;
-		if ((qrc = rational(conf, conf / 3 * 2, 2, 3, &b->tab_below_out)) != MI_OK) return qrc;
+	if (pl.r32_below) {
+		want.push_back({conf / 3 * 2, conf, 6 * RQ_FT, REARRANGED, &b->args.tab_below_in});
+		want.push_back({conf, conf / 3 * 2, 6 * RQ_FT, REARRANGED, &b->args.tab_below_out});
 	}
 	for (int r = 2; r < 7; ++r) {
-		int rc;
-		if (above[r]) {
-			if ((rc = design_table(b->ctx, b->cfg.rate * r, b->cfg.rate, t)) != MI_OK) return rc;
-			if (t.size() != (size_t)r * RS_FILT) return MI_ENOTSUP;
-			b->tab_down_in[r] = (int)all.size();
-			for (int p = 0; p < r; ++p)
-				for (int i = 0; i < RS_FILT; ++i) all.push_back(t[(size_t)i * r + p]);
-			if ((rc = design_table(b->ctx, b->cfg.rate, b->cfg.rate * r, t)) != MI_OK) return rc;
-			if (t.size() != (size_t)r * RS_FILT) return MI_ENOTSUP;
-			b->tab_up_out[r] = (int)all.size();
-			all.insert(all.end(), t.begin(), t.end());
+		const size_t size = (size_t)r * RS_FILT;
+		if (pl.above[r]) { // (whose down-sampler is the in_resampler and runs from rate * r)
+			want.push_back({conf * r, conf, size, PHASE_MAJOR, &ua.tab_down_in[r]});
+			want.push_back({conf, conf * r, size, AS_DESIGNED, &ua.tab_up_out[r]});
 		}
-		if (!used[r]) continue;
-		if ((rc = design_table(b->ctx, b->cfg.rate / r, b->cfg.rate, t)) != MI_OK) return rc;
-		if (t.size() != (size_t)r * RS_FILT) return MI_ENOTSUP;
-		b->tab_up[r] = (int)all.size();
-		all.insert(all.end(), t.begin(), t.end());
-		if ((rc = design_table(b->ctx, b->cfg.rate, b->cfg.rate / r, t)) != MI_OK) return rc;
-		if (t.size() != (size_t)r * RS_FILT) return MI_ENOTSUP;
-		b->tab_down[r] = (int)all.size();
-		for (int p = 0; p < r; ++p)
-			for (int i = 0; i < RS_FILT; ++i) all.push_back(t[(size_t)i * r + p]);
+		if (pl.used[r]) {
+			want.push_back({conf / r, conf, size, AS_DESIGNED, &ra.tab_up[r]});
+			want.push_back({conf, conf / r, size, PHASE_MAJOR, &ra.tab_down[r]});
+		}
+	}
+	std::vector<float> all, t;
+	for (const Table &w : want) {
+		const int rc = design_table(b->ctx, w.in_rate, w.out_rate, t);
+		if (rc != MI_OK) return rc;
+		if (t.size() != w.size) return MI_ENOTSUP;
+		*w.offset = (int)all.size();
+		const int g = std::min(w.in_rate, w.out_rate) / (w.layout == REARRANGED ? 2 : 1); // the rates are M * g and L * g
+		const int L = w.out_rate / g, M = w.in_rate / g;
+		if (w.layout == AS_DESIGNED) all.insert(all.end(), t.begin(), t.end());
+		else if (w.layout == PHASE_MAJOR)
+			for (int p = 0; p < M; ++p)
+				for (int i = 0; i < RS_FILT; ++i) all.push_back(t[(size_t)i * M + p]);
+		else
+			for (int r = 0; r < L; ++r)
+				for (int pp = 0; pp < M; ++pp)
+					for (int k = 0; k < RQ_FT; ++k) all.push_back(t[(size_t)((r * M) % L) * RQ_FT * M + (size_t)k * M + pp]);
 	}
 	if (!(b->d_tab = (float *)mi_dev_alloc(b->ctx, all.size() * sizeof(float)))) return MI_ENOMEM;
 	MI_HIP(hipMemcpy(b->d_tab, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -502,10 +472,9 @@ void mi_bridge_destroy(mi_bridge *b) {
 		for (uint8_t *p : {b->d_in[i], b->d_present[i], b->d_ev[i], b->d_out[i]})
 			if (p) mi_dev_free(c, p);
 	}
-	for (void *p : {(void *)b->d_ratio, (void *)b->d_hist_in, (void *)b->d_hist_out, (void *)b->d_tab, (void *)b->d_codec})
+	void *const rest[] = {b->d_ratio, b->d_hist_in, b->d_hist_out, b->d_tab, b->d_codec, b->d_pcm, b->d_evlen};
+	for (void *p : rest)
 		if (p) mi_dev_free(c, p);
-	if (b->d_pcm) mi_dev_free(c, b->d_pcm);
-	if (b->d_evlen) mi_dev_free(c, b->d_evlen);
 	if (b->plc) mi_plc_destroy(b->plc);
 	if (b->vol) mi_volume_destroy(b->vol);
 	if (b->mix) mi_mixer_destroy(b->mix);
@@ -513,306 +482,101 @@ void mi_bridge_destroy(mi_bridge *b) {
 	delete b;
 }
 
-int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) { return mi_bridge_create_rated(ctx, cfg, nullptr, out); }
-
-// h_codec [nstreams]: in_codec | out_codec << 2 of legs that differ (mi_bridge_create_legs, which has checked them), or null.
-// endpoints: mi_bridge_create_endpoints' rules -- a leg may be above cfg->rate, and h_codec is there whenever one is
-// leg_plc: mi_bridge_create_concealed with cfg->plc and legs that differ -- the concealer is the per-leg one (h_codec is there)
-// rational: mi_bridge_create_rational with a leg at 3/2 or 2/3 of cfg->rate (endpoints' rules besides; h_codec is there)
-static int create_bridge(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, const uint8_t *h_codec, mi_bridge **out,
-                         bool endpoints = false, bool leg_plc = false, bool rational = false) {
-	const char *fn = rational ? "mi_bridge_create_rational"
-	                 : leg_plc ? "mi_bridge_create_concealed"
-	                 : endpoints ? "mi_bridge_create_endpoints"
-	                             : "mi_bridge_create_rated";
-	MI_CHECK_ARG(ctx && cfg && out);
-	*out = nullptr;
-	MI_CHECK_ARG(cfg->nstreams > 0 && cfg->members_per_conference > 0 && cfg->members_per_conference <= MI_MIXER_MAX_CHANNELS &&
-	             cfg->nstreams % cfg->members_per_conference == 0);
-	MI_CHECK_ARG(cfg->rate > 0);
-	MI_CHECK_ARG(cfg->in_codec >= MI_SESSION_PCM16 && cfg->in_codec <= MI_SESSION_PCMU && cfg->out_codec >= MI_SESSION_PCM16 &&
-	             cfg->out_codec <= MI_SESSION_PCMU);
-	if (cfg->rate % 800 != 0) {
-		mi::set_error("mi_bridge_create: rate %d is no multiple of 800 (a 10 ms tick must be whole groups of 8 samples)", cfg->rate);
-		return MI_ENOTSUP;
-	}
-	const int len = cfg->rate / 100, mm = cfg->members_per_conference;
-	// ---- the legs' rates: every refusal before anything is allocated
-	bool used[7] = {}, above[7] = {}; // the ratios of legs below the mix, and of legs above it
-	int widest = 0, common = 0, max_ratio = 1;
-	bool rated = false, updown = false, r32_above = false, r32_below = false;
-	// what holds for a leg of any ratio, checked once that ratio is known to be served: a tick of whole groups, and one rate
-	// for the one concealer batch
-	auto leg_fits = [&](int s, int lr) {
-		if (lr % 800 != 0) {
-			mi::set_error("%s: leg %d's rate %d is no multiple of 800 (a 10 ms tick must be whole groups of 8 samples)", fn, s, lr);
-			return false;
-		}
-		if (cfg->plc && !leg_plc && common && lr != common) {
-			mi::set_error("%s: plc with legs at %d Hz and %d Hz: the concealer batch has one rate", fn, common, lr);
-			return false;
-		}
-		if (!common) common = lr;
-		widest = std::max(widest, lr);
-		return true;
-	};
-	if (h_leg_rate) {
-		for (int s = 0; s < cfg->nstreams; ++s) {
-			const int lr = h_leg_rate[s];
-			MI_CHECK_ARG(lr > 0);
-			const bool up = lr > cfg->rate;
-			// 3/2 or 2/3, both rates multiples of 800: leg and mix are 2400 k and 1600 k Hz, their ticks 24 k and 16 k samples --
-			// 8 k periods of 3 samples against 2: whole periods and whole eight-period tiles, eight-sample groups, both ways
-			if (rational && ((int64_t)2 * lr == (int64_t)3 * cfg->rate || (int64_t)3 * lr == (int64_t)2 * cfg->rate)) {
-				if (!leg_fits(s, lr)) return MI_ENOTSUP;
-				(up ? r32_above : r32_below) = true;
-				continue;
-			}
-			if (up && !endpoints) {
-				mi::set_error("mi_bridge_create_rated: leg %d at %d Hz is above its conference's %d Hz (only legs at or below the mix are resampled)",
-				              s, lr, cfg->rate);
-				return MI_ENOTSUP;
-			}
-			const int hi = up ? lr : cfg->rate, lo = up ? cfg->rate : lr;
-			if (hi % lo != 0) {
-				mi::set_error("%s: leg %d at %d Hz in a %d Hz conference is no whole ratio (%.3f); supported: 1, 2, 3, 6%s", fn, s, lr, cfg->rate,
-				              (double)hi / lo, rational ? ", and 3/2 either way" : "");
-				return MI_ENOTSUP;
-			}
-			const int r = hi / lo;
-			if (r != 1 && r != 2 && r != 3 && r != 6) {
-				mi::set_error("%s: leg %d at %d Hz in a %d Hz conference is ratio %d; supported: 1, 2, 3, 6%s", fn, s, lr, cfg->rate, r,
-				              rational ? ", and 3/2 either way" : "");
-				return MI_ENOTSUP;
-			}
-			if (!leg_fits(s, lr)) return MI_ENOTSUP;
-			(up ? above : used)[r] = true;
-			updown |= up;
-			max_ratio = std::max(max_ratio, r);
-		}
-		rated = max_ratio > 1 || r32_above || r32_below;
-	}
-	rational = r32_above || r32_below; // without such a leg: mi_bridge_create_concealed's bridge exactly
-	// samples per row in LDS: the widest leg's tick where one is above the mix
-	const int wide = updown ? widest / 100 : rational ? std::max(len, widest / 100) : len;
-	const int row_w = (wide >> 2) | 1;             // 8-byte words per row, odd
-	const size_t sum_off = mi::round_up((size_t)mm * row_w * 8, 16);
-	size_t lds = sum_off + (size_t)len * 4, scratch_off = 0, scratch = 0;
-	if (rated) {
-		for (int r = 2; r < 7; ++r) {
-			// each wavefront's scratch: the larger of the forms per used ratio -- up-sampler and down-sampler of a leg below the
-			// mix (in front of the pin, behind it), down-sampler and up-sampler of a leg above it
-			size_t up = 0, down = 0;
-			if (used[r]) {
-				up = (size_t)((RS_FILT - 1 + len / r + RS_R + 1 + 3) & ~3) * 4;
-				down = ((size_t)r * rated_plen(r, len) + (size_t)len) * 4;
-			}
-			if (above[r]) {
-				up = std::max(up, (size_t)((RS_FILT - 1 + len + RS_R + 1 + 3) & ~3) * 4);
-				down = std::max(down, ((size_t)r * updown_plen(r, r * len) + (size_t)r * len) * 4);
-			}
-			scratch = std::max(scratch, mi::round_up(std::max(up, down), 16));
-		}
-		// a leg at 3/2 of the mix: x 2/3 from its tick in front of the pin, x 3/2 from the mix's behind it; one at 2/3: x 3/2 from
-		// its tick, x 2/3 from the mix's
-		if (r32_above) scratch = std::max(scratch, std::max(rational_scratch(3, len / 2 * 3), rational_scratch(2, len)));
-		if (r32_below) scratch = std::max(scratch, std::max(rational_scratch(2, len / 3 * 2), rational_scratch(3, len)));
-		scratch_off = mi::round_up(lds, 16);
-		lds = scratch_off + (BT / 64) * scratch;
-		if (lds + RATED_STATIC_LDS > BRIDGE_LDS_MAX) {
-			mi::set_error("%s: a conference's tick and its resamplers' scratch must fit %zu bytes of LDS (%d members x %d samples "
-			              "= %zu, + %d wavefronts x %zu for ratio %d%s, + %zu of the kernel's own: %zu)",
-			              fn, BRIDGE_LDS_MAX, mm, wide, scratch_off, BT / 64, scratch, max_ratio, rational ? " and 3/2" : "", RATED_STATIC_LDS,
-			              lds + RATED_STATIC_LDS);
-			return MI_ENOTSUP;
-		}
-	} else if (lds > BRIDGE_LDS_MAX) {
-		mi::set_error("mi_bridge_create: a conference's tick must fit %zu bytes of LDS (%d members x %d samples need %zu)", BRIDGE_LDS_MAX, mm,
-		              len, lds);
-		return MI_ENOTSUP;
-	}
-	const int pitch = rated ? widest / 100 : len;
-	size_t in_bytes = (size_t)pitch * (cfg->in_codec ? 1 : 2), out_bytes = (size_t)pitch * (cfg->out_codec ? 1 : 2);
-	if (h_codec) { // byte rows: the widest leg's tick in bytes, rounded up to the 16 bytes a lane loads
-		in_bytes = out_bytes = 0;
-		for (int s = 0; s < cfg->nstreams; ++s) {
-			const size_t ll = (size_t)(h_leg_rate ? h_leg_rate[s] : cfg->rate) / 100;
-			in_bytes = std::max(in_bytes, ll * ((h_codec[s] & 3) ? 1 : 2));
-			out_bytes = std::max(out_bytes, ll * ((h_codec[s] >> 2) ? 1 : 2));
-		}
-		in_bytes = mi::round_up(in_bytes, 16), out_bytes = mi::round_up(out_bytes, 16);
-	}
+// allocation only: everything is sized by the plan, which has refused what cannot be served
+static int build_bridge(mi_ctx *ctx, Plan &plan, mi_bridge **out) {
 	if (ctx->activate() != MI_OK) return MI_ENODEV;
 	mi_bridge *b = new mi_bridge();
 	b->ctx = b->pipe.ctx = ctx;
-	b->cfg = *cfg;
-	b->n = cfg->nstreams;
-	b->mm = mm;
-	b->nconf = cfg->nstreams / mm;
-	b->len = len;
-	b->row_w = row_w;
-	b->sum_off = (int)sum_off;
-	b->lds = lds;
-	b->nslice = std::max(1, std::min(mm, BT / (len >> 2)));
-	b->rated = rated, b->pitch = pitch;
-	b->updown = updown, b->wide = wide;
-	b->rational = rational;
-	b->in_bytes = in_bytes, b->out_bytes = out_bytes;
-	if (h_leg_rate) b->leg_rate.assign(h_leg_rate, h_leg_rate + cfg->nstreams);
-	b->roster.init(b->n, mm);
+	b->plan = std::move(plan);
+	const Plan &pl = b->plan;
+	const size_t n = (size_t)pl.n;
+	b->roster.init(pl.n, pl.mm);
 	int rc = MI_OK;
-	auto fail = [&](int code) {
-		mi_bridge_destroy(b);
-		return code;
-	};
-	if ((rc = mi_volume_create(ctx, b->n, cfg->rate, &b->vol)) != MI_OK) return fail(rc);
-	if ((rc = mi_mixer_create(ctx, b->nconf, mm, len, &b->mix)) != MI_OK) return fail(rc);
+	auto fail = [&](int code) { return mi_bridge_destroy(b), code; };
+	if ((rc = mi_volume_create(ctx, pl.n, pl.cfg.rate, &b->vol)) != MI_OK) return fail(rc);
+	if ((rc = mi_mixer_create(ctx, pl.nconf, pl.mm, pl.len, &b->mix)) != MI_OK) return fail(rc);
 	if ((rc = b->pipe.create(ctx, SLOTS)) != MI_OK) return fail(rc);
-	const size_t n = (size_t)b->n;
 	for (int i = 0; i < SLOTS; ++i) {
-		b->h_in[i] = (uint8_t *)mi_host_alloc(ctx, n * b->in_bytes);
+		b->h_in[i] = (uint8_t *)mi_host_alloc(ctx, n * pl.in_bytes);
 		b->h_present[i] = (uint8_t *)mi_host_alloc(ctx, n);
-		b->h_out[i] = (uint8_t *)mi_host_alloc(ctx, n * b->out_bytes);
-		b->d_in[i] = (uint8_t *)mi_dev_alloc(ctx, n * b->in_bytes);
+		b->h_out[i] = (uint8_t *)mi_host_alloc(ctx, n * pl.out_bytes);
+		b->d_in[i] = (uint8_t *)mi_dev_alloc(ctx, n * pl.in_bytes);
 		b->d_present[i] = (uint8_t *)mi_dev_alloc(ctx, n);
-		b->d_out[i] = (uint8_t *)mi_dev_alloc(ctx, n * b->out_bytes);
+		b->d_out[i] = (uint8_t *)mi_dev_alloc(ctx, n * pl.out_bytes);
 		if (!b->h_in[i] || !b->h_present[i] || !b->h_out[i] || !b->d_in[i] || !b->d_present[i] || !b->d_out[i]) return fail(MI_ENOMEM);
+		if (pl.cfg.plc) b->h_ev[i] = (uint8_t *)mi_host_alloc(ctx, n), b->d_ev[i] = (uint8_t *)mi_dev_alloc(ctx, n);
+		if (pl.cfg.plc && (!b->h_ev[i] || !b->d_ev[i])) return fail(MI_ENOMEM);
 		// rows of pins whose output is off are never written: they read as zeros
-		MI_HIP(hipMemsetAsync(b->d_out[i], 0, n * b->out_bytes, ctx->stream));
-		memset(b->h_out[i], 0, n * b->out_bytes);
+		MI_HIP(hipMemsetAsync(b->d_out[i], 0, n * pl.out_bytes, ctx->stream));
+		memset(b->h_out[i], 0, n * pl.out_bytes);
 	}
-	if (rated) {
-		b->scratch_off = (int)scratch_off, b->scratch_per_wave = (int)scratch;
-		b->hout_stride = max_ratio * RS_FILT; // mi_resampler's round_up(filt_len - 1, 8) of the longest filter
-		if (rational) b->hout_stride = std::max(b->hout_stride, 3 * RQ_FT); // x 2/3 keeps 71 samples (x 3/2: 47)
-		if (updown || rational) b->hin_stride = b->hout_stride; // a down-sampler's history on either side of the pin
-		std::vector<uint8_t> ratio(n);
-		for (size_t s = 0; s < n; ++s) {
-			const int lr = h_leg_rate[s];
-			ratio[s] = lr > cfg->rate ? (uint8_t)(UD_ABOVE | (unsigned)(lr / cfg->rate)) : (uint8_t)(cfg->rate / lr);
-			if ((int64_t)2 * lr == (int64_t)3 * cfg->rate || (int64_t)3 * lr == (int64_t)2 * cfg->rate) ratio[s] |= UD_R32; // (the whole part: 1)
-		}
+	if (pl.rated) {
 		b->d_ratio = (uint8_t *)mi_dev_alloc(ctx, n);
-		b->d_hist_in = (int16_t *)mi_dev_alloc(ctx, n * b->hin_stride * sizeof(int16_t));
-		b->d_hist_out = (int16_t *)mi_dev_alloc(ctx, n * b->hout_stride * sizeof(int16_t));
+		b->d_hist_in = (int16_t *)mi_dev_alloc(ctx, n * pl.hin_stride * sizeof(int16_t));
+		b->d_hist_out = (int16_t *)mi_dev_alloc(ctx, n * pl.hout_stride * sizeof(int16_t));
 		if (!b->d_ratio || !b->d_hist_in || !b->d_hist_out) return fail(MI_ENOMEM);
-		if (hipMemcpy(b->d_ratio, ratio.data(), n, hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
-		if ((rc = reset_resamplers(b, 0, b->n)) != MI_OK) return fail(rc);
-		if ((rc = build_tables(b, used, above, r32_above, r32_below)) != MI_OK) return fail(rc);
+		if (hipMemcpy(b->d_ratio, pl.ratio.data(), n, hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
+		if ((rc = reset_resamplers(b, 0, pl.n)) != MI_OK) return fail(rc);
+		if ((rc = build_tables(b)) != MI_OK) return fail(rc);
 	}
-	if (h_codec) {
-		b->leg_codec.assign(h_codec, h_codec + n);
-		if (cfg->plc) // (one pair on every leg) a second row for the kernel behind the concealer, whose input is PCM
-			for (size_t s = 0; s < n; ++s) b->leg_codec.push_back((uint8_t)(h_codec[s] & ~3u));
-		if (!(b->d_codec = (uint8_t *)mi_dev_alloc(ctx, b->leg_codec.size()))) return fail(MI_ENOMEM);
-		if (hipMemcpy(b->d_codec, b->leg_codec.data(), b->leg_codec.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
-		b->leg_codec.resize(n);
+	if (!pl.leg_codec.empty()) {
+		std::vector<uint8_t> rows = pl.leg_codec;
+		if (pl.cfg.plc) // (one pair on every leg) a second row for the kernel behind the concealer, whose input is PCM
+			for (size_t s = 0; s < n; ++s) rows.push_back((uint8_t)(pl.leg_codec[s] & ~3u));
+		if (!(b->d_codec = (uint8_t *)mi_dev_alloc(ctx, rows.size()))) return fail(MI_ENOMEM);
+		if (hipMemcpy(b->d_codec, rows.data(), rows.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
 	}
-	if (cfg->plc) {
-		if (leg_plc) { // at every leg's own rate behind its own decoder, into PCM rows of `pitch` samples
+	if (pl.cfg.plc) {
+		if (pl.leg_plc) { // at every leg's own rate behind its own decoder, into PCM rows of `pitch` samples
 			std::vector<uint8_t> kind(n);
-			for (size_t s = 0; s < n; ++s) kind[s] = h_codec[s] & 3;
-			b->leg_plc = true;
-			if ((rc = mi_plc_create_legs(ctx, b->n, h_leg_rate, kind.data(), pitch, &b->plc)) != MI_OK) return fail(rc);
-			if (!(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * pitch * 2))) return fail(MI_ENOMEM);
-			if (hipMemsetAsync(b->d_pcm, 0, n * pitch * 2, ctx->stream) != hipSuccess) return fail(MI_ENODEV);
+			for (size_t s = 0; s < n; ++s) kind[s] = pl.leg_codec[s] & 3;
+			if ((rc = mi_plc_create_legs(ctx, pl.n, pl.leg_rate.data(), kind.data(), pl.pitch, &b->plc)) != MI_OK) return fail(rc);
+			if (!(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * pl.pitch * 2))) return fail(MI_ENOMEM);
+			if (hipMemsetAsync(b->d_pcm, 0, n * pl.pitch * 2, ctx->stream) != hipSuccess) return fail(MI_ENODEV);
 		} else { // at the legs' one rate, on rows of the host buffers' pitch
-			if ((rc = mi_plc_create(ctx, b->n, rated ? common : cfg->rate, pitch, &b->plc)) != MI_OK) return fail(rc);
-			std::vector<int32_t> lens(n, pitch);
+			if ((rc = mi_plc_create(ctx, pl.n, pl.rated ? pl.common : pl.cfg.rate, pl.pitch, &b->plc)) != MI_OK) return fail(rc);
+			std::vector<int32_t> lens(n, pl.pitch);
 			if (!(b->d_evlen = (int32_t *)mi_dev_alloc(ctx, n * 4))) return fail(MI_ENOMEM);
 			if (hipMemcpy(b->d_evlen, lens.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(MI_ENODEV);
-			if (cfg->in_codec && !(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * pitch * 2))) return fail(MI_ENOMEM);
-		}
-		for (int i = 0; i < SLOTS; ++i) {
-			b->h_ev[i] = (uint8_t *)mi_host_alloc(ctx, n);
-			b->d_ev[i] = (uint8_t *)mi_dev_alloc(ctx, n);
-			if (!b->h_ev[i] || !b->d_ev[i]) return fail(MI_ENOMEM);
+			if (pl.cfg.in_codec && !(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * pl.pitch * 2))) return fail(MI_ENOMEM);
 		}
 	}
+	fill_args(b);
 	if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(MI_ENODEV);
 	*out = b;
 	return MI_OK;
 }
 
-int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, mi_bridge **out) {
-	return create_bridge(ctx, cfg, h_leg_rate, nullptr, out);
-}
-
-// mi_bridge_create_legs and mi_bridge_create_endpoints: the legs' codecs checked, then create_bridge with the first's rules on
-// rates or the second's.  concealed: mi_bridge_create_concealed -- the second's rules, and cfg->plc with legs that differ is
-// served by the per-leg concealer instead of refused.  rational: mi_bridge_create_rational -- the third's rules, and a leg may
-// be at 3/2 or 2/3 of cfg->rate
-static int create_from_legs(const char *fn, bool endpoints, mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs,
-                            mi_bridge **out, bool concealed = false, bool rational = false) {
-	if (!h_legs) return mi_bridge_create(ctx, cfg, out);
+// every public constructor: its rules' plan, then the build (legs null: rates or nothing, and no rule about codecs is read)
+static int create(const Rules &rules, mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *rates, const mi_bridge_leg *legs, mi_bridge **out) {
 	MI_CHECK_ARG(ctx && cfg && out);
 	*out = nullptr;
-	MI_CHECK_ARG(cfg->nstreams > 0);
-	const size_t n = (size_t)cfg->nstreams;
-	std::vector<int32_t> rate(n);
-	std::vector<uint8_t> codec(n);
-	int differs = -1; // the first leg whose pair is not leg 0's
-	bool above = false;
-	for (size_t s = 0; s < n; ++s) {
-		const mi_bridge_leg &l = h_legs[s];
-		for (int v : {l.in_codec, l.out_codec})
-			if (v < MI_SESSION_PCM16 || v > MI_SESSION_PCMU) {
-				mi::set_error("%s: leg %zu names codec %d; supported: MI_SESSION_PCM16 (0), MI_SESSION_PCMA (1), "
-				              "MI_SESSION_PCMU (2)", fn, s, v);
-				return MI_ENOTSUP;
-			}
-		rate[s] = l.rate;
-		codec[s] = (uint8_t)(l.in_codec | l.out_codec << 2);
-		if (differs < 0 && codec[s] != codec[0]) differs = (int)s;
-		above |= l.rate > cfg->rate;
-		// (such a leg brings the codecs as data and byte rows, as one above the mix does)
-		if (rational) above |= (int64_t)3 * l.rate == (int64_t)2 * cfg->rate;
-	}
-	if (concealed && cfg->plc) {
-		bool one_rate = true;
-		for (size_t s = 0; s < n; ++s) { // what the concealer cannot serve, before anything is allocated
-			const int rc = mi_plc_check_rate(fn, "leg", (int)s, rate[s]);
-			if (rc != MI_OK) return rc;
-			one_rate &= rate[s] == rate[0];
-		}
-		if (differs >= 0 || !one_rate) {
-			mi_bridge_config c = *cfg; // (its pair is not read: the codecs are the kernel's data)
-			c.in_codec = h_legs[0].in_codec, c.out_codec = h_legs[0].out_codec;
-			return create_bridge(ctx, &c, rate.data(), codec.data(), out, true, true, rational);
-		}
-	}
-	if (differs >= 0 && cfg->plc) {
-		mi::set_error("%s: plc with leg %d's codecs (in %d, out %d) unlike leg 0's (in %d, out %d): the concealer batch "
-		              "sits behind one decoder", fn, differs, h_legs[differs].in_codec, h_legs[differs].out_codec, h_legs[0].in_codec,
-		              h_legs[0].out_codec);
-		return MI_ENOTSUP;
-	}
-	mi_bridge_config c = *cfg; // a uniform bridge is mi_bridge_create_rated's, its one pair compile-time in the kernels
-	c.in_codec = h_legs[0].in_codec, c.out_codec = h_legs[0].out_codec;
-	// with a leg above the mix (endpoints; create_bridge refuses it otherwise) the codecs are the kernel's data whether they
-	// differ or not, and the host rows byte rows
-	return create_bridge(ctx, &c, rate.data(), differs >= 0 || (endpoints && above) ? codec.data() : nullptr, out, endpoints, false, rational);
+	Plan plan;
+	const int rc = legs ? plan_legs(rules, cfg, legs, &plan) : plan_bridge(rules, cfg, rates, nullptr, &plan);
+	return rc != MI_OK ? rc : build_bridge(ctx, plan, out);
 }
 
+int mi_bridge_create(mi_ctx *ctx, const mi_bridge_config *cfg, mi_bridge **out) { return create(RULES_RATED, ctx, cfg, nullptr, nullptr, out); }
+
+int mi_bridge_create_rated(mi_ctx *ctx, const mi_bridge_config *cfg, const int32_t *h_leg_rate, mi_bridge **out) {
+	return create(RULES_RATED, ctx, cfg, h_leg_rate, nullptr, out);
+}
 int mi_bridge_create_legs(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
-	return create_from_legs("mi_bridge_create_legs", false, ctx, cfg, h_legs, out);
+	return create(RULES_LEGS, ctx, cfg, nullptr, h_legs, out);
 }
-
 int mi_bridge_create_endpoints(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
-	return create_from_legs("mi_bridge_create_endpoints", true, ctx, cfg, h_legs, out);
+	return create(RULES_ENDPOINTS, ctx, cfg, nullptr, h_legs, out);
 }
-
 int mi_bridge_create_concealed(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
-	return create_from_legs("mi_bridge_create_concealed", true, ctx, cfg, h_legs, out, true);
+	return create(RULES_CONCEALED, ctx, cfg, nullptr, h_legs, out);
 }
-
 int mi_bridge_create_rational(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
-	return create_from_legs("mi_bridge_create_rational", true, ctx, cfg, h_legs, out, true, true);
+	return create(RULES_RATIONAL, ctx, cfg, nullptr, h_legs, out);
 }
 
 int mi_bridge_leg_codec(const mi_bridge *b, int stream, int *in_codec, int *out_codec) {
-	if (!b || stream < 0 || stream >= b->n) return MI_EINVAL;
-	const int pair = b->leg_codec.empty() ? b->cfg.in_codec | b->cfg.out_codec << 2 : b->leg_codec[(size_t)stream];
+	if (!b || stream < 0 || stream >= b->plan.n) return MI_EINVAL;
+	const int pair = b->plan.leg_codec.empty() ? b->plan.cfg.in_codec | b->plan.cfg.out_codec << 2 : b->plan.leg_codec[(size_t)stream];
 	if (in_codec) *in_codec = pair & 3;
 	if (out_codec) *out_codec = pair >> 2;
 	return MI_OK;
@@ -828,14 +592,14 @@ int mi_bridge_leg_bytes(const mi_bridge *b, int stream, int *in_bytes, int *out_
 }
 
 int mi_bridge_leg_rate(const mi_bridge *b, int stream) {
-	if (!b || stream < 0 || stream >= b->n) return MI_EINVAL;
-	return b->leg_rate.empty() ? b->cfg.rate : b->leg_rate[(size_t)stream];
+	if (!b || stream < 0 || stream >= b->plan.n) return MI_EINVAL;
+	return b->plan.leg_rate.empty() ? b->plan.cfg.rate : b->plan.leg_rate[(size_t)stream];
 }
 
 int mi_bridge_tick_bytes(const mi_bridge *b, int *in_bytes, int *out_bytes) {
 	MI_CHECK_ARG(b != nullptr);
-	if (in_bytes) *in_bytes = (int)b->in_bytes;
-	if (out_bytes) *out_bytes = (int)b->out_bytes;
+	if (in_bytes) *in_bytes = (int)b->plan.in_bytes;
+	if (out_bytes) *out_bytes = (int)b->plan.out_bytes;
 	return MI_OK;
 }
 
@@ -848,7 +612,7 @@ int mi_bridge_acquire(mi_bridge *b, void **h_in, uint8_t **h_present) {
 	if (rc != MI_OK) return rc;
 	*h_in = b->h_in[slot];
 	*h_present = b->h_present[slot];
-	memset(b->h_present[slot], 1, (size_t)b->n);
+	memset(b->h_present[slot], 1, (size_t)b->plan.n);
 	return MI_OK;
 }
 
@@ -858,10 +622,10 @@ int mi_bridge_submit(mi_bridge *b) {
 		mi::set_error("mi_bridge_submit without mi_bridge_acquire");
 		return MI_EINVAL;
 	}
-	const size_t n = (size_t)b->n;
+	const size_t n = (size_t)b->plan.n;
 	return b->pipe.submit(
 	    [&](int slot) {
-		    MI_HIP(hipMemcpyAsync(b->d_in[slot], b->h_in[slot], n * b->in_bytes, hipMemcpyHostToDevice, b->pipe.s_up));
+		    MI_HIP(hipMemcpyAsync(b->d_in[slot], b->h_in[slot], n * b->plan.in_bytes, hipMemcpyHostToDevice, b->pipe.s_up));
 		    if (b->plc) { // an absent leg is the concealer's to fill
 			    for (size_t i = 0; i < n; ++i) b->h_ev[slot][i] = b->h_present[slot][i] ? MI_PLC_RECEIVED : MI_PLC_CONCEAL;
 			    MI_HIP(hipMemcpyAsync(b->d_ev[slot], b->h_ev[slot], n, hipMemcpyHostToDevice, b->pipe.s_up));
@@ -872,7 +636,7 @@ int mi_bridge_submit(mi_bridge *b) {
 	    },
 	    [&](int slot) { return run_tick_kernels(b, slot); },
 	    [&](int slot) {
-		    MI_HIP(hipMemcpyAsync(b->h_out[slot], b->d_out[slot], n * b->out_bytes, hipMemcpyDeviceToHost, b->pipe.s_down));
+		    MI_HIP(hipMemcpyAsync(b->h_out[slot], b->d_out[slot], n * b->plan.out_bytes, hipMemcpyDeviceToHost, b->pipe.s_down));
 		    return MI_OK;
 	    });
 }
@@ -897,7 +661,7 @@ int mi_bridge_set_controls(mi_bridge *b, const uint8_t *h_flags, const float *h_
 }
 
 int mi_bridge_set_volume_params(mi_bridge *b, int first, int count, const mi_volume_params *h_params) {
-	MI_CHECK_ARG(b && h_params && first >= 0 && count >= 0 && first + count <= b->n);
+	MI_CHECK_ARG(b && h_params && first >= 0 && count >= 0 && first + count <= b->plan.n);
 	for (int i = 0; i < count; ++i)
 		if (h_params[i].peer != -1) {
 			mi::set_error("mi_bridge_set_volume_params: stream %d names an echo-limiter peer (%d); a bridge has no far end to limit against",
@@ -908,7 +672,7 @@ int mi_bridge_set_volume_params(mi_bridge *b, int first, int count, const mi_vol
 }
 
 int mi_bridge_reset_streams(mi_bridge *b, int first, int count) {
-	MI_CHECK_ARG(b && first >= 0 && count >= 0 && first + count <= b->n);
+	MI_CHECK_ARG(b && first >= 0 && count >= 0 && first + count <= b->plan.n);
 	if (count == 0) return MI_OK;
 	int rc;
 	if ((rc = mi::reset_meters(b->vol, first, count)) != MI_OK) return rc;
@@ -917,7 +681,7 @@ int mi_bridge_reset_streams(mi_bridge *b, int first, int count) {
 }
 
 int mi_bridge_add_member(mi_bridge *b, int stream) {
-	MI_CHECK_ARG(b && stream >= 0 && stream < b->n);
+	MI_CHECK_ARG(b && stream >= 0 && stream < b->plan.n);
 	if (b->roster.is_member(stream)) {
 		mi::set_error("mi_bridge_add_member: stream %d is a member already", stream);
 		return MI_EINVAL;
@@ -929,7 +693,7 @@ int mi_bridge_add_member(mi_bridge *b, int stream) {
 }
 
 int mi_bridge_remove_member(mi_bridge *b, int stream) {
-	MI_CHECK_ARG(b && stream >= 0 && stream < b->n);
+	MI_CHECK_ARG(b && stream >= 0 && stream < b->plan.n);
 	if (!b->roster.leave(stream)) {
 		mi::set_error("mi_bridge_remove_member: stream %d is no member", stream);
 		return MI_EINVAL;
@@ -941,20 +705,20 @@ int mi_bridge_remove_member(mi_bridge *b, int stream) {
 	MI_HIP(hipStreamSynchronize(b->ctx->stream));
 	MI_HIP(hipStreamSynchronize(b->pipe.s_down));
 	for (int i = 0; i < SLOTS; ++i) {
-		MI_HIP(hipMemsetAsync(b->d_out[i] + (size_t)stream * b->out_bytes, 0, b->out_bytes, b->ctx->stream));
-		memset(b->h_out[i] + (size_t)stream * b->out_bytes, 0, b->out_bytes);
+		MI_HIP(hipMemsetAsync(b->d_out[i] + (size_t)stream * b->plan.out_bytes, 0, b->plan.out_bytes, b->ctx->stream));
+		memset(b->h_out[i] + (size_t)stream * b->plan.out_bytes, 0, b->plan.out_bytes);
 	}
 	return MI_OK;
 }
 
 int mi_bridge_member_count(const mi_bridge *b, int conference) {
-	if (!b || conference < 0 || conference >= b->nconf) return MI_EINVAL;
+	if (!b || conference < 0 || conference >= b->plan.nconf) return MI_EINVAL;
 	return b->roster.count(conference);
 }
 
 int mi_bridge_get_levels(mi_bridge *b, float *h_linear) {
 	MI_CHECK_ARG(b && h_linear);
-	return mi::get_levels(b->vol, b->n, h_linear);
+	return mi::get_levels(b->vol, b->plan.n, h_linear);
 }
 
 int mi_bridge_active_speakers(mi_bridge *b, uint64_t now_ms, int32_t *h_winner, float *h_max_db) {

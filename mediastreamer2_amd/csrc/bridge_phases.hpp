@@ -15,7 +15,7 @@
 #include "g711.hpp"
 #include "volume_ctl.hpp"
 
-#include "../../include/msmi355x_bridge.h"
+#include "bridge_plan.hpp" // BT, the resamplers' constants and lengths, the ratio byte's bits: what the host's plan shares
 
 #pragma clang fp contract(off)
 
@@ -23,12 +23,8 @@ namespace {
 
 #include "resample_tile.hpp"
 
-constexpr int BT = 256, BMAX = MI_MIXER_MAX_CHANNELS;
-constexpr int RS_FILT = 48, RS_R = 8; // quality 3: 48 taps per polyphase row, fir_tile's eight positions
-constexpr int RQ_FT = 24;             // taps per lane of the rational resamplers: filt_len / M, 48 / 2 and 72 / 3
-
-// ---- the kernels' arguments.  Each kernel's struct holds the one before it, so the host fills a RationalArgs once per tick
-// (tick_args, bridge.hip) and every kernel is passed its own part of it.
+// ---- the kernels' arguments.  Each kernel's struct holds the one before it, so the host fills a RationalArgs once per bridge
+// (mi_bridge::args, bridge.hip) and every kernel is passed its own part of it.
 struct BridgeArgs {
 	const void *in;         // [nconf * mm][ns] uint8 code words or int16
 	const uint8_t *present; // [nconf * mm], or null: every member present
@@ -79,16 +75,13 @@ struct RationalArgs {
 	int tab_above_in, tab_above_out, tab_below_in, tab_below_out;
 };
 
-// ---- a member's ratio byte.  Conference rate / leg rate (1, 2, 3 or 6) for a leg at or below the mix; with UD_ABOVE the
-// leg is above it and the low three bits are leg rate / conference rate; with UD_R32 the ratio is 3/2 (the whole part: 1),
-// UD_ABOVE still giving the direction.  A kernel meets only the forms it was built for:
+// ---- a member's ratio byte (bridge_plan.hpp writes it).  A kernel meets only the forms it was built for:
 enum Forms {
 	F_SAME,  // every leg at the conference's rate: no ratio byte, no resampler
 	F_BELOW, // legs at or below the mix
 	F_ABOVE, // and above it
 	F_R32,   // and at 3/2 or 2/3 of it
 };
-constexpr unsigned UD_ABOVE = 0x80, UD_R32 = 0x40;
 
 // The one place where a ratio byte becomes a length or a rate: the leg's share of `conf` -- groups, words or samples of the
 // conference's tick, or its sample rate.  F_SAME folds to `conf` at compile time.
@@ -378,20 +371,7 @@ __device__ __forceinline__ void mix_minus(const Conf &k, uint8_t *out, int pitch
 	}
 }
 
-// ---- the resamplers, one wavefront running one member's.  floats per phase array of a down-sampler (history ++ tick split
-// by input phase, + the tile FIR's look-ahead): rated_plen behind a pin; updown_plen, the same with plen / 4 odd, in FRONT
-// of one.  Lane l of the tile FIR reads 16 bytes at phase (l % num) * plen + 8 * (l / num): the tiles fall on the even
-// 16-byte slots of the 256-byte bank row, an odd plen / 4 puts the neighbouring phase on the odd ones (an even one -- 144,
-// 224 -- stacks the phases on one slot).  The two stay apart: they decide the LDS bank placement of each form and the scratch
-// create_bridge budgets for it.
-__host__ __device__ inline int rated_plen(int num, int in_len) { return ((num * RS_FILT - 1 + in_len + num - 1) / num + RS_R + 8 + 3) & ~3; }
-__host__ __device__ inline int updown_plen(int num, int in_len) { return rated_plen(num, in_len) | 4; }
-// of a rational resampler: resample_ratio_kernel's length with plen / 4 odd, as updown_plen and for its reason: lanes
-// (tile, r) and (tile, r + 1) read neighbouring arrays at one offset
-__host__ __device__ inline int rational_plen(int m, int in_len) { return (((RQ_FT * m - 1 + in_len + m - 1) / m + RS_R + 8 + 3) & ~3) | 4; }
-// bytes of a wavefront's scratch for it: two copies of M phase arrays
-__host__ __device__ inline size_t rational_scratch(int m, int in_len) { return (size_t)2 * m * rational_plen(m, in_len) * sizeof(float); }
-
+// ---- the resamplers, one wavefront running one member's (their lengths: rated_plen and its kin, bridge_plan.hpp)
 __device__ __forceinline__ void load_taps(const float *row, f2 (&t2)[RS_FILT / 2]) {
 	const float4 *tp = reinterpret_cast<const float4 *>(row);
 #pragma unroll

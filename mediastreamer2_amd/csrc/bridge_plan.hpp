@@ -1,0 +1,254 @@
+// bridge_plan.hpp -- what creating an mi_bridge decides before anything is allocated, as plain C++ with no HIP in it: the
+// refusals, the kernel family, the LDS layout, the pitches and strides, every leg's ratio byte.  bridge.hip's constructors
+// plan, then allocate what the plan says, then tick by it; tests/host/bridge_plan_check.cpp runs the plan alone on the CPU.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/msmi355x.h"
+#include "../../include/msmi355x_bridge.h"
+
+#ifdef __HIPCC__
+#define MI_PLAN_HD __host__ __device__
+#else
+#define MI_PLAN_HD
+#endif
+
+namespace mi { void set_error(const char *fmt, ...); }
+// plc.hip: what the concealer cannot serve, said for one rate without a device
+int mi_plc_check_rate(const char *fn, const char *what, int index, int rate);
+
+namespace {
+
+constexpr int BT = 256, BMAX = MI_MIXER_MAX_CHANNELS;
+constexpr int RS_FILT = 48, RS_R = 8; // quality 3: 48 taps per polyphase row, fir_tile's eight positions
+constexpr int RQ_FT = 24;             // taps per lane of the rational resamplers: filt_len / M, 48 / 2 and 72 / 3
+constexpr size_t BRIDGE_LDS_MAX = 64 * 1024;
+constexpr size_t RATED_STATIC_LDS = 2048; // bound on a kernel's static LDS (tests/test_bridge_rates_cpu.py holds it)
+
+// ---- the resamplers' lengths, one wavefront running one member's.  floats per phase array of a down-sampler (history ++ tick
+// split by input phase, + the tile FIR's look-ahead): rated_plen behind a pin; updown_plen, the same with plen / 4 odd, in
+// FRONT of one.  Lane l of the tile FIR reads 16 bytes at phase (l % num) * plen + 8 * (l / num): the tiles fall on the even
+// 16-byte slots of the 256-byte bank row, an odd plen / 4 puts the neighbouring phase on the odd ones (an even one -- 144,
+// 224 -- stacks the phases on one slot).  The two stay apart: they decide the LDS bank placement of each form and the scratch
+// plan_bridge budgets for it.
+MI_PLAN_HD inline int rated_plen(int num, int in_len) { return ((num * RS_FILT - 1 + in_len + num - 1) / num + RS_R + 8 + 3) & ~3; }
+MI_PLAN_HD inline int updown_plen(int num, int in_len) { return rated_plen(num, in_len) | 4; }
+// of a rational resampler: resample_ratio_kernel's length with plen / 4 odd, as updown_plen and for its reason: lanes
+// (tile, r) and (tile, r + 1) read neighbouring arrays at one offset
+MI_PLAN_HD inline int rational_plen(int m, int in_len) { return (((RQ_FT * m - 1 + in_len + m - 1) / m + RS_R + 8 + 3) & ~3) | 4; }
+// bytes of a wavefront's scratch for it: two copies of M phase arrays
+MI_PLAN_HD inline size_t rational_scratch(int m, int in_len) { return (size_t)2 * m * rational_plen(m, in_len) * sizeof(float); }
+
+// ---- a member's ratio byte.  Conference rate / leg rate (1, 2, 3 or 6) for a leg at or below the mix; with UD_ABOVE the
+// leg is above it and the low three bits are leg rate / conference rate; with UD_R32 the ratio is 3/2 (the whole part: 1),
+// UD_ABOVE still giving the direction.  The kernels read it through leg_span (bridge_phases.hpp).
+constexpr unsigned UD_ABOVE = 0x80, UD_R32 = 0x40;
+constexpr int NO_WHOLE_RATIO = -1, RATIO_NOT_SERVED = -2;
+
+// The one place where two rates become a ratio byte, or one of the two reasons why there is none.  3/2 or 2/3, both rates
+// multiples of 800: leg and mix are 2400 k and 1600 k Hz, their ticks 24 k and 16 k samples -- 8 k periods of 3 samples against
+// 2: whole periods and whole eight-period tiles, eight-sample groups, both ways
+inline int ratio_byte(int leg, int conf) {
+	if ((int64_t)2 * leg == (int64_t)3 * conf) return (int)(UD_R32 | UD_ABOVE | 1u);
+	if ((int64_t)3 * leg == (int64_t)2 * conf) return (int)(UD_R32 | 1u);
+	const int hi = std::max(leg, conf), lo = std::min(leg, conf);
+	if (hi % lo != 0) return NO_WHOLE_RATIO;
+	const int r = hi / lo;
+	if (r != 1 && r != 2 && r != 3 && r != 6) return RATIO_NOT_SERVED;
+	return leg > conf ? (int)(UD_ABOVE | (unsigned)r) : r;
+}
+
+// ---- a public constructor's rules.  fn: its name, in the texts about the legs' codecs; rates_fn: the name in the texts about
+// rates of a bridge without the per-leg concealer, which is the older constructor's bridge and speaks as that one
+struct Rules {
+	const char *fn, *rates_fn;
+	// above: a leg may be above the mix (and brings the codecs as data and byte rows); leg_plc: cfg->plc with legs that differ in
+	// rate or codec is served by the per-leg concealer, not refused; rational: a leg may be at 3/2 or 2/3 of the mix
+	bool above, leg_plc, rational;
+};
+constexpr Rules RULES_RATED = {"mi_bridge_create_rated", "mi_bridge_create_rated", false, false, false};
+constexpr Rules RULES_LEGS = {"mi_bridge_create_legs", "mi_bridge_create_rated", false, false, false};
+constexpr Rules RULES_ENDPOINTS = {"mi_bridge_create_endpoints", "mi_bridge_create_endpoints", true, false, false};
+constexpr Rules RULES_CONCEALED = {"mi_bridge_create_concealed", "mi_bridge_create_endpoints", true, true, false};
+constexpr Rules RULES_RATIONAL = {"mi_bridge_create_rational", "mi_bridge_create_rational", true, true, true};
+
+struct Plan {
+	// which kernel a tick launches, chosen once: compile-time codecs without and with resamplers, per-leg codecs without and
+	// with them, a leg above the mix, a leg at 3/2 or 2/3 of it
+	enum Family { TICK, RATED, LEGS, LEGS_RATED, UPDOWN, RATIONAL } family = TICK;
+	mi_bridge_config cfg = {}; // in_codec, out_codec: leg 0's where the legs were given
+	int n = 0, nconf = 0, mm = 0, len = 0;
+	// a leg not at the conference's rate (ratio bytes, resamplers, tables); one above the mix by a whole ratio; one at 3/2 or 2/3 of
+	// it; the concealer is the per-leg one, behind every leg's own decoder
+	bool rated = false, updown = false, rational = false, leg_plc = false;
+	bool used[7] = {}, above[7] = {};         // the whole ratios of legs below the mix, and of legs above it
+	bool r32_above = false, r32_below = false; // a leg at 3/2 of the mix, a leg at 2/3
+	int max_ratio = 1, common = 0; // common: the first leg's rate, the one concealer batch's
+	int wide = 0;   // samples per LDS row: the widest leg's tick where one is above the mix
+	int row_w = 0, sum_off = 0, nslice = 0; // 8-byte words per row (odd), the sum row's byte offset, member slices of (C)
+	size_t lds = 0;                         // dynamic LDS of a launch
+	int scratch_off = 0, scratch_per_wave = 0; // bytes: each wavefront's resampler scratch in it
+	int pitch = 0;                          // samples per row of the host buffers: the widest leg's tick
+	size_t in_bytes = 0, out_bytes = 0;     // per stream and tick, on the host side; byte rows' pitch where the codecs are data
+	int hin_stride = RS_FILT, hout_stride = 0; // samples per member of the in_resamplers' and out_resamplers' histories
+	std::vector<int32_t> leg_rate;  // [n], empty: every leg at cfg.rate
+	std::vector<uint8_t> leg_codec; // [n] in_codec | out_codec << 2 where the codecs are the kernel's data; empty: cfg's pair
+	std::vector<uint8_t> ratio;     // [n] ratio bytes, empty unless `rated`
+};
+
+#define MI_PLAN_ARG(cond) if (!(cond)) return mi::set_error("%s:%d invalid argument: %s", __FILE__, __LINE__, #cond), (int)MI_EINVAL
+#define MI_REFUSE(...) return mi::set_error(__VA_ARGS__), (int)MI_ENOTSUP
+
+inline size_t up16(size_t v) { return (v + 15) / 16 * 16; }
+
+// rates [nstreams] or null: every leg at cfg->rate.  codec [nstreams] in_codec | out_codec << 2 (plan_legs has checked them)
+// or null: cfg's pair on every leg.  MI_OK, or the refusal with its text set; *p is whole only with MI_OK.
+inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const int32_t *rates, const uint8_t *codec, Plan *p) {
+	MI_PLAN_ARG(cfg && p);
+	MI_PLAN_ARG(cfg->nstreams > 0 && cfg->members_per_conference > 0 && cfg->members_per_conference <= MI_MIXER_MAX_CHANNELS &&
+	            cfg->nstreams % cfg->members_per_conference == 0);
+	MI_PLAN_ARG(cfg->rate > 0);
+	MI_PLAN_ARG(cfg->in_codec >= MI_SESSION_PCM16 && cfg->in_codec <= MI_SESSION_PCMU && cfg->out_codec >= MI_SESSION_PCM16 &&
+	            cfg->out_codec <= MI_SESSION_PCMU);
+	if (cfg->rate % 800 != 0)
+		MI_REFUSE("mi_bridge_create: rate %d is no multiple of 800 (a 10 ms tick must be whole groups of 8 samples)", cfg->rate);
+	*p = Plan(), p->cfg = *cfg;
+	const int n = p->n = cfg->nstreams, mm = p->mm = cfg->members_per_conference, len = p->len = cfg->rate / 100;
+	p->nconf = n / mm;
+	bool mixed = false, differ = false; // the legs' pairs differ: the codecs are the kernel's data; they or the rates do
+	for (int s = 1; codec && s < n; ++s) mixed |= codec[s] != codec[0], differ |= codec[s] != codec[0] || (rates && rates[s] != rates[0]);
+	p->leg_plc = rules.leg_plc && cfg->plc && differ;
+	const char *fn = p->leg_plc ? rules.fn : rules.rates_fn;
+	// ---- the legs' rates
+	int widest = 0;
+	bool data = mixed || p->leg_plc; // the codecs are the kernel's data and the host rows byte rows
+	for (int s = 0; rates && s < n; ++s) {
+		const int lr = rates[s];
+		MI_PLAN_ARG(lr > 0);
+		const bool up = lr > cfg->rate;
+		int rb = ratio_byte(lr, cfg->rate);
+		if (rb >= 0 && (rb & UD_R32) && !rules.rational) rb = NO_WHOLE_RATIO;
+		if (up && !rules.above)
+			MI_REFUSE("mi_bridge_create_rated: leg %d at %d Hz is above its conference's %d Hz (only legs at or below the mix are resampled)",
+			          s, lr, cfg->rate);
+		const int hi = up ? lr : cfg->rate, lo = up ? cfg->rate : lr;
+		if (rb == NO_WHOLE_RATIO)
+			MI_REFUSE("%s: leg %d at %d Hz in a %d Hz conference is no whole ratio (%.3f); supported: 1, 2, 3, 6%s", fn, s, lr, cfg->rate,
+			          (double)hi / lo, rules.rational ? ", and 3/2 either way" : "");
+		if (rb == RATIO_NOT_SERVED)
+			MI_REFUSE("%s: leg %d at %d Hz in a %d Hz conference is ratio %d; supported: 1, 2, 3, 6%s", fn, s, lr, cfg->rate, hi / lo,
+			          rules.rational ? ", and 3/2 either way" : "");
+		// what holds for a leg of any ratio, checked once that ratio is known to be served: a tick of whole groups, and one rate
+		// for the one concealer batch
+		if (lr % 800 != 0)
+			MI_REFUSE("%s: leg %d's rate %d is no multiple of 800 (a 10 ms tick must be whole groups of 8 samples)", fn, s, lr);
+		if (cfg->plc && !p->leg_plc && p->common && lr != p->common)
+			MI_REFUSE("%s: plc with legs at %d Hz and %d Hz: the concealer batch has one rate", fn, p->common, lr);
+		if (!p->common) p->common = lr;
+		widest = std::max(widest, lr);
+		if (rb & UD_R32) {
+			(up ? p->r32_above : p->r32_below) = true;
+		} else {
+			(up ? p->above : p->used)[rb & 7] = true;
+			p->updown |= up;
+			p->max_ratio = std::max(p->max_ratio, rb & 7);
+		}
+		data |= codec && (rb & (UD_ABOVE | UD_R32)); // (such a leg brings the codecs as data, whether they differ or not)
+		p->ratio.push_back((uint8_t)rb);
+	}
+	p->rational = p->r32_above || p->r32_below; // without such a leg: mi_bridge_create_concealed's bridge exactly
+	p->rated = p->max_ratio > 1 || p->rational;
+	if (!p->rated) p->ratio.clear();
+	// ---- the LDS of a launch.  Samples per row: the widest leg's tick where one is above the mix
+	p->wide = p->updown ? widest / 100 : p->rational ? std::max(len, widest / 100) : len;
+	p->row_w = (p->wide >> 2) | 1;
+	p->sum_off = (int)up16((size_t)mm * p->row_w * 8);
+	p->nslice = std::max(1, std::min(mm, BT / (len >> 2)));
+	size_t lds = p->sum_off + (size_t)len * 4;
+	if (p->rated) {
+		size_t scratch = 0;
+		for (int r = 2; r < 7; ++r) {
+			// each wavefront's scratch: the larger of the forms per used ratio -- up-sampler and down-sampler of a leg below the
+			// mix (in front of the pin, behind it), down-sampler and up-sampler of a leg above it
+			size_t up = 0, down = 0;
+			if (p->used[r]) {
+				up = (size_t)((RS_FILT - 1 + len / r + RS_R + 1 + 3) & ~3) * 4;
+				down = ((size_t)r * rated_plen(r, len) + (size_t)len) * 4;
+			}
+			if (p->above[r]) {
+				up = std::max(up, (size_t)((RS_FILT - 1 + len + RS_R + 1 + 3) & ~3) * 4);
+				down = std::max(down, ((size_t)r * updown_plen(r, r * len) + (size_t)r * len) * 4);
+			}
+			scratch = std::max(scratch, up16(std::max(up, down)));
+		}
+		// a leg at 3/2 of the mix: x 2/3 from its tick in front of the pin, x 3/2 from the mix's behind it; one at 2/3: x 3/2 from
+		// its tick, x 2/3 from the mix's
+		if (p->r32_above) scratch = std::max(scratch, std::max(rational_scratch(3, len / 2 * 3), rational_scratch(2, len)));
+		if (p->r32_below) scratch = std::max(scratch, std::max(rational_scratch(2, len / 3 * 2), rational_scratch(3, len)));
+		const size_t scratch_off = up16(lds);
+		lds = scratch_off + (BT / 64) * scratch;
+		if (lds + RATED_STATIC_LDS > BRIDGE_LDS_MAX)
+			MI_REFUSE("%s: a conference's tick and its resamplers' scratch must fit %zu bytes of LDS (%d members x %d samples "
+			          "= %zu, + %d wavefronts x %zu for ratio %d%s, + %zu of the kernel's own: %zu)",
+			          fn, BRIDGE_LDS_MAX, mm, p->wide, scratch_off, BT / 64, scratch, p->max_ratio, p->rational ? " and 3/2" : "", RATED_STATIC_LDS,
+			          lds + RATED_STATIC_LDS);
+		p->scratch_off = (int)scratch_off, p->scratch_per_wave = (int)scratch;
+		p->hout_stride = p->max_ratio * RS_FILT; // mi_resampler's round_up(filt_len - 1, 8) of the longest filter
+		if (p->rational) p->hout_stride = std::max(p->hout_stride, 3 * RQ_FT); // x 2/3 keeps 71 samples (x 3/2: 47)
+		if (p->updown || p->rational) p->hin_stride = p->hout_stride;          // a down-sampler's history on either side of the pin
+	} else if (lds > BRIDGE_LDS_MAX)
+		MI_REFUSE("mi_bridge_create: a conference's tick must fit %zu bytes of LDS (%d members x %d samples need %zu)", BRIDGE_LDS_MAX, mm, len, lds);
+	p->lds = lds;
+	// ---- the host rows
+	p->pitch = p->rated ? widest / 100 : len;
+	p->in_bytes = (size_t)p->pitch * (cfg->in_codec ? 1 : 2), p->out_bytes = (size_t)p->pitch * (cfg->out_codec ? 1 : 2);
+	if (data) { // byte rows: the widest leg's tick in bytes, rounded up to the 16 bytes a lane loads
+		p->in_bytes = p->out_bytes = 0;
+		for (int s = 0; s < n; ++s) {
+			const size_t ll = (size_t)(rates ? rates[s] : cfg->rate) / 100;
+			p->in_bytes = std::max(p->in_bytes, ll * ((codec[s] & 3) ? 1 : 2));
+			p->out_bytes = std::max(p->out_bytes, ll * ((codec[s] >> 2) ? 1 : 2));
+		}
+		p->in_bytes = up16(p->in_bytes), p->out_bytes = up16(p->out_bytes);
+		p->leg_codec.assign(codec, codec + n);
+	}
+	if (rates) p->leg_rate.assign(rates, rates + n);
+	// the widest form a leg needs: the order matters
+	p->family = p->rational ? Plan::RATIONAL : p->updown ? Plan::UPDOWN : data ? (p->rated ? Plan::LEGS_RATED : Plan::LEGS)
+	            : p->rated  ? Plan::RATED : Plan::TICK;
+	return MI_OK;
+}
+
+// mi_bridge_create_legs and its successors: the legs' codecs checked, the concealer asked about every rate where it will be
+// the per-leg one, then plan_bridge under the same rules with the first leg's pair as the bridge's.  A uniform bridge is
+// mi_bridge_create_rated's, its one pair compile-time in the kernels.
+inline int plan_legs(const Rules &rules, const mi_bridge_config *cfg, const mi_bridge_leg *legs, Plan *p) {
+	MI_PLAN_ARG(cfg && legs && p);
+	MI_PLAN_ARG(cfg->nstreams > 0);
+	const size_t n = (size_t)cfg->nstreams;
+	std::vector<int32_t> rate(n);
+	std::vector<uint8_t> codec(n);
+	int differs = -1; // the first leg whose pair is not leg 0's
+	for (size_t s = 0; s < n; ++s) {
+		const mi_bridge_leg &l = legs[s];
+		for (int v : {l.in_codec, l.out_codec})
+			if (v < MI_SESSION_PCM16 || v > MI_SESSION_PCMU)
+				MI_REFUSE("%s: leg %zu names codec %d; supported: MI_SESSION_PCM16 (0), MI_SESSION_PCMA (1), MI_SESSION_PCMU (2)", rules.fn, s, v);
+		rate[s] = l.rate;
+		codec[s] = (uint8_t)(l.in_codec | l.out_codec << 2);
+		if (differs < 0 && codec[s] != codec[0]) differs = (int)s;
+	}
+	if (rules.leg_plc && cfg->plc) {
+		for (size_t s = 0; s < n; ++s) // what the concealer cannot serve
+			if (const int rc = mi_plc_check_rate(rules.fn, "leg", (int)s, rate[s])) return rc;
+	} else if (differs >= 0 && cfg->plc)
+		MI_REFUSE("%s: plc with leg %d's codecs (in %d, out %d) unlike leg 0's (in %d, out %d): the concealer batch "
+		          "sits behind one decoder", rules.fn, differs, legs[differs].in_codec, legs[differs].out_codec, legs[0].in_codec, legs[0].out_codec);
+	mi_bridge_config c = *cfg;
+	c.in_codec = legs[0].in_codec, c.out_codec = legs[0].out_codec;
+	return plan_bridge(rules, &c, rate.data(), codec.data(), p);
+}
+
+} // namespace

@@ -5,16 +5,14 @@ nothing and use no scratch memory while the three older kernels of plc.hip keep 
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+import kernel_remarks
 from mediastreamer2_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "mediastreamer2_amd", "csrc", "plc.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 NEW = "mi_bridge_create_concealed"
 NEW_KERNELS = ("plc_legs_received_kernel", "plc_legs_conceal_kernel")
 # (VGPRs, TotalSGPRs, LDS bytes / block, scratch bytes / lane, SGPRs spilled, VGPRs spilled) of plc.hip as of commit 7d53fc1,
@@ -76,26 +74,13 @@ def test_lossy_gateway_example_builds(tmp_path):
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    d = tmp_path_factory.mktemp("plc_res")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", SRC, "-o", str(d / "plc_dev.o")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
-def usages(remarks, kernel_substr):
-    out = []
-    for b in re.split(r"remark: Function Name: ", remarks)[1:]:
-        name = b.split()[0]
-        if kernel_substr in name:
-            out.append((name, {m.group(1).strip(): m.group(2).strip() for m in re.finditer(r"remark:\s+([A-Za-z /\[\]]+):\s+(\S+)", b)}))
-    return out
+def remarks():
+    return kernel_remarks.remarks("plc.hip")
 
 
 @pytest.mark.parametrize("kernel", NEW_KERNELS)
 def test_new_kernels_spill_nothing_and_use_no_scratch(remarks, kernel):
-    found = usages(remarks, kernel)
+    found = kernel_remarks.usages(remarks, kernel)
     assert len(found) == 1, [n for n, _ in found]
     name, u = found[0]
     assert int(u["VGPRs Spill"]) == 0 and int(u["SGPRs Spill"]) == 0 and int(u["ScratchSize [bytes/lane]"]) == 0, (name, u)
@@ -103,7 +88,7 @@ def test_new_kernels_spill_nothing_and_use_no_scratch(remarks, kernel):
 
 @pytest.mark.parametrize("kernel", sorted(PARENT))
 def test_older_kernels_keep_their_resources(remarks, kernel):
-    found = usages(remarks, f"{len(kernel)}{kernel}E")  # the mangled name: its length, the name, the end of the nested name
+    found = kernel_remarks.usages(remarks, f"{len(kernel)}{kernel}E")  # the mangled name: its length, the name, the end of the nested name
     assert len(found) == 1, [n for n, _ in found]
     name, u = found[0]
     got = tuple(int(u[k]) for k in ("VGPRs", "TotalSGPRs", "LDS Size [bytes/block]", "ScratchSize [bytes/lane]", "SGPRs Spill", "VGPRs Spill"))

@@ -5,16 +5,14 @@ no scratch memory and keeps its static LDS inside what creation budgets."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+import kernel_remarks
 from mediastreamer2_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "mediastreamer2_amd", "csrc", "bridge.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 NEW = "mi_bridge_create_endpoints"
 KERNEL = "bridge_updown_kernel"
 OLD_KERNELS = ("bridge_tick_kernel", "bridge_rated_kernel", "bridge_legs_kernel")
@@ -63,28 +61,15 @@ def test_wideband_room_example_builds(tmp_path):
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    d = tmp_path_factory.mktemp("bridge_endpoints_res")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", SRC, "-o", str(d / "bridge_dev.o")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
-def usages(remarks, kernel_substr):
-    out = []
-    for b in re.split(r"remark: Function Name: ", remarks)[1:]:
-        name = b.split()[0]
-        if kernel_substr in name:
-            out.append((name, {m.group(1).strip(): m.group(2).strip() for m in re.finditer(r"remark:\s+([A-Za-z /\[\]]+):\s+(\S+)", b)}))
-    return out
+def remarks():
+    return kernel_remarks.remarks("bridge.hip")
 
 
 def test_updown_kernel_spills_nothing_and_fits_the_lds_budget(remarks):
     """one kernel, codec and direction per-member data; mi_bridge_create_endpoints accepts a shape when its dynamic LDS +
     RATED_STATIC_LDS <= 64 KB, so the kernel's static LDS must stay inside that constant"""
-    budget = int(re.search(r"RATED_STATIC_LDS\s*=\s*(\d+)", open(SRC).read()).group(1))
-    found = usages(remarks, KERNEL)
+    budget = kernel_remarks.bridge_budget()[0]
+    found = kernel_remarks.usages(remarks, KERNEL)
     assert len(found) == 1, [n for n, _ in found]
     name, u = found[0]
     assert not any(old in name for old in OLD_KERNELS), name  # the older kernels' pins count instantiations by these names

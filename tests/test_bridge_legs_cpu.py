@@ -4,16 +4,14 @@ kernels of the mixed case spill nothing and the one with the resamplers keeps it
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+import kernel_remarks
 from mediastreamer2_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "mediastreamer2_amd", "csrc", "bridge.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 NEW = ("mi_bridge_create_legs", "mi_bridge_leg_codec", "mi_bridge_leg_bytes")
 KERNEL = "bridge_legs_kernel"  # <false>: legs at the conference's rate; <true>: with the two resamplers
 
@@ -64,28 +62,15 @@ def test_gateway_example_builds(tmp_path):
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    d = tmp_path_factory.mktemp("bridge_legs_res")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", SRC, "-o", str(d / "bridge_dev.o")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
-def usages(remarks, kernel_substr):
-    out = []
-    for b in re.split(r"remark: Function Name: ", remarks)[1:]:
-        name = b.split()[0]
-        if kernel_substr in name:
-            out.append((name, {m.group(1).strip(): m.group(2).strip() for m in re.finditer(r"remark:\s+([A-Za-z /\[\]]+):\s+(\S+)", b)}))
-    return out
+def remarks():
+    return kernel_remarks.remarks("bridge.hip")
 
 
 def test_mixed_kernels_spill_nothing_and_fit_the_lds_budget(remarks):
     """one form without resamplers, one with; mi_bridge_create_legs accepts a rated shape when its dynamic LDS +
     RATED_STATIC_LDS <= 64 KB, so the rated form's static LDS must stay inside that constant"""
-    budget = int(re.search(r"RATED_STATIC_LDS\s*=\s*(\d+)", open(SRC).read()).group(1))
-    legs = dict(usages(remarks, KERNEL))
+    budget = kernel_remarks.bridge_budget()[0]
+    legs = dict(kernel_remarks.usages(remarks, KERNEL))
     plain = [n for n in legs if f"{KERNEL}ILb0E" in n]
     rated = [n for n in legs if f"{KERNEL}ILb1E" in n]
     assert len(legs) == 2 and len(plain) == 1 and len(rated) == 1, sorted(legs)

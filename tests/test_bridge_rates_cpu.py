@@ -4,16 +4,14 @@ rated kernel spills nothing and keeps its static LDS inside what mi_bridge_creat
 kernel is built exactly as before."""
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+import kernel_remarks
 from mediastreamer2_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "mediastreamer2_amd", "csrc", "bridge.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 NEW = ("mi_bridge_create_rated", "mi_bridge_leg_rate")
 
 # (VGPRs, static LDS bytes) of bridge_tick_kernel<IN, OUT> per input kind, recorded from a build of the commit BEFORE the rated
@@ -46,31 +44,16 @@ def test_header_is_still_plain_c99(tmp_path):
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    d = tmp_path_factory.mktemp("bridge_res")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", SRC, "-o", str(d / "bridge_dev.o")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
-def usages(remarks, kernel_substr):
-    out = []
-    for b in re.split(r"remark: Function Name: ", remarks)[1:]:
-        name = b.split()[0]
-        if kernel_substr in name:
-            out.append((name, {m.group(1).strip(): m.group(2).strip() for m in re.finditer(r"remark:\s+([A-Za-z /\[\]]+):\s+(\S+)", b)}))
-    return out
+def remarks():
+    return kernel_remarks.remarks("bridge.hip")
 
 
 def test_rated_kernel_spills_nothing_and_fits_its_lds_budget(remarks):
     """mi_bridge_create_rated accepts a shape when its dynamic LDS + RATED_STATIC_LDS <= 64 KB: every instantiation's static
     LDS must stay inside that constant, so the largest accepted shape is inside 64 KB"""
-    src = open(SRC).read()
-    budget = int(re.search(r"RATED_STATIC_LDS\s*=\s*(\d+)", src).group(1))
-    limit = re.search(r"BRIDGE_LDS_MAX\s*=\s*(\d+)\s*\*\s*(\d+)", src)
-    assert int(limit.group(1)) * int(limit.group(2)) == 65536 and "lds + RATED_STATIC_LDS > BRIDGE_LDS_MAX" in src
-    rated = usages(remarks, "bridge_rated_kernel")
+    budget, limit, src = kernel_remarks.bridge_budget()
+    assert limit == 65536 and "lds + RATED_STATIC_LDS > BRIDGE_LDS_MAX" in src
+    rated = kernel_remarks.usages(remarks, "bridge_rated_kernel")
     assert len(rated) == 9, [n for n, _ in rated]
     for name, u in rated:
         assert int(u["VGPRs Spill"]) == 0 and int(u["SGPRs Spill"]) == 0 and int(u["ScratchSize [bytes/lane]"]) == 0, (name, u)
@@ -78,7 +61,7 @@ def test_rated_kernel_spills_nothing_and_fits_its_lds_budget(remarks):
 
 
 def test_same_rate_kernel_is_built_as_before(remarks):
-    tick = usages(remarks, "bridge_tick_kernel")
+    tick = kernel_remarks.usages(remarks, "bridge_tick_kernel")
     assert len(tick) == 9, [n for n, _ in tick]
     for name, u in tick:
         kind = int(re.search(r"bridge_tick_kernelILi(\d)ELi\dE", name).group(1))

@@ -5,16 +5,14 @@ uses no scratch memory and keeps its static LDS inside what creation budgets."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+import kernel_remarks
 from mediastreamer2_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "mediastreamer2_amd", "csrc", "bridge.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 NEW = "mi_bridge_create_rational"
 OLD_KERNELS = ("bridge_tick_kernel", "bridge_rated_kernel", "bridge_legs_kernel", "bridge_updown_kernel")
 
@@ -64,28 +62,16 @@ def test_superwideband_room_example_builds(tmp_path):
 
 
 @pytest.fixture(scope="module")
-def remarks(tmp_path_factory):
-    d = tmp_path_factory.mktemp("bridge_rational_res")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", SRC, "-o", str(d / "bridge_dev.o")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
-def kernels(remarks):
-    """(name, resource usage) of every __global__ function of the unit"""
-    out = []
-    for b in re.split(r"remark: Function Name: ", remarks)[1:]:
-        out.append((b.split()[0], {m.group(1).strip(): m.group(2).strip() for m in re.finditer(r"remark:\s+([A-Za-z /\[\]]+):\s+(\S+)", b)}))
-    return [(n, u) for n, u in out if "kernel" in n]
+def remarks():
+    return kernel_remarks.remarks("bridge.hip")
 
 
 def test_one_new_kernel_that_spills_nothing_and_fits_the_lds_budget(remarks):
     """exactly one kernel beside the four older families, whatever it is called; direction, ratio and codec are per-member
     data.  mi_bridge_create_rational accepts a shape when its dynamic LDS + RATED_STATIC_LDS <= 64 KB, so the kernel's
     static LDS must stay inside that constant"""
-    budget = int(re.search(r"RATED_STATIC_LDS\s*=\s*(\d+)", open(SRC).read()).group(1))
-    new = [(n, u) for n, u in kernels(remarks) if not any(old in n for old in OLD_KERNELS)]
+    budget = kernel_remarks.bridge_budget()[0]
+    new = [(n, u) for n, u in kernel_remarks.kernels(remarks) if not any(old in n for old in OLD_KERNELS)]
     assert len(new) == 1, [n for n, _ in new]
     name, u = new[0]
     assert "rational" in name, name

@@ -11,150 +11,19 @@ import numpy as np
 import pytest
 
 import mediastreamer2_amd as ms
+from bridge_parts import LAW, NTICKS, assert_same_meters, assert_same_rows, leg_rows, loss_patterns, mk, one_tick  # noqa: F401 (mk: a fixture)
+from bridge_parts import ConcealedParts as Parts
+from bridge_parts import up16 as _up16
 from mediastreamer2_amd import _lib
-from test_gpu_plc import voiced
 
 pytestmark = pytest.mark.gpu
 
 PCM16, PCMA, PCMU = ms.MI_SESSION_PCM16, ms.MI_SESSION_PCMA, ms.MI_SESSION_PCMU
-LAW = {PCMA: ms.MI_LAW_PCMA, PCMU: ms.MI_LAW_PCMU}
-R, C_ = ms.MI_PLC_RECEIVED, ms.MI_PLC_CONCEAL
-NTICKS, MM = 45, 3
+MM = 3
 
 GATEWAY16 = [(8000, PCMU, PCMU), (8000, PCMA, PCMU), (16000, PCM16, PCM16), (48000, PCM16, PCM16), (8000, PCMA, PCMA), (16000, PCMU, PCM16)]
 CODECS8 = [(8000, PCMU, PCMU), (8000, PCMA, PCM16), (8000, PCM16, PCMA), (8000, PCMA, PCMA), (8000, PCM16, PCM16), (8000, PCMU, PCMA)]
 RATES16 = [(8000, PCMU, PCMA), (16000, PCMU, PCMA)] * 3
-
-
-@pytest.fixture
-def mk(ctx):
-    """factory(cls, ...) whose objects are closed with the test, passed or failed, while the context is still there"""
-    made = []
-
-    def make(cls, *a, **kw):
-        made.append(cls(ctx, *a, **kw))
-        return made[-1]
-    yield make
-    for b in reversed(made):
-        b.close()
-
-
-def _up16(v):
-    return (int(v) + 15) & ~15
-
-
-def loss_patterns(n, nticks=NTICKS, seed=7):
-    """present [nticks, n]: per leg none / single losses / a 12-tick burst (past about 90 ms the generated signal is extended
-    from itself: the second fftbf) / a 25-tick outage (fade, silence, the cross-fade back) / loss on ticks 0-1 / 15 % random"""
-    rng = np.random.default_rng(seed)
-    present = np.ones((nticks, n), np.uint8)
-    for s in range(n):
-        kind = s % 6
-        if kind == 1:
-            present[[10, 25, 40], s] = 0
-        elif kind == 2:
-            present[14:26, s] = 0
-        elif kind == 3:
-            present[12:37, s] = 0
-        elif kind == 4:
-            present[0:2, s] = 0
-        elif kind == 5:
-            present[:, s] = rng.random(nticks) >= 0.15
-    return present
-
-
-def leg_rows(oracle, legs, nticks=NTICKS, seed=0, talk=None):
-    """[nticks, n, pitch] uint8: every leg's voiced signal through its own encoder at the head of its byte row, the tails
-    random (they must be ignored).  talk: the legs that speak; the others send digital silence"""
-    n = len(legs)
-    pitch = _up16(max(r // 100 * (1 if ic else 2) for r, ic, _ in legs))
-    rng = np.random.default_rng(0xC0 + seed)
-    x = rng.integers(0, 256, (nticks, n, pitch), dtype=np.uint8)
-    for s, (rate, ic, _) in enumerate(legs):
-        ll = rate // 100
-        sig = voiced(seed + s, ll * nticks, rate) if talk is None or s in talk else np.zeros(ll * nticks, np.int16)
-        sig = sig.reshape(nticks, ll)
-        if ic == PCM16:
-            x[:, s, :2 * ll] = sig.view(np.uint8)
-        else:
-            x[:, s, :ll] = oracle.g711_encode(LAW[ic], sig)
-    return x
-
-
-class Parts:
-    """the stages one by one over byte rows laid out as the bridge's: the decoders, a PlcBatch per distinct rate over all n
-    rows, and the plc-less bridge (`inner`) that takes the concealed PCM"""
-
-    def __init__(self, ctx, mk, mm, conf, legs):
-        import torch
-        self.t = torch
-        legs = np.asarray(legs, np.int32)
-        self.ctx, self.n = ctx, len(legs)
-        self.rates, self.ic, self.oc = legs[:, 0].copy(), legs[:, 1].copy(), legs[:, 2].copy()
-        self.leg_len = self.rates // 100
-        self.width = int(self.leg_len.max())
-        self.in_bytes = self.leg_len * np.where(self.ic, 1, 2)
-        self.plc = {int(r): mk(ms.PlcBatch, self.n, int(r), max_block=self.width) for r in sorted(set(self.rates))}
-        self.inner = mk(ms.Bridge, self.n, members=mm, rate=conf, endpoints=[(r, PCM16, oc) for r, oc in zip(self.rates, self.oc)])
-        assert self.inner.tick_bytes()[0] == 2 * self.width
-        self.pcm = torch.zeros((self.n, self.width), dtype=torch.int16, device="cuda")
-        self.lens = self._dev(self.leg_len.astype(np.int32))
-        self.law_lens = {c: self._dev(np.where(self.ic == c, self.leg_len, 0).astype(np.int32)) for c in LAW if (self.ic == c).any()}
-        torch.cuda.synchronize()
-
-    def _dev(self, a):
-        return self.t.from_numpy(np.ascontiguousarray(a)).cuda()
-
-    def restart(self, s):
-        """a new endpoint's concealer on stream s"""
-        self.plc[int(self.rates[s])].reset(s, 1)
-
-    def conceal(self, x, present):
-        """the decoders and the concealers: [n, width] int16, a leg's tick at the head of its row"""
-        t, n = self.t, self.n
-        pcm = np.zeros((n, self.width), np.int16)
-        for s in np.nonzero(self.ic == PCM16)[0]:
-            pcm[s, :self.leg_len[s]] = x[s, :self.in_bytes[s]].view(np.int16)
-        arrive = self._dev(x)
-        modes = {r: self._dev(np.where(self.rates == r, np.where(present, R, C_), 0).astype(np.uint8)) for r in self.plc}
-        self.ctx.sync()
-        self.pcm.copy_(self._dev(pcm))
-        t.cuda.synchronize()
-        for c, lens in self.law_lens.items():
-            ms.g711_decode(self.ctx, LAW[c], arrive, self.pcm, length=self.width, lens=lens)
-        for r, plc in self.plc.items():
-            plc.process(self.pcm, self.lens, modes[r])
-        self.ctx.sync()
-        return self.pcm.cpu().numpy()
-
-    def tick(self, x, present):
-        pcm = self.conceal(x, present)
-        h_in, h_present = self.inner.acquire()
-        h_in[:] = pcm.view(np.uint8)
-        assert h_present.all()
-        self.inner.submit()
-        return self.inner.collect().copy()
-
-
-def one_tick(br, x, present):
-    h_in, h_present = br.acquire()
-    assert h_present.all()
-    h_in[:] = x
-    h_present[:] = present
-    br.submit()
-    return br.collect().copy()
-
-
-def assert_same_rows(br, got, want, t):
-    for s in range(br.n):
-        np.testing.assert_array_equal(br.leg_out(got, s), br.leg_out(want, s), err_msg=f"tick {t} leg {s}")
-
-
-def assert_same_meters(br, inner):
-    assert bytes(br.volume_state()) == bytes(inner.volume_state())
-    np.testing.assert_array_equal(br.levels().view(np.uint32), inner.levels().view(np.uint32))
-    for a, b in zip(br.active_speakers(), inner.active_speakers()):
-        np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def tiled(legs, n):

@@ -8,168 +8,15 @@ import numpy as np
 import pytest
 
 import mediastreamer2_amd as ms
+from bridge_parts import mk  # noqa: F401 (a fixture)
+from bridge_parts import one_tick as _one_tick
+from bridge_parts import pair as _pair
 from mediastreamer2_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
 PCM16, PCMA, PCMU = ms.MI_SESSION_PCM16, ms.MI_SESSION_PCMA, ms.MI_SESSION_PCMU
 L, A, O = ms.MI_MIX_LINKED, ms.MI_MIX_ACTIVE, ms.MI_MIX_OUTPUT
-LAW = {PCMA: ms.MI_LAW_PCMA, PCMU: ms.MI_LAW_PCMU}
-
-
-@pytest.fixture
-def mk(ctx):
-    """factory(cls, ...) whose objects are closed with the test, passed or failed, while the context is still there"""
-    made = []
-
-    def make(cls, *a, **kw):
-        made.append(cls(ctx, *a, **kw))
-        return made[-1]
-    yield make
-    for b in reversed(made):
-        b.close()
-
-
-def _up16(v):
-    return (int(v) + 15) & ~15
-
-
-def _one_tick(br, x, present=None):
-    h_in, h_present = br.acquire()
-    assert h_present.all()
-    h_in[:] = x
-    if present is not None:
-        h_present[:] = present
-    br.submit()
-    return br.collect().copy()
-
-
-class Parts:
-    """the stages called one by one over byte rows laid out as the bridge's: every batch over all n streams with a run mask
-    / a length of 0 for the streams that are not its own"""
-
-    def __init__(self, ctx, mk, mm, conf, legs):
-        import torch
-        self.t = torch
-        legs = np.asarray(legs, np.int32)
-        self.ctx, self.n, self.mm, self.conf, self.ns = ctx, len(legs), mm, conf, conf // 100
-        n = self.n
-        self.rates, self.ic, self.oc = legs[:, 0].copy(), legs[:, 1].copy(), legs[:, 2].copy()
-        self.leg_len = self.rates // 100
-        self.in_bytes = self.leg_len * np.where(self.ic, 1, 2)
-        self.out_bytes = self.leg_len * np.where(self.oc, 1, 2)
-        self.in_pitch, self.out_pitch = _up16(self.in_bytes.max()), _up16(self.out_bytes.max())
-        self.distinct = sorted(set(int(r) for r in self.rates))
-        self.vol = {r: mk(ms.VolumeBatch, n, r) for r in self.distinct}
-        self.up = {r: mk(ms.ResamplerBatch, n, r, conf) for r in self.distinct if r != conf}
-        self.down = {r: mk(ms.ResamplerBatch, n, conf, r) for r in self.distinct if r != conf}
-        self.mix = mk(ms.MixerBatch, n // mm, mm, self.ns)
-        self.flags = np.full(n, L | A | O, np.uint8)
-        self.gain = np.ones(n, np.float32)
-        # a row that is not written keeps what ITS staging slot held; the bridge rotates three slots, one per tick
-        self.held = np.zeros((3, n, self.out_pitch), np.uint8)
-        self.ticks = 0
-        z = lambda cols, dt=torch.int16: torch.zeros((n, cols), dtype=dt, device="cuda")
-        self.pcm, self.wide, self.mixed, self.back = z(self.ns), z(self.ns), z(self.ns), z(self.ns)
-        self.codes_out = z(self.out_pitch, torch.uint8)
-        torch.cuda.synchronize()
-
-    def rows(self, rng):
-        """a tick of input rows: every byte random (the tails must be ignored), PCM legs a moderate noise"""
-        x = rng.integers(0, 256, (self.n, self.in_pitch), dtype=np.uint8)
-        for s in np.nonzero(self.ic == PCM16)[0]:
-            x[s, :self.in_bytes[s]] = rng.normal(0.0, 5000.0, self.leg_len[s]).astype(np.int16).view(np.uint8)
-        return x
-
-    def set_params(self, params):
-        for v in self.vol.values():
-            v.set_params(params)
-
-    def set_controls(self):
-        self.mix.set_controls(flags=self.flags, gain=self.gain)
-
-    def restart(self, s):
-        """a NEW endpoint on stream s: fresh MSVolume, fresh resamplers"""
-        r = int(self.rates[s])
-        st = ms.VolumeState()
-        st.gain = st.target_gain = st.ng_gain = 1.0
-        self.vol[r].set_state([st], first=s)
-        self.vol[r].reset_max(s, 1)
-        if r in self.up:
-            self.up[r].reset(s, 1)
-            self.down[r].reset(s, 1)
-
-    def _dev(self, a):
-        return self.t.from_numpy(np.ascontiguousarray(a)).cuda()
-
-    def tick(self, x, present=None):
-        t, n, ns, Lb = self.t, self.n, self.ns, self.ctx.L
-        present = np.ones(n, np.uint8) if present is None else np.asarray(present, np.uint8)
-        linked, output = (self.flags & L) != 0, (self.flags & O) != 0
-        # decoders: the PCM legs' samples copied, then one mi_g711_decode per law over that law's rows
-        pcm = np.zeros((n, ns), np.int16)
-        for s in np.nonzero(self.ic == PCM16)[0]:
-            pcm[s, :self.leg_len[s]] = x[s, :self.in_bytes[s]].view(np.int16)
-        arrive = self._dev(x)
-        law_in = {c: self._dev(np.where(self.ic == c, self.leg_len, 0).astype(np.int32)) for c in LAW if (self.ic == c).any()}
-        law_out = {c: self._dev(np.where(self.oc == c, self.leg_len, 0).astype(np.int32)) for c in LAW if (self.oc == c).any()}
-        masks = {r: (self._dev((present != 0) & (self.rates == r) & linked), self._dev(output & (self.rates == r)),
-                     self._dev(np.where((present != 0) & (self.rates == r), self.leg_len, 0).astype(np.int32))) for r in self.distinct}
-        has = self._dev(present)
-        same = self._dev(self.rates == self.conf)
-        self.ctx.sync()
-        self.pcm.copy_(self._dev(pcm))
-        self.wide.zero_()
-        self.codes_out.zero_()
-        t.cuda.synchronize()
-        for c, lens in law_in.items():
-            ms.g711_decode(self.ctx, LAW[c], arrive, self.pcm, length=int(self.leg_len.max()), lens=lens)
-        for r in self.distinct:
-            self.vol[r].process(self.pcm, nsamples=int(r) // 100, per_stream=masks[r][2])
-        for r, rs in self.up.items():
-            ms.check(Lb.mi_resampler_process_masked(rs.h, ms._ptr(self.pcm), r // 100, ns, ms._ptr(self.wide), ns, None, ms._ptr(masks[r][0])))
-        self.ctx.sync()
-        self.wide[same] = self.pcm[same]
-        t.cuda.synchronize()
-        self.mix.process(self.wide.view(n // self.mm, self.mm, ns), has, 1, self.mixed.view(n // self.mm, self.mm, ns))
-        for r, rs in self.down.items():
-            ms.check(Lb.mi_resampler_process_masked(rs.h, ms._ptr(self.mixed), ns, ns, ms._ptr(self.back), ns, None, ms._ptr(masks[r][1])))
-        self.ctx.sync()
-        self.back[same] = self.mixed[same]
-        t.cuda.synchronize()
-        for c, lens in law_out.items():
-            ms.g711_encode(self.ctx, LAW[c], self.back, self.codes_out, length=int(self.leg_len.max()), lens=lens)
-        self.ctx.sync()
-        codes, back = self.codes_out.cpu().numpy(), self.back.cpu().numpy()
-        held = self.held[self.ticks % 3]
-        self.ticks += 1
-        for s in np.nonzero(output)[0]:
-            ll = self.leg_len[s]
-            held[s, :self.out_bytes[s]] = codes[s, :ll] if self.oc[s] else back[s, :ll].view(np.uint8)
-        return held.copy()
-
-    def state_bytes(self):
-        st = {r: self.vol[r].get_state() for r in self.distinct}
-        return b"".join(bytes(st[int(self.rates[s])][s]) for s in range(self.n))
-
-    def maxima(self):
-        mx = {r: self.vol[r].get_max() for r in self.distinct}
-        return np.array([mx[int(self.rates[s])][s] for s in range(self.n)], np.float32)
-
-    def check_state(self, br):
-        assert bytes(br.volume_state()) == self.state_bytes()
-        np.testing.assert_array_equal(br.volume_max().view(np.uint32), self.maxima().view(np.uint32))
-
-
-def _pair(br, ctx, mk, mm, conf, legs):
-    parts = Parts(ctx, mk, mm, conf, legs)
-    assert br.tick_bytes() == (parts.in_pitch, parts.out_pitch)
-    for s in range(parts.n):
-        assert br.leg_codec(s) == (parts.ic[s], parts.oc[s]) and br.leg_bytes(s) == (parts.in_bytes[s], parts.out_bytes[s])
-        assert br.leg_rate(s) == parts.rates[s]
-    return parts
-
-
 def _run_with_controls(br, parts, nticks, seed):
     """AGC and DC removal on, an inactive pin, an input gain != 1, a pin with its output off (moved to another pin half
     way), a seeded fifth of the legs absent per tick"""

@@ -12,6 +12,10 @@ import numpy as np
 import pytest
 
 import mediastreamer2_amd as ms
+from bridge_parts import FLOAT_STATE, INT_STATE, mk  # noqa: F401 (mk: a fixture)
+from bridge_parts import SampleParts as Parts
+from bridge_parts import bits as _bits
+from bridge_parts import one_tick as _one_tick
 from conftest import synth_pcm
 from mediastreamer2_amd import _lib
 
@@ -19,153 +23,8 @@ pytestmark = pytest.mark.gpu
 
 PCM16, PCMA, PCMU = ms.MI_SESSION_PCM16, ms.MI_SESSION_PCMA, ms.MI_SESSION_PCMU
 L, A, O = ms.MI_MIX_LINKED, ms.MI_MIX_ACTIVE, ms.MI_MIX_OUTPUT
-FLOAT_STATE = ("energy", "level_pk", "instant_energy", "lt_speaker_en", "gain", "target_gain", "ng_gain")
-INT_STATE = ("dc_offset", "sustain_dur", "ng_noise_dur", "fast_upramp")
-
-
 def _law(codec):
     return ms.MI_LAW_PCMA if codec == PCMA else ms.MI_LAW_PCMU
-
-
-def _bits(f):
-    return np.float32(f).view(np.uint32)
-
-
-@pytest.fixture
-def mk(ctx):
-    """factory(cls, ...) whose objects are closed with the test, passed or failed, while the context is still there"""
-    made = []
-
-    def make(cls, *a, **kw):
-        made.append(cls(ctx, *a, **kw))
-        return made[-1]
-    yield make
-    for b in reversed(made):
-        b.close()
-
-
-def _one_tick(br, x, present=None):
-    h_in, h_present = br.acquire()
-    assert h_present.all()
-    h_in[:] = x
-    if present is not None:
-        h_present[:] = present
-    br.submit()
-    return br.collect().copy()
-
-
-class Parts:
-    """the yardstick on the C ABI: the stages called one by one, every batch over all n streams with a run mask / a length
-    of 0 for the streams that are not its own"""
-
-    def __init__(self, ctx, mk, n, mm, conf, rates, in_codec, out_codec, plc=False):
-        import torch
-        self.t = torch
-        self.ctx, self.n, self.mm, self.conf, self.ns = ctx, n, mm, conf, conf // 100
-        self.rates = np.asarray(rates, np.int32)
-        self.leg_len = self.rates // 100
-        self.pitch = int(self.leg_len.max())
-        self.in_codec, self.out_codec = in_codec, out_codec
-        self.distinct = sorted(set(int(r) for r in self.rates))
-        self.vol = {r: mk(ms.VolumeBatch, n, r) for r in self.distinct}
-        self.up = {r: mk(ms.ResamplerBatch, n, r, conf) for r in self.distinct if r != conf}
-        self.down = {r: mk(ms.ResamplerBatch, n, conf, r) for r in self.distinct if r != conf}
-        self.mix = mk(ms.MixerBatch, n // mm, mm, self.ns)
-        self.plc = mk(ms.PlcBatch, n, self.distinct[0], max_block=self.pitch) if plc else None
-        self.flags = np.full(n, L | A | O, np.uint8)
-        self.gain = np.ones(n, np.float32)
-        # what the bridge's output rows hold: a row that is not written keeps what ITS staging slot held, and the bridge
-        # rotates three slots, one per tick
-        self.held = np.zeros((3, n, self.pitch), np.uint8 if out_codec else np.int16)
-        self.ticks = 0
-        z = lambda cols, dt=torch.int16: torch.zeros((n, cols), dtype=dt, device="cuda")
-        self.pcm, self.wide, self.mixed, self.back = z(self.ns), z(self.ns), z(self.ns), z(self.ns)
-        self.codes_out = z(self.pitch, torch.uint8)
-        torch.cuda.synchronize()
-
-    def set_params(self, params):
-        for v in self.vol.values():
-            v.set_params(params)
-
-    def set_controls(self):
-        self.mix.set_controls(flags=self.flags, gain=self.gain)
-
-    def restart(self, s):
-        """a NEW endpoint on stream s: fresh MSVolume, fresh resamplers"""
-        r = int(self.rates[s])
-        st = ms.VolumeState()
-        st.gain = st.target_gain = st.ng_gain = 1.0
-        self.vol[r].set_state([st], first=s)
-        self.vol[r].reset_max(s, 1)
-        if r in self.up:
-            self.up[r].reset(s, 1)
-            self.down[r].reset(s, 1)
-
-    def _dev(self, a):
-        return self.t.from_numpy(np.ascontiguousarray(a)).cuda()
-
-    def tick(self, x, present=None):
-        t, n, ns, Lb = self.t, self.n, self.ns, self.ctx.L
-        present = np.ones(n, np.uint8) if present is None else np.asarray(present, np.uint8)
-        linked, output = (self.flags & L) != 0, (self.flags & O) != 0
-        arrive = self._dev(x)
-        masks = {r: (self._dev((present != 0) & (self.rates == r) & linked), self._dev(output & (self.rates == r)),
-                     self._dev(np.where((present != 0) & (self.rates == r), self.leg_len, 0).astype(np.int32))) for r in self.distinct}
-        has = self._dev(present)
-        self.wide.zero_()
-        t.cuda.synchronize()
-        if self.in_codec:
-            ms.g711_decode(self.ctx, _law(self.in_codec), arrive, self.pcm, length=self.pitch)
-        else:
-            self.ctx.sync()
-            self.pcm[:, :self.pitch] = arrive
-            t.cuda.synchronize()
-        if self.plc is not None:
-            modes = self._dev(np.where(present, ms.MI_PLC_RECEIVED, ms.MI_PLC_CONCEAL).astype(np.uint8))
-            lens = self._dev(self.leg_len.astype(np.int32))
-            t.cuda.synchronize()
-            self.plc.process(self.pcm, lens, modes)
-            present = np.ones(n, np.uint8)  # a concealed leg counts as present
-            masks = {r: (self._dev((self.rates == r) & linked), m[1], lens) for r, m in masks.items()}
-            has = self._dev(present)
-            t.cuda.synchronize()
-        for r in self.distinct:
-            self.vol[r].process(self.pcm, nsamples=int(r) // 100, per_stream=masks[r][2])
-        for r, rs in self.up.items():
-            ms.check(Lb.mi_resampler_process_masked(rs.h, ms._ptr(self.pcm), r // 100, ns, ms._ptr(self.wide), ns, None, ms._ptr(masks[r][0])))
-        self.ctx.sync()
-        same = self._dev(self.rates == self.conf)
-        self.wide[same] = self.pcm[same]
-        t.cuda.synchronize()
-        self.mix.process(self.wide.view(n // self.mm, self.mm, ns), has, 1, self.mixed.view(n // self.mm, self.mm, ns))
-        for r, rs in self.down.items():
-            ms.check(Lb.mi_resampler_process_masked(rs.h, ms._ptr(self.mixed), ns, ns, ms._ptr(self.back), ns, None, ms._ptr(masks[r][1])))
-        self.ctx.sync()
-        self.back[same] = self.mixed[same]
-        t.cuda.synchronize()
-        if self.out_codec:
-            ms.g711_encode(self.ctx, _law(self.out_codec), self.back, self.codes_out, length=self.pitch)
-            self.ctx.sync()
-            res = self.codes_out.cpu().numpy()
-        else:
-            res = self.back.cpu().numpy()[:, :self.pitch]
-        held = self.held[self.ticks % 3]
-        self.ticks += 1
-        for s in np.nonzero(output)[0]:
-            held[s, :self.leg_len[s]] = res[s, :self.leg_len[s]]
-        return held.copy()
-
-    def state_bytes(self):
-        st = {r: self.vol[r].get_state() for r in self.distinct}
-        return b"".join(bytes(st[int(self.rates[s])][s]) for s in range(self.n))
-
-    def maxima(self):
-        mx = {r: self.vol[r].get_max() for r in self.distinct}
-        return np.array([mx[int(self.rates[s])][s] for s in range(self.n)], np.float32)
-
-    def check_state(self, br):
-        assert bytes(br.volume_state()) == self.state_bytes()
-        np.testing.assert_array_equal(br.volume_max().view(np.uint32), self.maxima().view(np.uint32))
 
 
 def _rates(n, case):

@@ -2,7 +2,7 @@
 a 32 kHz member of a 48 kHz room, a 24 kHz member of a 16 kHz one, 12 kHz in 8 kHz -- the resampler's 3/2 and 2/3 tile-FIR
 arithmetic inside the bridge's one launch per tick (bridge_rational_kernel), next to legs at 1, 2, 3 and 6 below and above.
 
-The yardstick is tests/test_gpu_bridge_endpoints.py's Parts on the C ABI -- mi_g711_decode once per law ->
+The yardstick is tests/bridge_parts.py's Parts on the C ABI -- mi_g711_decode once per law ->
 mi_volume_process (a batch per leg rate) -> mi_resampler_process_masked (leg -> conference) -> mi_mixer_process ->
 mi_resampler_process_masked (conference -> leg) -> mi_g711_encode once per law -- and every comparison with it is BIT-EXACT
 over all legs, samples and ticks: output bytes, mi_volume_state bytes, meter maxima.  Every shape here lies where
@@ -11,19 +11,19 @@ at most 30 KB of LDS; the widest input here is 480 samples) -- past that it take
 another order.  Against the oracle chain the meters are bit-exact and the audio is held to the float resampler path's
 tolerance (tests/test_gpu_resample.py): 1e-4 RMS of full scale and at most 1 LSB."""
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import mediastreamer2_amd as ms
+from bridge_parts import FLOAT_STATE, INT_STATE, ConcealedParts, assert_same_meters, assert_same_rows, leg_rows, loss_patterns, mk, one_tick  # noqa: F401 (mk: a fixture)
+from bridge_parts import bits as _bits
+from bridge_parts import one_tick as _one_tick
+from bridge_parts import pair as _pair
 from conftest import synth_pcm
+from kernel_remarks import bridge_budget, bridge_lds
 from mediastreamer2_amd import _lib
-from test_gpu_bridge_concealed import Parts as ConcealedParts
-from test_gpu_bridge_concealed import assert_same_meters, assert_same_rows, leg_rows, loss_patterns, one_tick
-from test_gpu_bridge_endpoints import FLOAT_STATE, INT_STATE, LAW, _bits, _one_tick, mk  # noqa: F401 (mk: a fixture)
-from test_gpu_bridge_endpoints import Parts as EndpointParts
 
 pytestmark = pytest.mark.gpu
 
@@ -39,83 +39,6 @@ CASES = {
     "c-12k-ulaw-in-8k": (8000, [(12000, PCMU, PCMU), (8000, PCMU, PCMU), (12000, PCMU, PCM16), (8000, *P16), (12000, PCMU, PCMU)]),
     "d-16k-36k-in-24k": (24000, [(16000, *P16), (36000, *P16), (24000, *P16), (36000, *P16), (16000, *P16)]),
 }
-
-
-class Parts(EndpointParts):
-    """tests/test_gpu_bridge_endpoints.py's parts with room for the 3/2 and 2/3 resamplers, which like every resampler
-    that is no whole up-sampler want mi_resampler_out_capacity = out_len + 1 samples per output row: the rows at the legs'
-    rates are eight samples wider than the widest leg's tick, and an in_resampler of either new ratio writes the roomy
-    rows the down-samplers in front of a pin write there, from which the rows that ran are moved onto the mixer's"""
-
-    def __init__(self, ctx, mk, mm, conf, legs, plc=False):
-        super().__init__(ctx, mk, mm, conf, legs, plc=plc)
-        self.width += 8
-        self.pcm, self.back = (self.t.zeros((self.n, self.width), dtype=self.t.int16, device="cuda") for _ in range(2))
-        self.t.cuda.synchronize()
-
-    def tick(self, x, present=None):
-        t, n, ns, W, Lb = self.t, self.n, self.ns, self.width, self.ctx.L
-        present = np.ones(n, np.uint8) if present is None else np.asarray(present, np.uint8)
-        linked, output = (self.flags & L) != 0, (self.flags & O) != 0
-        roomy = lambda r: r > self.conf or self.conf % r != 0  # the in_resampler is no whole up-sampler
-        # decoders: the PCM legs' samples copied, then one mi_g711_decode per law over that law's rows
-        pcm = np.zeros((n, W), np.int16)
-        for s in np.nonzero(self.ic == PCM16)[0]:
-            pcm[s, :self.leg_len[s]] = x[s, :self.in_bytes[s]].view(np.int16)
-        arrive = self._dev(x)
-        law_in = {c: self._dev(np.where(self.ic == c, self.leg_len, 0).astype(np.int32)) for c in LAW if (self.ic == c).any()}
-        law_out = {c: self._dev(np.where(self.oc == c, self.leg_len, 0).astype(np.int32)) for c in LAW if (self.oc == c).any()}
-        self.ctx.sync()
-        self.pcm.copy_(self._dev(pcm))
-        self.wide.zero_()
-        self.codes_out.zero_()
-        t.cuda.synchronize()
-        for c, lens in law_in.items():
-            ms.g711_decode(self.ctx, LAW[c], arrive, self.pcm, length=int(self.leg_len.max()), lens=lens)
-        masks = {r: (self._dev((present != 0) & (self.rates == r) & linked), self._dev(output & (self.rates == r)),
-                     self._dev(np.where((present != 0) & (self.rates == r), self.leg_len, 0).astype(np.int32))) for r in self.distinct}
-        has = self._dev(present)
-        same = self._dev(self.rates == self.conf)
-        t.cuda.synchronize()
-        for r in self.distinct:
-            self.vol[r].process(self.pcm, nsamples=int(r) // 100, per_stream=masks[r][2])
-        for r, rs in self.res_in.items():
-            if roomy(r):  # one ratio at a time through the roomy rows; the rows that ran, onto the mixer's contiguous rows
-                ms.check(Lb.mi_resampler_process_masked(rs.h, ms._ptr(self.pcm), r // 100, W, ms._ptr(self.narrow), ns + 8, None, ms._ptr(masks[r][0])))
-                self.ctx.sync()
-                ran = masks[r][0]
-                self.wide[ran] = self.narrow[ran][:, :ns]
-                t.cuda.synchronize()
-            else:
-                ms.check(Lb.mi_resampler_process_masked(rs.h, ms._ptr(self.pcm), r // 100, W, ms._ptr(self.wide), ns, None, ms._ptr(masks[r][0])))
-        self.ctx.sync()
-        self.wide[same] = self.pcm[same][:, :ns]
-        t.cuda.synchronize()
-        self.mix.process(self.wide.view(n // self.mm, self.mm, ns), has, 1, self.mixed.view(n // self.mm, self.mm, ns))
-        for r, rs in self.res_out.items():
-            ms.check(Lb.mi_resampler_process_masked(rs.h, ms._ptr(self.mixed), ns, ns, ms._ptr(self.back), W, None, ms._ptr(masks[r][1])))
-        self.ctx.sync()
-        self.back[:, :ns][same] = self.mixed[same]
-        t.cuda.synchronize()
-        for c, lens in law_out.items():
-            ms.g711_encode(self.ctx, LAW[c], self.back, self.codes_out, length=int(self.leg_len.max()), lens=lens)
-        self.ctx.sync()
-        codes, back = self.codes_out.cpu().numpy(), self.back.cpu().numpy()
-        held = self.held[self.ticks % 3]
-        self.ticks += 1
-        for s in np.nonzero(output)[0]:
-            ll = self.leg_len[s]
-            held[s, :self.out_bytes[s]] = codes[s, :ll] if self.oc[s] else back[s, :ll].view(np.uint8)
-        return held.copy()
-
-
-def _pair(br, ctx, mk, mm, conf, legs, **kw):
-    parts = Parts(ctx, mk, mm, conf, legs, **kw)
-    assert br.tick_bytes() == (parts.in_pitch, parts.out_pitch)
-    for s in range(parts.n):
-        assert br.leg_codec(s) == (parts.ic[s], parts.oc[s]) and br.leg_bytes(s) == (parts.in_bytes[s], parts.out_bytes[s])
-        assert br.leg_rate(s) == parts.rates[s]
-    return parts
 
 
 def _legs(case, mm, nconf=2):
@@ -315,32 +238,11 @@ def test_no_such_leg_is_the_concealed_bridge(ctx, mk, plc):
 
 
 def _lds_cap(conf, rates):
-    """the member cap of a conference whose legs' rates are `rates`, from creation's formula (create_bridge, csrc/bridge.hip):
+    """the member cap of a conference whose legs' rates are `rates`, from creation's formula (plan_bridge, csrc/bridge_plan.hpp):
     rows of the widest tick at an odd number of 8-byte words, the int32 sum row, four wavefronts' resampler scratch -- the
     largest form any leg needs -- and the kernel's own RATED_STATIC_LDS, within 64 KB"""
-    src = open(os.path.join(ROOT, "mediastreamer2_amd", "csrc", "bridge.hip")).read()
-    static = int(re.search(r"RATED_STATIC_LDS\s*=\s*(\d+)", src).group(1))
-    up16 = lambda v: (v + 15) & ~15
-    ns, wide = conf // 100, max(conf, max(rates)) // 100
-    rated_plen = lambda num, in_len: ((num * 48 - 1 + in_len + num - 1) // num + 8 + 8 + 3) & ~3
-    rational = lambda m, in_len: 2 * m * (((((24 * m - 1 + in_len + m - 1) // m) + 8 + 8 + 3) & ~3) | 4) * 4
-    scratch = 0
-    for r in set(rates):
-        if 2 * r == 3 * conf:
-            need = max(rational(3, ns // 2 * 3), rational(2, ns))
-        elif 3 * r == 2 * conf:
-            need = max(rational(2, ns // 3 * 2), rational(3, ns))
-        elif r < conf:
-            k = conf // r
-            need = max(((47 + ns // k + 8 + 1 + 3) & ~3) * 4, (k * rated_plen(k, ns) + ns) * 4)
-        elif r > conf:
-            k = r // conf
-            need = max(((47 + ns + 8 + 1 + 3) & ~3) * 4, (k * (rated_plen(k, k * ns) | 4) + k * ns) * 4)
-        else:
-            continue
-        scratch = max(scratch, up16(need))
-    fits = lambda mm: up16(up16(mm * ((wide >> 2) | 1) * 8) + ns * 4) + 4 * scratch + static <= 64 * 1024
-    return max(mm for mm in range(1, 129) if fits(mm))
+    static = bridge_budget()[0]
+    return max(mm for mm in range(1, 129) if bridge_lds(conf, rates, mm) + static <= 64 * 1024)
 
 
 def test_refusals(ctx, mk):
@@ -374,28 +276,6 @@ def test_refusals(ctx, mk):
     assert _one_tick(br, np.zeros((6, 480), np.uint8)).shape == (6, 480)
 
 
-class RationalConcealedParts(ConcealedParts):
-    """tests/test_gpu_bridge_concealed.py's parts -- the decoders, a PlcBatch per distinct rate -- in front of a plc-less
-    rational= bridge"""
-
-    def __init__(self, ctx, mk, mm, conf, legs):
-        import torch
-        self.t = torch
-        legs = np.asarray(legs, np.int32)
-        self.ctx, self.n = ctx, len(legs)
-        self.rates, self.ic, self.oc = legs[:, 0].copy(), legs[:, 1].copy(), legs[:, 2].copy()
-        self.leg_len = self.rates // 100
-        self.width = int(self.leg_len.max())
-        self.in_bytes = self.leg_len * np.where(self.ic, 1, 2)
-        self.plc = {int(r): mk(ms.PlcBatch, self.n, int(r), max_block=self.width) for r in sorted(set(self.rates))}
-        self.inner = mk(ms.Bridge, self.n, members=mm, rate=conf, rational=[(r, PCM16, oc) for r, oc in zip(self.rates, self.oc)])
-        assert self.inner.tick_bytes()[0] == 2 * self.width
-        self.pcm = torch.zeros((self.n, self.width), dtype=torch.int16, device="cuda")
-        self.lens = self._dev(self.leg_len.astype(np.int32))
-        self.law_lens = {c: self._dev(np.where(self.ic == c, self.leg_len, 0).astype(np.int32)) for c in (PCMA, PCMU) if (self.ic == c).any()}
-        torch.cuda.synchronize()
-
-
 def test_plc_equal_to_the_parts(ctx, mk, oracle):
     """a 16 kHz room of 16 kHz mu-law, 24 kHz PCM and 16 kHz PCM legs with scattered losses: bit for bit mi_g711_decode per law
     -> mi_plc_process per rate -> the plc-less rational= bridge, the relation of tests/test_gpu_bridge_concealed.py"""
@@ -403,7 +283,7 @@ def test_plc_equal_to_the_parts(ctx, mk, oracle):
     legs = [(16000, PCMU, PCMU), (24000, PCM16, PCM16), (16000, PCM16, PCM16)] * 2
     n = len(legs)
     br = mk(ms.Bridge, n, members=mm, rate=conf, rational=legs, plc=True)
-    parts = RationalConcealedParts(ctx, mk, mm, conf, legs)
+    parts = ConcealedParts(ctx, mk, mm, conf, legs, form="rational")
     assert br.tick_bytes() == (480, 480) == parts.inner.tick_bytes()
     p = ms.VolumeBatch.default_params()
     p.agc_enabled, p.remove_dc = 1, 1

@@ -5,45 +5,22 @@ performance silently, so the build is checked here (hipcc cross-compiles without
   * under 64 KB of code: the instruction cache two CUs share (99.99 % hits measured at that size)."""
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+from kernel_remarks import compile_unit, usages
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "mediastreamer2_amd", "csrc", "aec.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 @pytest.fixture(scope="module")
 def build(tmp_path_factory):
+    """a build of its own, not kernel_remarks.remarks': the code sizes are read off the object file"""
     d = tmp_path_factory.mktemp("aec_res")
     obj = d / "aec_dev.o"
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", SRC, "-o", str(obj)], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return d, obj, r.stderr
-
-
-def usage(remarks, kernel_substr):
-    """{field: value} of the kernel-resource-usage remark block of the first function whose name contains kernel_substr"""
-    blocks = re.split(r"remark: Function Name: ", remarks)
-    for b in blocks[1:]:
-        if kernel_substr in b.split()[0]:
-            return {m.group(1).strip(): m.group(2).strip() for m in re.finditer(r"remark:\s+([A-Za-z /\[\]]+):\s+(\S+)", b)}
-    raise AssertionError(f"no remarks for {kernel_substr}")
-
-
-def usages(remarks, kernel_substr):
-    """[(function name, {field: value})] of every kernel-resource-usage remark block whose function name contains kernel_substr"""
-    out = []
-    for b in re.split(r"remark: Function Name: ", remarks)[1:]:
-        name = b.split()[0]
-        if kernel_substr in name:
-            out.append((name, {m.group(1).strip(): m.group(2).strip() for m in re.finditer(r"remark:\s+([A-Za-z /\[\]]+):\s+(\S+)", b)}))
-    assert out, f"no remarks for {kernel_substr}"
-    return out
+    return d, obj, compile_unit("aec.hip", obj)
 
 
 def test_tick_kernel_registers_and_lds(build):
@@ -56,7 +33,9 @@ def test_tick_kernel_registers_and_lds(build):
         assert int(u["Occupancy [waves/SIMD]"]) == 2, (name, u)
         assert int(u["LDS Size [bytes/block]"]) <= 20480, (name, u)  # one wave per block: 8 per CU
     for k in ("aec_tick_kernelILi128E", "aec_tick_kernelILi64E"):
-        for name, v in usages(remarks, k):
+        found = usages(remarks, k)
+        assert found, f"no remarks for {k}"
+        for name, v in found:
             assert int(v["VGPRs Spill"]) <= 12, (name, v)  # the small frames run at 3 / 4 waves per SIMD: a handful of spills is the price
 
 
