@@ -247,6 +247,7 @@ __device__ __forceinline__ void band_sum3(const AecTables &t, int b, const float
 
 #include "resample_tile.hpp"
 #include "aec_wave.hpp"
+#include "aec_steps.hpp"
 #include "aec_tick.hpp"
 #include "aec_group.hpp"
 
@@ -535,7 +536,6 @@ int mi_aec_framesize(int framesize_at_8000, int sample_rate) { // speexec.c:171-
 	return n;
 }
 
-static bool aec_group_form_on();
 int mi_aec_create(mi_ctx *ctx, int nstreams, int sample_rate, int frame_size, int filter_length, mi_aec **out) {
 	MI_CHECK_ARG(ctx && out && nstreams > 0 && sample_rate > 0 && filter_length > 0);
 	*out = nullptr;
@@ -575,7 +575,7 @@ int mi_aec_create(mi_ctx *ctx, int nstreams, int sample_rate, int frame_size, in
 		}
 		for (int i = M - 1; i >= 0; i--) a->h_prop0[(size_t)i] = (.8f * a->h_prop0[(size_t)i]) / sum;
 	}
-	a->small_stride = 19 * frame_size + 256; // TickLayout<F>::TOTAL
+	a->small_stride = small_layout(frame_size).TOTAL;
 	const size_t xn = (size_t)(M + 1) * a->N;
 	int rc = build_tables(a);
 	if (rc != MI_OK) {
@@ -640,6 +640,18 @@ size_t mi_aec_state_bytes(const mi_aec *a) {
 }
 
 static std::atomic<int> g_group_form{-1}; // -1: ask the environment on first use (MSMI355X_AEC_GROUP); mi_debug_aec_group_form sets it
+// (The FIFO entries at the small frame sizes -- 8 kHz: F = 64, 16 kHz: F = 128 -- stay on the tick form, one leg per wavefront with the
+// FIFOs inside the launch.  Round 5 built the entry out of the group kernel too -- queue, pop frames into rows, one aec_group_kernel launch
+// per frame index, push -- and measured it 5 % slower per whole tick (1 010 / 1 559 us against 960 / 1 482 at 65 536 legs: a tick is 1.25
+// frames per leg and the second launch serves a quarter of the legs at the price of all): profiles/r05_small_frame_fifo_entry.txt.  That
+// path is no longer in the source; rows handed in directly -- mi_aec_process / mi_aec_process_frames -- run the group kernel.)
+static bool aec_group_form_on() {
+	if (g_group_form.load(std::memory_order_relaxed) < 0) {
+		const char *e = getenv("MSMI355X_AEC_GROUP");
+		g_group_form.store(e && e[0] == '0' ? 0 : 1, std::memory_order_relaxed);
+	}
+	return g_group_form.load(std::memory_order_relaxed) > 0;
+}
 
 struct AecFifoCall {
 	ResamplerView rs; // rs.ok: the microphone block is up-sampled inside the launch from rs_in
@@ -766,21 +778,6 @@ int mi_aec_process_frames(mi_aec *a, const int16_t *d_mic, const int16_t *d_ref,
 	             stride >= max_frames * a->F);
 	return aec_launch(a, d_mic, d_ref, d_out, stride, nullptr, d_count, max_frames, flags, nullptr);
 }
-
-// (The FIFO entries at the small frame sizes -- 8 kHz: F = 64, 16 kHz: F = 128 -- stay on the tick form, one leg per wavefront with the
-// FIFOs inside the launch.  Round 5 built the entry out of the group kernel too -- queue, pop frames into rows, one aec_group_kernel launch
-// per frame index, push -- and measured it 5 % slower per whole tick (1 010 / 1 559 us against 960 / 1 482 at 65 536 legs: a tick is 1.25
-// frames per leg and the second launch serves a quarter of the legs at the price of all): profiles/r05_small_frame_fifo_entry.txt.  That
-// path is no longer in the source; rows handed in directly -- mi_aec_process / mi_aec_process_frames -- run the group kernel.)
-static bool aec_group_form_on() {
-	if (g_group_form.load(std::memory_order_relaxed) < 0) {
-		const char *e = getenv("MSMI355X_AEC_GROUP");
-		g_group_form.store(e && e[0] == '0' ? 0 : 1, std::memory_order_relaxed);
-	}
-	return g_group_form.load(std::memory_order_relaxed) > 0;
-}
-static int aec_launch(mi_aec *a, const int16_t *d_mic, const int16_t *d_ref, int16_t *d_out, int stride, const uint8_t *d_run,
-                      const uint8_t *d_count, int max_frames, unsigned flags, const AecFifoCall *fifo);
 
 int mi_aec_process_fifos_masked(mi_aec *a, mi_fifo *f_mic, const int16_t *d_mic_tick, int mic_stride, mi_fifo *f_ref,
                                 const int16_t *d_ref_tick, int ref_stride, const int32_t *d_ref_len, int tick_len, mi_fifo *f_out,
@@ -925,10 +922,10 @@ int mi_aec_get(mi_aec *a, int stream, const char *what, float *h_dst, int cap) {
 	std::vector<float> small((size_t)a->small_stride);
 	MI_HIP(hipMemcpy(small.data(), a->d_small + (size_t)stream * a->small_stride, small.size() * sizeof(float),
 	                 hipMemcpyDeviceToHost));
-	const int o_e = F, o_pw = 3 * F, o_p1 = 4 * F, o_eh = 5 * F, o_yh = 6 * F, o_ly = 7 * F, o_misc = 19 * F, o_prop = o_misc, o_tail = o_misc + 128;
+	const SmallLayout sl = small_layout(F);
 	auto with_tail = [&](int off, int t) { // the per-bin array plus its Nyquist entry
 		std::vector<float> v(small.begin() + off, small.begin() + off + F);
-		v.push_back(small[(size_t)o_tail + t]);
+		v.push_back(small[(size_t)sl.TAIL + t]);
 		return v;
 	};
 	std::vector<float> res;
@@ -950,13 +947,13 @@ int mi_aec_get(mi_aec *a, int stream, const char *what, float *h_dst, int cap) {
 			unpack(raw.data() + (size_t)((sc.xhead + j) % (M + 1)) * N, res.data() + (size_t)j * N);
 	} else if (!strcmp(what, "E")) {
 		res.resize((size_t)N);
-		unpack(small.data() + o_e, res.data());
-	} else if (!strcmp(what, "power")) res = with_tail(o_pw, 0);
-	else if (!strcmp(what, "power_1")) res = with_tail(o_p1, 1);
-	else if (!strcmp(what, "Eh")) res = with_tail(o_eh, 2);
-	else if (!strcmp(what, "Yh")) res = with_tail(o_yh, 3);
-	else if (!strcmp(what, "last_y")) res.assign(small.begin() + o_ly, small.begin() + o_ly + N); // [older | newest]
-	else if (!strcmp(what, "prop")) res.assign(small.begin() + o_prop, small.begin() + o_prop + M);
+		unpack(small.data() + sl.E, res.data());
+	} else if (!strcmp(what, "power")) res = with_tail(sl.POWER, 0);
+	else if (!strcmp(what, "power_1")) res = with_tail(sl.POWER1, 1);
+	else if (!strcmp(what, "Eh")) res = with_tail(sl.EH, 2);
+	else if (!strcmp(what, "Yh")) res = with_tail(sl.YH, 3);
+	else if (!strcmp(what, "last_y")) res.assign(small.begin() + sl.LASTY, small.begin() + sl.LASTY + N); // [older | newest]
+	else if (!strcmp(what, "prop")) res.assign(small.begin() + sl.PROP, small.begin() + sl.PROP + M);
 	else if (!strcmp(what, "order")) { // the list the next launch of the FIFO entry will serve the legs in, class after class
 		std::vector<int> ctl(TickOrder::WORDS), ord((size_t)2 * 8 * a->cap8);
 		MI_HIP(hipMemcpy(ctl.data(), a->d_ctl, ctl.size() * sizeof(int), hipMemcpyDeviceToHost));

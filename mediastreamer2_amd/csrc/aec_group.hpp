@@ -1,5 +1,6 @@
 // aec_group.hpp -- the canceller at the SMALL frame sizes (8 kHz: F = 64, 16 kHz: F = 128; speexec.c:171-180), several legs
-// per wavefront (included by aec.hip after aec_tick.hpp, whose addressing helpers and layout it shares).
+// per wavefront (included by aec.hip after aec_steps.hpp, whose steps it composes, and aec_tick.hpp, whose addressing
+// helpers and layout it shares).
 //
 // One wavefront per leg (aec_tick.hpp) is built for F = 256: four bins per lane.  At F = 64 a lane holds ONE bin, three
 // quarters of the lanes idle through every radix-4 stage of the 13 transforms of a frame, and every one of the library's
@@ -17,10 +18,12 @@
 //     read zeros, its stores are dropped, it computes on zeros and nobody sees it.
 // ONE frame per launch (mi_aec_process; mi_aec_process_frames runs the tick's frames as one launch each): the two-frame
 // machinery of the tick form (speculated foreground response, unwritten W1) needs the registers that the per-leg scalars
-// now take.  Arithmetic, operation order and the state in HBM are those of aec_tick_kernel<F>: the same sums in the
-// library's order, the same trees (a balanced tree over the bins in natural order is the same tree whichever lanes hold
-// them), so a leg may change between the two kernels from one launch to the next -- the FIFO entries stay on the tick form
-// -- and tests/test_gpu_aec.py holds both to the oracle.
+// now take.  The frame's steps are aec_steps.hpp's, composed here with Grp<F> as their lanes policy; this file holds what
+// a leg in G lanes needs of its own: the policy, the transforms and serial chains in G lanes, the wave's addressing, the
+// proportional step and the streaming pass.  The trees are the tick form's too (a balanced tree over the bins in natural
+// order is the same tree whichever lanes hold them) and so is the state in HBM, so a leg may change between the two
+// kernels from one launch to the next -- the FIFO entries stay on the tick form -- and tests/test_gpu_aec.py holds both
+// to the oracle and to each other.
 
 template <int F>
 struct GroupShape {
@@ -44,8 +47,17 @@ struct alignas(16) GLds {
 };
 
 template <int F>
-struct Grp { // the leg's lanes inside the wave
-	static constexpr int K = GroupShape<F>::K, G = GroupShape<F>::G, LPW = GroupShape<F>::LPW;
+struct GSeq;
+template <int F, typename LL, typename LT>
+__device__ void g_rfft_forward(LL &L, const LT &T, float2 (&out)[4], const float *src = nullptr);
+template <int F, typename LL, typename LT>
+__device__ void g_rfft_inverse(LL &L, const LT &T, const float2 (&in)[4]);
+
+template <int F_>
+struct Grp { // the leg's lanes inside the wave: the lanes policy of the shared steps (aec_steps.hpp)
+	static constexpr int F = F_, K = GroupShape<F>::K, G = GroupShape<F>::G, LPW = GroupShape<F>::LPW;
+	static constexpr int NBL = (NB_BANDS + G - 1) / G; // Bark bands per lane: 24 bands over the leg's G lanes
+	using Seq = GSeq<F>;
 	__device__ static __forceinline__ int lane() { return threadIdx.x & (G - 1); }
 	__device__ static __forceinline__ int index() { return threadIdx.x / G; }
 	// the value lane `from` of the leg holds, in all of the leg's lanes
@@ -102,6 +114,27 @@ struct Grp { // the leg's lanes inside the wave
 		const unsigned long long b = __ballot(p);
 		const unsigned long long m = (G == 32 ? 0xffffffffull : 0xffffull) << (threadIdx.x & ~(G - 1));
 		return (b & m) != 0;
+	}
+	__device__ static __forceinline__ void dc_notch(const float (&in)[K], float radius, float den2, float &m0, float &m1, float (&out)[K]) {
+		Seq::dc_notch(in, radius, den2, m0, m1, out);
+	}
+	__device__ static __forceinline__ void deemphasis(const float (&d)[K], float &mem, float (&out)[K]) { Seq::deemphasis(d, mem, out); }
+	template <typename LL, typename LT>
+	__device__ static __forceinline__ void rfft_forward(LL &L, const LT &T, float2 (&out)[K], const float *src = nullptr) {
+		g_rfft_forward<F>(L, T, out, src);
+	}
+	template <typename LL, typename LT>
+	__device__ static __forceinline__ void rfft_inverse(LL &L, const LT &T, const float2 (&in)[K]) { g_rfft_inverse<F>(L, T, in); }
+	// the library's ascending sum over the 24 bands, whose values the leg's lanes hold (lane l: bands l, l + G): through `slot`,
+	// 24 floats of the leg's LDS
+	__device__ static __forceinline__ float band_total(const float (&vb)[NBL], float *slot) {
+#pragma unroll
+		for (int bi = 0; bi < NBL; ++bi)
+			if (lane() + bi * G < NB_BANDS) slot[lane() + bi * G] = vb[bi];
+		WSYNC();
+		float sum = 0;
+		for (int i = 0; i < NB_BANDS; ++i) sum = sum + slot[i];
+		return sum;
 	}
 };
 
@@ -193,7 +226,7 @@ __device__ void g_cfft(LL &L, const LT &T, const float2 *src, bool inverse) {
 
 // L.tbuf (2F time samples; or `src`) -> this lane's K bins, scaled 1/N.  Bin 0 = (DC, Nyquist).
 template <int F, typename LL, typename LT>
-__device__ void g_rfft_forward(LL &L, const LT &T, float2 (&out)[4], const float *src = nullptr) {
+__device__ void g_rfft_forward(LL &L, const LT &T, float2 (&out)[4], const float *src) {
 	using GP = Grp<F>;
 	constexpr int K = GP::K;
 	if (src == nullptr) src = L.tbuf;
@@ -473,18 +506,7 @@ __global__ __launch_bounds__(64, 2) void aec_group_kernel(AecArgs a, int frame) 
 		float xp[K], far[K], xn[K];
 		bload_vec<K>(rS, vb4, SL::XPREV * 4, xp);
 		load_row(rRef, far);
-		float prev = GP::shr1(sc.memX, far[K - 1]);
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			xn[k] = far[k] - .9f * prev;
-			prev = far[k];
-		}
-		sc.memX = GP::last(far[K - 1]);
-		Sxx = GSeq<F>::inner_prod(xn, xn);
-		WSYNC();
-		store_vec<K>(L.tbuf + e0, xp);
-		store_vec<K>(L.tbuf + F + e0, xn);
-		g_rfft_forward<F>(L, LW, X0);
+		far_end<GP>(L, LW, far, xp, sc.memX, xn, X0, Sxx);
 		bstore_vec<K>(rS, vb4, SL::XPREV * 4, xn);
 	}
 	bool pendingFG = sc.fg_pending != 0, pendingBG = sc.bg_pending != 0;
@@ -492,25 +514,8 @@ __global__ __launch_bounds__(64, 2) void aec_group_kernel(AecArgs a, int frame) 
 
 	// ---- near end: saturation flag, DC notch (serial IIR), pre-emphasis
 	float input[K], micf[K];
-	bool any_sat;
-	{
-		bool satl = false;
-		load_row(rMic, micf);
-#pragma unroll
-		for (int k = 0; k < K; ++k) satl |= (micf[k] <= -32000.f || micf[k] >= 32000.f);
-		any_sat = GP::any(satl);
-		const float radius = a.notch_radius;
-		const float den2 = (float)(radius * radius + .7 * (1 - radius) * (1 - radius));
-		float v[K];
-		GSeq<F>::dc_notch(micf, radius, den2, sc.notch0, sc.notch1, v);
-		float vprev = GP::shr1(sc.memD, v[K - 1]);
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			input[k] = v[k] - .9f * vprev;
-			vprev = v[k];
-		}
-		sc.memD = GP::last(v[K - 1]);
-	}
+	load_row(rMic, micf);
+	const bool any_sat = near_end<GP>(micf, a.notch_radius, sc, input);
 	sc.cancel_count++;
 	sc.frames++;
 
@@ -518,17 +523,8 @@ __global__ __launch_bounds__(64, 2) void aec_group_kernel(AecArgs a, int frame) 
 	const int head = (sc.xhead + M) % (M + 1);
 	sc.xhead = head;
 	bstore_bins<K>(rX, oX + (unsigned)head * (F * 8), 0, X0);
-	float Xf[K], Xf_F = 0;
-#pragma unroll
-	for (int k = 0; k < K; ++k) {
-		if (e0 + k == 0) {
-			Xf[k] = X0[k].x * X0[k].x;
-			Xf_F = X0[k].y * X0[k].y;
-		} else {
-			Xf[k] = X0[k].x * X0[k].x + X0[k].y * X0[k].y;
-		}
-	}
-	Xf_F = GP::first(Xf_F);
+	float Xf[K], Xf_F;
+	bin_power<GP>(X0, Xf, Xf_F);
 
 	// ---- proportional step (mdf_adjust_prop): prop_j = sqrt(1 + |W_j|^2) + .1 max, normalised by the library's serial sum
 	{
@@ -552,21 +548,6 @@ __global__ __launch_bounds__(64, 2) void aec_group_kernel(AecArgs a, int frame) 
 	WSYNC();
 	const bool do_grad = (sc.saturated == 0);
 	if (!do_grad) sc.saturated--;
-
-	// W += prop p1 conj(X) E, bin by bin (weighted_spectral_mul_conj); bin 0 = (DC, Nyquist): real products with their own steps
-	auto grad = [&](v2f (&w)[K], const v2f (&x)[K], float prop) {
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			const v2f xv = x[k], ev = {Eprev[k].x, Eprev[k].y};
-			const float Wt = prop * p1[k];
-			v2f st = pk_cmul_conj(xv, ev) * (v2f){Wt, Wt};
-			if (k == 0) {
-				const v2f dc = (xv * ev) * (v2f){Wt, prop * p1_F};
-				if (e0 == 0) st = dc;
-			}
-			w[k] = w[k] + st;
-		}
-	};
 
 	// ---- one streaming pass over the blocks (next block's loads in flight); AUMDF constraint where the pass meets block
 	// 0 and the leg's round-robin block -- for the whole wave (the transforms need every lane), kept by the legs that ask
@@ -600,17 +581,12 @@ __global__ __launch_bounds__(64, 2) void aec_group_kernel(AecArgs a, int frame) 
 				xi = xi2;
 			}
 			const bool aumdf = (j == 0 || j == jc);
-			if (do_grad) grad(wl, xn, L.prop[j]);
+			if (do_grad) gradient<GP>(wl, xn, L.prop[j], Eprev, p1, p1_F);
 			if (__any(aumdf)) {
 				float2 w[K];
 #pragma unroll
 				for (int k = 0; k < K; ++k) w[k] = make_float2(wl[k].x, wl[k].y);
-				g_rfft_inverse<F>(L, LW, w);
-				float z[K];
-#pragma unroll
-				for (int k = 0; k < K; ++k) z[k] = 0.f;
-				store_vec<K>(w_time(L) + F + e0, z);
-				g_rfft_forward<F>(L, LW, w, w_time(L));
+				constrain<GP>(L, LW, w);
 				if (aumdf) {
 #pragma unroll
 					for (int k = 0; k < K; ++k) wl[k] = (v2f){w[k].x, w[k].y};
@@ -654,106 +630,30 @@ __global__ __launch_bounds__(64, 2) void aec_group_kernel(AecArgs a, int frame) 
 	Dbf = 10 + Dbf;
 
 	// ---- two-path control
-	sc.Davg1 = .6f * sc.Davg1 + .4f * (Sff - See);
-	sc.Davg2 = .85f * sc.Davg2 + .15f * (Sff - See);
-	sc.Dvar1 = .36f * sc.Dvar1 + (.4f * Sff) * (.4f * Dbf);
-	sc.Dvar2 = .7225f * sc.Dvar2 + (.15f * Sff) * (.15f * Dbf);
-	bool update_foreground = false;
-	if ((Sff - See) * fabsf(Sff - See) > Sff * Dbf) update_foreground = true;
-	else if (sc.Davg1 * fabsf(sc.Davg1) > .5f * sc.Dvar1) update_foreground = true;
-	else if (sc.Davg2 * fabsf(sc.Davg2) > .25f * sc.Dvar2) update_foreground = true;
 	WSYNC();
-	if (update_foreground) {
-		sc.fg_updates++;
-		sc.Davg1 = sc.Davg2 = 0;
-		sc.Dvar1 = sc.Dvar2 = 0;
+	if (two_path_update(sc, Sff, See, Dbf)) {
 		pendingFG = true; // the next pass over the filter carries the copy out
 		for (int j = lane; j < M; j += G) L.fgnorm[j] = L.wnorm[j];
-		float h0[K], h1[K];
-		load_vec<K>(a.t.hann + e0, h0);
-		load_vec<K>(a.t.hann + F + e0, h1);
-#pragma unroll
-		for (int k = 0; k < K; ++k) efg[k] = h1[k] * efg[k] + h0[k] * ybg[k];
-	} else {
-		bool reset_background = false;
-		if ((-(Sff - See)) * fabsf(Sff - See) > 4.f * (Sff * Dbf)) reset_background = true;
-		if ((-sc.Davg1) * fabsf(sc.Davg1) > 4.f * sc.Dvar1) reset_background = true;
-		if ((-sc.Davg2) * fabsf(sc.Davg2) > 4.f * sc.Dvar2) reset_background = true;
-		if (reset_background) {
-			sc.bg_resets++;
-			pendingBG = true; // the next pass reads the foreground's blocks as the background's
-			for (int j = lane; j < M; j += G) L.wnorm[j] = L.fgnorm[j];
-#pragma unroll
-			for (int k = 0; k < K; ++k) {
-				ybg[k] = efg[k];
-				e2[k] = input[k] - efg[k];
-			}
-			See = Sff;
-			sc.Davg1 = sc.Davg2 = 0;
-			sc.Dvar1 = sc.Dvar2 = 0;
-		}
+		blend_foreground<GP>(a.t.hann, efg, ybg);
+	} else if (two_path_reset(sc, Sff, See, Dbf)) {
+		pendingBG = true; // the next pass reads the foreground's blocks as the background's
+		for (int j = lane; j < M; j += G) L.wnorm[j] = L.fgnorm[j];
+		take_foreground<GP>(efg, input, Sff, ybg, e2, See);
 	}
 
-	// ---- output (serial de-emphasis) and correlations
 	int out_i[K];
-	{
-		float d[K], tout[K];
-#pragma unroll
-		for (int k = 0; k < K; ++k) d[k] = input[k] - efg[k];
-		GSeq<F>::deemphasis(d, sc.memE, tout);
-#pragma unroll
-		for (int k = 0; k < K; ++k) out_i[k] = word2int(tout[k]);
-	}
 	float Sey, Syy, Sdd;
-	GSeq<F>::inner_prod3(e2, ybg, ybg, ybg, input, input, Sey, Syy, Sdd);
-	if (any_sat && sc.saturated == 0) sc.saturated = 1;
+	output_and_correlations<GP>(sc, input, efg, e2, ybg, any_sat, out_i, Sey, Syy, Sdd);
 
-	// ---- error / response spectra
 	float2 Ecur[K], Ycur[K];
-	{
-		float z[K];
-#pragma unroll
-		for (int k = 0; k < K; ++k) z[k] = 0.f;
-		WSYNC();
-		store_vec<K>(L.tbuf + e0, z);
-		store_vec<K>(L.tbuf + F + e0, e2);
-		g_rfft_forward<F>(L, LW, Ecur);
-		store_vec<K>(L.tbuf + e0, z);
-		store_vec<K>(L.tbuf + F + e0, ybg);
-		g_rfft_forward<F>(L, LW, Ycur);
-	}
-	float Rf[K], Yf[K], Rf_F = 0, Yf_F = 0;
-#pragma unroll
-	for (int k = 0; k < K; ++k) {
-		if (e0 + k == 0) {
-			Rf[k] = Ecur[k].x * Ecur[k].x;
-			Rf_F = Ecur[k].y * Ecur[k].y;
-			Yf[k] = Ycur[k].x * Ycur[k].x;
-			Yf_F = Ycur[k].y * Ycur[k].y;
-		} else {
-			Rf[k] = Ecur[k].x * Ecur[k].x + Ecur[k].y * Ecur[k].y;
-			Yf[k] = Ycur[k].x * Ycur[k].x + Ycur[k].y * Ycur[k].y;
-		}
-	}
-	Rf_F = GP::first(Rf_F);
-	Yf_F = GP::first(Yf_F);
+	error_spectra<GP>(L, LW, e2, ybg, Ecur, Ycur);
+	float Rf[K], Yf[K], Rf_F, Yf_F;
+	bin_power<GP>(Ecur, Rf, Rf_F);
+	bin_power<GP>(Ycur, Yf, Yf_F);
 #pragma unroll
 	for (int k = 0; k < K; ++k) Eprev[k] = Ecur[k];
 
-	// ---- sanity checks
-	bool zero_out = false;
-	if (!(Syy >= 0 && Sxx >= 0 && See >= 0) || !(Sff < N * 1e9 && Syy < N * 1e9 && Sxx < N * 1e9)) {
-		sc.screwed_up += 50;
-		zero_out = true;
-	} else if (Sff > Sdd + (float)(N * 10000)) {
-		sc.screwed_up++;
-	} else {
-		sc.screwed_up = 0;
-	}
-	if (zero_out) {
-#pragma unroll
-		for (int k = 0; k < K; ++k) out_i[k] = 0;
-	}
+	sanity_checks<GP>(sc, Sff, See, Sxx, Syy, Sdd, out_i);
 	// the echo estimate pair the residual-echo stage works on: [the last frame's | this frame's]
 	float ly_old[K], ly_new[K];
 	bload_vec<K>(rS, vb4, (SL::LASTY + F) * 4, ly_old);
@@ -789,82 +689,16 @@ __global__ __launch_bounds__(64, 2) void aec_group_kernel(AecArgs a, int frame) 
 			for (int k = 0; k < K; ++k) z[k] = 0.f;
 			bstore_vec<K>(rS, vb4, SL::XPREV * 4, z);
 		}
-		sc.state_resets++;
-		sc.cancel_count = 0;
-		sc.screwed_up = 0;
-		sc.notch0 = sc.notch1 = 0;
-		sc.memD = sc.memE = sc.memX = 0;
-		sc.saturated = 0;
-		sc.adapted = 0;
-		sc.sum_adapt = 0;
-		sc.Pey = sc.Pyy = 1.0f;
-		sc.Davg1 = sc.Davg2 = sc.Dvar1 = sc.Dvar2 = 0;
+		reset_scalars(sc);
 		pendingFG = pendingBG = false;
 		leak_pf = sc.leak_estimate;
 	} else {
 		if (See < (float)(N * 100)) See = (float)(N * 100);
 		float Sxx2 = Sxx + Sxx; // sic: the library accumulates the far-end energy a second time here
-
-		// ---- far-end power, leak estimate
-#pragma unroll
-		for (int k = 0; k < K; ++k) pw[k] = a.ss_1 * pw[k] + 1 + a.ss * Xf[k];
-		pw_F = a.ss_1 * pw_F + 1 + a.ss * Xf_F;
+		far_power<GP>(a, Xf, Xf_F, pw, pw_F);
 		float Ehd[K], Yhd[K], Ehd_F, Yhd_F;
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			Ehd[k] = Rf[k] - eh[k];
-			Yhd[k] = Yf[k] - yh[k];
-			eh[k] = (1 - a.spec_average) * eh[k] + a.spec_average * Rf[k];
-			yh[k] = (1 - a.spec_average) * yh[k] + a.spec_average * Yf[k];
-		}
-		Ehd_F = Rf_F - eh_F;
-		Yhd_F = Yf_F - yh_F;
-		eh_F = (1 - a.spec_average) * eh_F + a.spec_average * Rf_F;
-		yh_F = (1 - a.spec_average) * yh_F + a.spec_average * Yf_F;
-		float Pey = 1.0f, Pyy = 1.0f;
-		Pey = Pey + Ehd_F * Yhd_F;
-		Pyy = Pyy + Yhd_F * Yhd_F;
-		GSeq<F>::dot_desc2(Pey, Ehd, Yhd, Pyy, Yhd, Yhd, Pey, Pyy);
-		Pyy = sqrt_via_double(Pyy);
-		Pey = Pey / Pyy;
-		float tmp32 = a.beta0 * Syy;
-		if (tmp32 > a.beta_max * See) tmp32 = a.beta_max * See;
-		const float alpha = tmp32 / See;
-		const float alpha_1 = 1.0f - alpha;
-		sc.Pey = alpha_1 * sc.Pey + alpha * Pey;
-		sc.Pyy = alpha_1 * sc.Pyy + alpha * Pyy;
-		if (sc.Pyy < 1.0f) sc.Pyy = 1.0f;
-		if (sc.Pey < .005f * sc.Pyy) sc.Pey = .005f * sc.Pyy;
-		if (sc.Pey > sc.Pyy) sc.Pey = sc.Pyy;
-		sc.leak_estimate = sc.Pey / sc.Pyy;
-		float RER = (float)((.0001 * Sxx2 + 3. * (sc.leak_estimate * Syy)) / See);
-		if (RER < Sey * Sey / (1 + See * Syy)) RER = Sey * Sey / (1 + See * Syy);
-		if (RER > .5) RER = .5;
-		if (!sc.adapted && sc.sum_adapt > (float)M && sc.leak_estimate * Syy > .03f * Syy) sc.adapted = 1;
-
-		auto step = [&](float Yfv, float Rfv, float pwv) -> float {
-			float r = sc.leak_estimate * Yfv;
-			const float e = Rfv + 1;
-			if (r > .5 * e) r = (float)(.5 * e);
-			r = .7f * r + .3f * (float)(RER * e);
-			return r / (e * (pwv + 10));
-		};
-		if (sc.adapted) {
-#pragma unroll
-			for (int k = 0; k < K; ++k) p1[k] = step(Yf[k], Rf[k], pw[k]);
-			p1_F = step(Yf_F, Rf_F, pw_F);
-		} else {
-			float adapt_rate = 0;
-			if (Sxx2 > (float)(N * 1000)) {
-				tmp32 = .25f * Sxx2;
-				if (tmp32 > .25 * See) tmp32 = (float)(.25 * See);
-				adapt_rate = tmp32 / See;
-			}
-#pragma unroll
-			for (int k = 0; k < K; ++k) p1[k] = adapt_rate / (pw[k] + 10);
-			p1_F = adapt_rate / (pw_F + 10);
-			sc.sum_adapt = sc.sum_adapt + adapt_rate;
-		}
+		spectral_averages<GP>(a, Rf, Rf_F, Yf, Yf_F, eh, eh_F, yh, yh_F, Ehd, Ehd_F, Yhd, Yhd_F);
+		leak_and_steps<GP>(a, sc, M, Sxx2, See, Syy, Sey, Ehd, Ehd_F, Yhd, Yhd_F, Rf, Rf_F, Yf, Yf_F, pw, pw_F, p1, p1_F);
 		// ---- echo estimate of this frame for the residual-echo stage
 #pragma unroll
 		for (int k = 0; k < K; ++k) ly_new[k] = sc.adapted ? (float)((int)micf[k] - out_i[k]) : ly_old[k];
@@ -903,286 +737,33 @@ __global__ __launch_bounds__(64, 2) void aec_group_kernel(AecArgs a, int frame) 
 	}
 
 	// ---- residual-echo / noise post-filter (speex_preprocess_run) of the same frame: per-bin state in registers, one or
-	// two Bark bands per lane (24 bands over the leg's G lanes)
-	constexpr int NBL = (NB_BANDS + G - 1) / G;
-	float en[K], inb[K], S[K], Smin[K], Stmp[K], noise[K], old_ps[K], zeta[K], ob[K], wl[K], wr[K], h0[K], h1[K], w0[K], w1[K];
-	bload_vec<K>(rS, vb4, SL::ECHON * 4, en);
-	bload_vec<K>(rS, vb4, SL::INBUF * 4, inb);
-	bload_vec<K>(rS, vb4, SL::S_ * 4, S);
-	bload_vec<K>(rS, vb4, SL::SMIN * 4, Smin);
-	bload_vec<K>(rS, vb4, SL::STMP * 4, Stmp);
-	bload_vec<K>(rS, vb4, SL::NOISE * 4, noise);
-	bload_vec<K>(rS, vb4, SL::OLDPS * 4, old_ps);
-	bload_vec<K>(rS, vb4, SL::ZETA * 4, zeta);
-	bload_vec<K>(rS, vb4, SL::OUTBUF * 4, ob);
-	load_vec<K>(a.t.bfl + e0, wl);
-	load_vec<K>(a.t.bfr + e0, wr);
-	load_vec<K>(a.t.hann + e0, h0);
-	load_vec<K>(a.t.hann + F + e0, h1);
-	load_vec<K>(a.t.pwin + e0, w0);
-	load_vec<K>(a.t.pwin + F + e0, w1);
-	float old_ps_b[NBL], zeta_b[NBL];
+	// two Bark bands per lane
+	constexpr int NBL = GP::NBL;
+	PfState<GP> pf;
+	pf_load<GP>(rS, vb4, a.t, pf);
 #pragma unroll
 	for (int bi = 0; bi < NBL; ++bi) {
 		const int b = lane + bi * G;
-		old_ps_b[bi] = zeta_b[bi] = 0;
+		pf.old_ps_b[bi] = pf.zeta_b[bi] = 0;
 		if (b < NB_BANDS) {
-			old_ps_b[bi] = g_load_f(rS, oS + (unsigned)(SL::OLDPS_B + b) * 4u);
-			zeta_b[bi] = g_load_f(rS, oS + (unsigned)(SL::ZETA_B + b) * 4u);
+			pf.old_ps_b[bi] = g_load_f(rS, oS + (unsigned)(SL::OLDPS_B + b) * 4u);
+			pf.zeta_b[bi] = g_load_f(rS, oS + (unsigned)(SL::ZETA_B + b) * 4u);
 		}
 	}
-	float *pl = L.spec, *pr = L.spec + F;
-	float *bandv = L.band;
-	float *lvec = L.vec;
+	residual_echo<GP>(L, LW, pf, ly_old, ly_new, was_reset, leak_pf);
+	float xcur[K];
+#pragma unroll
+	for (int k = 0; k < K; ++k) xcur[k] = (float)(int16_t)out_i[k];
 	int out_f[K];
-	{
-		sc.nb_adapt++;
-		if (sc.nb_adapt > 20000) sc.nb_adapt = 20000;
-		sc.min_count++;
-		float beta = 1.0f / sc.nb_adapt;
-		if (beta < .03f) beta = .03f;
-		const float beta_1 = 1.0f - beta;
-		const float leak = leak_pf;
-
-		// residual echo spectrum (speex_echo_get_residual)
-		{
-			float lo[K], ln[K];
-#pragma unroll
-			for (int k = 0; k < K; ++k) lo[k] = h0[k] * (was_reset ? 0.f : ly_old[k]), ln[k] = h1[k] * ly_new[k];
-			WSYNC();
-			store_vec<K>(L.tbuf + e0, lo);
-			store_vec<K>(L.tbuf + F + e0, ln);
-		}
-		float2 Yr[K];
-		g_rfft_forward<F>(L, LW, Yr);
-		const float leak2 = (leak > .5) ? 1.f : 2 * leak;
-		float res[K];
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			const float r = (e0 + k == 0) ? Yr[k].x * Yr[k].x : Yr[k].x * Yr[k].x + Yr[k].y * Yr[k].y;
-			res[k] = (float)(int32_t)(leak2 * r);
-		}
-		const float res0 = GP::first(res[0]);
-		const bool bad = !(res0 >= 0 && res0 < F * 1e9f);
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			const float rr = bad ? 0.f : res[k];
-			const float c = .6f * en[k];
-			en[k] = c > rr ? c : rr;
-			pl[e0 + k] = wl[k] * en[k];
-			pr[e0 + k] = wr[k] * en[k];
-		}
-		// analysis frame [inbuf, x] * window
-		{
-			float xcur[K], a0[K], a1[K];
-#pragma unroll
-			for (int k = 0; k < K; ++k) {
-				xcur[k] = (float)(int16_t)out_i[k];
-				a0[k] = inb[k] * w0[k];
-				a1[k] = xcur[k] * w1[k];
-				inb[k] = xcur[k];
-			}
-			store_vec<K>(L.tbuf + e0, a0);
-			store_vec<K>(L.tbuf + F + e0, a1);
-		}
-		float2 ft[K];
-		g_rfft_forward<F>(L, LW, ft);
-		float ps[K];
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			ps[k] = (e0 + k == 0) ? ft[k].x * ft[k].x : ft[k].x * ft[k].x + ft[k].y * ft[k].y;
-			lvec[e0 + k] = ps[k];
-			L.tbuf[e0 + k] = wl[k] * ps[k];     // the analysis transform is done with its input: the frame's filterbank
-			L.tbuf[F + e0 + k] = wr[k] * ps[k]; // products wait there (left halves, right halves) for the fused band sums
-		}
-		WSYNC();
-		// update_noise_prob
-		int min_range;
-		if (sc.nb_adapt < 100) min_range = 15;
-		else if (sc.nb_adapt < 1000) min_range = 50;
-		else if (sc.nb_adapt < 10000) min_range = 150;
-		else min_range = 300;
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			const int b = e0 + k;
-			if (b == 0 || b == F - 1) S[k] = .8f * S[k] + .2f * ps[k];
-			else S[k] = .8f * S[k] + .05f * lvec[b - 1] + .1f * ps[k] + .05f * lvec[b + 1];
-			if (sc.nb_adapt == 1) Smin[k] = Stmp[k] = 0;
-			if (sc.min_count > min_range) {
-				Smin[k] = Stmp[k] < S[k] ? Stmp[k] : S[k];
-				Stmp[k] = S[k];
-			} else {
-				Smin[k] = Smin[k] < S[k] ? Smin[k] : S[k];
-				Stmp[k] = Stmp[k] < S[k] ? Stmp[k] : S[k];
-			}
-			const int update_prob = (.4f * S[k] > Smin[k]) ? 1 : 0;
-			if (!update_prob || ps[k] < noise[k]) {
-				const float v = beta_1 * noise[k] + beta * ps[k];
-				noise[k] = v > 0 ? v : 0;
-			}
-		}
-		if (sc.min_count > min_range) sc.min_count = 0;
-		{
-			float *np = w_time(L); // free between the analysis and the synthesis transform
-#pragma unroll
-			for (int k = 0; k < K; ++k) {
-				np[e0 + k] = wl[k] * noise[k];
-				np[F + e0 + k] = wr[k] * noise[k];
-			}
-			WSYNC();
-			// echo estimate (products in L.spec since the start of the frame), frame, noise: three band sums in one loop
-#pragma unroll
-			for (int bi = 0; bi < NBL; ++bi) {
-				const int b = lane + bi * G;
-				if (b < NB_BANDS) band_sum3<F>(a.t, b, L.spec, L.tbuf, np, bandv[b], bandv[NB_BANDS + b], bandv[2 * NB_BANDS + b]);
-			}
-		}
-		WSYNC();
-
-		auto snr = [&](float psv, float noisev, float echov, float oldps, float &post, float &prior) {
-			const float tot_noise = 1.f + noisev + echov + 0.f;
-			post = psv / tot_noise - 1.f;
-			if (post > 100.f) post = 100.f;
-			const float t = oldps / (oldps + tot_noise);
-			const float gamma = .1f + .89f * (t * t);
-			prior = gamma * (post > 0 ? post : 0) + (1.0f - gamma) * (oldps / tot_noise);
-			if (prior > 100.f) prior = 100.f;
-		};
-		float post[K], prior[K];
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			if (sc.nb_adapt == 1) old_ps[k] = ps[k];
-			snr(ps[k], noise[k], en[k], old_ps[k], post[k], prior[k]);
-			lvec[e0 + k] = prior[k];
-		}
-		float post_b[NBL], prior_b[NBL], ps_b[NBL];
-#pragma unroll
-		for (int bi = 0; bi < NBL; ++bi) {
-			const int b = lane + bi * G;
-			post_b[bi] = prior_b[bi] = ps_b[bi] = 0;
-			if (b < NB_BANDS) {
-				ps_b[bi] = bandv[NB_BANDS + b];
-				if (sc.nb_adapt == 1) old_ps_b[bi] = ps_b[bi];
-				snr(ps_b[bi], bandv[2 * NB_BANDS + b], bandv[b], old_ps_b[bi], post_b[bi], prior_b[bi]);
-			}
-		}
-		WSYNC();
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			const int b = e0 + k;
-			if (b == 0 || b >= F - 1) zeta[k] = .7f * zeta[k] + .3f * prior[k];
-			else zeta[k] = .7f * zeta[k] + .15f * prior[k] + .075f * lvec[b - 1] + .075f * lvec[b + 1];
-		}
-#pragma unroll
-		for (int bi = 0; bi < NBL; ++bi) {
-			const int b = lane + bi * G;
-			if (b < NB_BANDS) {
-				zeta_b[bi] = .7f * zeta_b[bi] + .3f * prior_b[bi];
-				bandv[3 * NB_BANDS + b] = zeta_b[bi];
-			}
-		}
-		WSYNC();
-		float Zframe = 0;
-		for (int i = 0; i < NB_BANDS; ++i) Zframe = Zframe + bandv[3 * NB_BANDS + i];
-		const float Pframe = .1f + .899f * qcurve(Zframe / NB_BANDS);
-		const int eff_echo = (int)((1.0f - Pframe) * -40 + Pframe * -15);
-		float g2v[NBL], gv[NBL], gfv[NBL];
-#pragma unroll
-		for (int bi = 0; bi < NBL; ++bi) {
-			const int b = lane + bi * G;
-			g2v[bi] = gv[bi] = gfv[bi] = 0;
-			if (b < NB_BANDS) {
-				const float noise_floor = (float)exp((double)(.2302585f * -15));
-				const float echo_floor = (float)exp((double)(.2302585f * eff_echo));
-				const float nb = bandv[2 * NB_BANDS + b], eb = bandv[b];
-				const float gfloor = (float)(sqrt((double)(noise_floor * nb + echo_floor * eb)) / sqrt((double)(1 + nb + eb)));
-				const float prior_ratio = prior_b[bi] / (prior_b[bi] + 1.f);
-				const float theta = prior_ratio * (1.f + post_b[bi]);
-				const float MM = hypergeom_gain(theta);
-				float gg = prior_ratio * MM;
-				if (gg > 1.f) gg = 1.f;
-				old_ps_b[bi] = .2f * old_ps_b[bi] + (.8f * (gg * gg)) * ps_b[bi];
-				const float P1 = .199f + .8f * qcurve(zeta_b[bi]);
-				const float q = 1.0f - Pframe * P1;
-				g2v[bi] = (float)(1 / (1.f + (q / (1.f - q)) * (1 + prior_b[bi]) * exp((double)(-theta))));
-				gv[bi] = gg;
-				gfv[bi] = gfloor;
-			}
-		}
-		WSYNC(); // (every lane has read the band energies: the gains take their place)
-#pragma unroll
-		for (int bi = 0; bi < NBL; ++bi) {
-			const int b = lane + bi * G;
-			if (b < NB_BANDS) {
-				bandv[b] = g2v[bi];
-				bandv[NB_BANDS + b] = gv[bi];
-				bandv[2 * NB_BANDS + b] = gfv[bi];
-			}
-		}
-		WSYNC();
-		float gain2[K];
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			const int bl = a.t.bleft[e0 + k], br = bl + 1;
-			auto psd = [&](const float *mel) -> float {
-				float t = mel[bl] * wl[k];
-				t += mel[br] * wr[k];
-				return t;
-			};
-			const float p = psd(bandv);
-			const float gain_bark = psd(bandv + NB_BANDS);
-			const float gfl = psd(bandv + 2 * NB_BANDS);
-			const float prior_ratio = prior[k] / (prior[k] + 1.f);
-			const float theta = prior_ratio * (1.f + post[k]);
-			const float MM = hypergeom_gain(theta);
-			float gg = prior_ratio * MM;
-			if (gg > 1.f) gg = 1.f;
-			if (.333f * gg > gain_bark) gg = 3 * gain_bark;
-			float gain = gg;
-			old_ps[k] = .2f * old_ps[k] + (.8f * (gain * gain)) * ps[k];
-			if (gain < gfl) gain = gfl;
-			const float tmp = p * sqrt_via_double(gain) + (1.0f - p) * sqrt_via_double(gfl);
-			gain2[k] = tmp * tmp;
-		}
-		const float g_last = GP::last(gain2[K - 1]); // gain2[F-1] scales the Nyquist term
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			if (e0 + k == 0) {
-				ft[k].x = gain2[k] * ft[k].x;
-				ft[k].y = g_last * ft[k].y;
-			} else {
-				ft[k].x = gain2[k] * ft[k].x;
-				ft[k].y = gain2[k] * ft[k].y;
-			}
-		}
-		g_rfft_inverse<F>(L, LW, ft);
-		{
-			float lo[K], hi[K];
-			load_vec<K>(w_time(L) + e0, lo);
-			load_vec<K>(w_time(L) + F + e0, hi);
-#pragma unroll
-			for (int k = 0; k < K; ++k) {
-				out_f[k] = word2int(ob[k] + lo[k] * w0[k]);
-				ob[k] = hi[k] * w1[k];
-			}
-		}
-	}
+	postfilter_frame<GP>(L, LW, a.t, L.vec, L.band, sc, pf, xcur, out_f);
 	store_out(out_f);
-	bstore_vec<K>(rS, vb4, SL::ECHON * 4, en);
-	bstore_vec<K>(rS, vb4, SL::INBUF * 4, inb);
-	bstore_vec<K>(rS, vb4, SL::S_ * 4, S);
-	bstore_vec<K>(rS, vb4, SL::SMIN * 4, Smin);
-	bstore_vec<K>(rS, vb4, SL::STMP * 4, Stmp);
-	bstore_vec<K>(rS, vb4, SL::NOISE * 4, noise);
-	bstore_vec<K>(rS, vb4, SL::OLDPS * 4, old_ps);
-	bstore_vec<K>(rS, vb4, SL::ZETA * 4, zeta);
-	bstore_vec<K>(rS, vb4, SL::OUTBUF * 4, ob);
+	pf_store<GP>(rS, vb4, pf);
 #pragma unroll
 	for (int bi = 0; bi < NBL; ++bi) {
 		const int b = lane + bi * G;
 		if (b < NB_BANDS) {
-			g_store_f(rS, oS + (unsigned)(SL::OLDPS_B + b) * 4u, old_ps_b[bi]);
-			g_store_f(rS, oS + (unsigned)(SL::ZETA_B + b) * 4u, zeta_b[bi]);
+			g_store_f(rS, oS + (unsigned)(SL::OLDPS_B + b) * 4u, pf.old_ps_b[bi]);
+			g_store_f(rS, oS + (unsigned)(SL::ZETA_B + b) * 4u, pf.zeta_b[bi]);
 		}
 	}
 	sc.fg_pending = pendingFG ? 1 : 0, sc.bg_pending = pendingBG ? 1 : 0;

@@ -1,6 +1,8 @@
 // aec_tick.hpp -- the AEC kernels in their per-TICK form (included by aec.hip after aec_wave.hpp, whose FFT / ordered-sum
-// helpers they share).  One launch serves every frame a stream has ready in this 10 ms tick: at 48 kHz the filter's
-// 256-sample frames (speexec.c:171-180) make that one or two frames (15 per 8 ticks).
+// helpers they use, and aec_steps.hpp, whose steps of a frame they compose with Wave<F> as the lanes policy).  One launch
+// serves every frame a stream has ready in this 10 ms tick: at 48 kHz the filter's 256-sample frames (speexec.c:171-180)
+// make that one or two frames (15 per 8 ticks).  What is written here is what only this form has: the FIFOs and the folded
+// resampler, the leg lists, the streaming passes and their two-frame machinery, the state parked in LDS, the barriers.
 //
 // Why per tick: the canceller is HBM-bound, and with both frames of a tick inside one wavefront
 //   * the per-stream "small" state (error spectrum, step sizes, power / Eh / Yh, post-filter estimates: ~40 KB moved per
@@ -20,32 +22,40 @@
 // Cost: the second frame's far-end spectrum is needed early, and ~50 more live registers: 2 waves per SIMD at F = 256
 // instead of 3 (measured on the per-frame kernel: 1.5 % slower per launch at that occupancy; the bytes saved are ~20 %).
 
+// The per-stream small-state block, offsets in floats: written ONCE, as a function of the frame size that the host calls
+// too (mi_aec_create sizes the block with it, init_state and mi_aec_get find the arrays with it).
+struct SmallLayout {
+	int XPREV;   // F   pre-emphasised far end of the last frame (first half of the next FFT input)
+	int E;       // 2F  error spectrum of the last frame, bin-interleaved
+	int POWER;   // F   (+1 in TAIL)
+	int POWER1, EH, YH;
+	int LASTY;   // 2F  echo estimate of the last two frames [older | newest] (3F reserved)
+	int ECHON, INBUF, OUTBUF, NOISE, OLDPS, ZETA, S_, SMIN, STMP; // post-filter, F each
+	int MISC;
+	int PROP;    // M <= 64
+	int WNORM;   // M
+	int TAIL;    // POWER[F], POWER1[F], EH[F], YH[F]
+	int OLDPS_B; // 24 Bark bands
+	int ZETA_B;
+	int FGNORM;  // M: |foreground block|^2, what WNORM becomes when the background is reset to it
+	int TOTAL;
+};
+__host__ __device__ constexpr SmallLayout small_layout(int F) {
+	SmallLayout l{};
+	l.XPREV = 0, l.E = F, l.POWER = 3 * F, l.POWER1 = 4 * F, l.EH = 5 * F, l.YH = 6 * F, l.LASTY = 7 * F;
+	l.ECHON = 10 * F, l.INBUF = 11 * F, l.OUTBUF = 12 * F, l.NOISE = 13 * F, l.OLDPS = 14 * F, l.ZETA = 15 * F;
+	l.S_ = 16 * F, l.SMIN = 17 * F, l.STMP = 18 * F, l.MISC = 19 * F;
+	l.PROP = l.MISC, l.WNORM = l.MISC + 64, l.TAIL = l.MISC + 128, l.OLDPS_B = l.MISC + 136, l.ZETA_B = l.MISC + 160, l.FGNORM = l.MISC + 192;
+	l.TOTAL = 19 * F + 256;
+	return l;
+}
 template <int F>
-struct TickLayout { // offsets in floats inside the per-stream small-state block
-	static constexpr int XPREV = 0;          // F   pre-emphasised far end of the last frame (first half of the next FFT input)
-	static constexpr int E = F;              // 2F  error spectrum of the last frame, bin-interleaved
-	static constexpr int POWER = 3 * F;      // F   (+1 in TAIL)
-	static constexpr int POWER1 = 4 * F;
-	static constexpr int EH = 5 * F;
-	static constexpr int YH = 6 * F;
-	static constexpr int LASTY = 7 * F;      // 2F  echo estimate of the last two frames [older | newest] (3F reserved)
-	static constexpr int ECHON = 10 * F;     // post-filter
-	static constexpr int INBUF = 11 * F;
-	static constexpr int OUTBUF = 12 * F;
-	static constexpr int NOISE = 13 * F;
-	static constexpr int OLDPS = 14 * F;
-	static constexpr int ZETA = 15 * F;
-	static constexpr int S_ = 16 * F;
-	static constexpr int SMIN = 17 * F;
-	static constexpr int STMP = 18 * F;
-	static constexpr int MISC = 19 * F;
-	static constexpr int PROP = MISC;        // M <= 64
-	static constexpr int WNORM = MISC + 64;  // M
-	static constexpr int TAIL = MISC + 128;  // POWER[F], POWER1[F], EH[F], YH[F]
-	static constexpr int OLDPS_B = MISC + 136; // 24 Bark bands
-	static constexpr int ZETA_B = MISC + 160;
-	static constexpr int FGNORM = MISC + 192; // M: |foreground block|^2, what WNORM becomes when the background is reset to it
-	static constexpr int TOTAL = 19 * F + 256;
+struct TickLayout { // the same as compile-time constants of a kernel
+	static constexpr SmallLayout L = small_layout(F);
+	static constexpr int XPREV = L.XPREV, E = L.E, POWER = L.POWER, POWER1 = L.POWER1, EH = L.EH, YH = L.YH, LASTY = L.LASTY;
+	static constexpr int ECHON = L.ECHON, INBUF = L.INBUF, OUTBUF = L.OUTBUF, NOISE = L.NOISE, OLDPS = L.OLDPS, ZETA = L.ZETA;
+	static constexpr int S_ = L.S_, SMIN = L.SMIN, STMP = L.STMP, PROP = L.PROP, WNORM = L.WNORM, TAIL = L.TAIL;
+	static constexpr int OLDPS_B = L.OLDPS_B, ZETA_B = L.ZETA_B, FGNORM = L.FGNORM, TOTAL = L.TOTAL;
 };
 
 // LDS of the canceller kernel: FFT work space + tables and the per-bin state parked while the blocks stream (none of the
@@ -147,6 +157,44 @@ __device__ __forceinline__ void bstore_vec(rsrc_t r, unsigned voff, unsigned sof
 	}
 }
 
+// the post-filter's per-bin state of a leg (aec_steps.hpp: PfState) from / to its small-state block, its tables alongside
+// (vb4: this lane's byte offset into a per-bin array; the Bark-band entries are the kernel's: one lane per band or two)
+template <typename P>
+__device__ __forceinline__ void pf_load(rsrc_t rS, unsigned vb4, const AecTables &t, PfState<P> &pf) {
+	using SL = TickLayout<P::F>;
+	constexpr int K = P::K, F = P::F;
+	const int e0 = P::lane() * K;
+	bload_vec<K>(rS, vb4, SL::ECHON * 4, pf.en);
+	bload_vec<K>(rS, vb4, SL::INBUF * 4, pf.inb);
+	bload_vec<K>(rS, vb4, SL::S_ * 4, pf.S);
+	bload_vec<K>(rS, vb4, SL::SMIN * 4, pf.Smin);
+	bload_vec<K>(rS, vb4, SL::STMP * 4, pf.Stmp);
+	bload_vec<K>(rS, vb4, SL::NOISE * 4, pf.noise);
+	bload_vec<K>(rS, vb4, SL::OLDPS * 4, pf.old_ps);
+	bload_vec<K>(rS, vb4, SL::ZETA * 4, pf.zeta);
+	bload_vec<K>(rS, vb4, SL::OUTBUF * 4, pf.ob);
+	load_vec<K>(t.bfl + e0, pf.wl);
+	load_vec<K>(t.bfr + e0, pf.wr);
+	load_vec<K>(t.hann + e0, pf.h0);
+	load_vec<K>(t.hann + F + e0, pf.h1);
+	load_vec<K>(t.pwin + e0, pf.w0);
+	load_vec<K>(t.pwin + F + e0, pf.w1);
+}
+template <typename P>
+__device__ __forceinline__ void pf_store(rsrc_t rS, unsigned vb4, const PfState<P> &pf) {
+	using SL = TickLayout<P::F>;
+	constexpr int K = P::K;
+	bstore_vec<K>(rS, vb4, SL::ECHON * 4, pf.en);
+	bstore_vec<K>(rS, vb4, SL::INBUF * 4, pf.inb);
+	bstore_vec<K>(rS, vb4, SL::S_ * 4, pf.S);
+	bstore_vec<K>(rS, vb4, SL::SMIN * 4, pf.Smin);
+	bstore_vec<K>(rS, vb4, SL::STMP * 4, pf.Stmp);
+	bstore_vec<K>(rS, vb4, SL::NOISE * 4, pf.noise);
+	bstore_vec<K>(rS, vb4, SL::OLDPS * 4, pf.old_ps);
+	bstore_vec<K>(rS, vb4, SL::ZETA * 4, pf.zeta);
+	bstore_vec<K>(rS, vb4, SL::OUTBUF * 4, pf.ob);
+}
+
 // acc += x w, bin by bin; bin 0 (lane 0's first) holds (DC, Nyquist): two real products there
 template <int K, typename TA, typename TX, typename TW>
 __device__ __forceinline__ void cmac_bins(TA (&acc)[K], const TX (&x)[K], const TW (&w)[K], int e0) {
@@ -206,6 +254,7 @@ template <int F, int MODE>
 __global__ __launch_bounds__(64, F == 512 ? 1 : (F == 256 ? 2 : (F == 128 ? 3 : 4))) void aec_tick_kernel(AecArgs a) {
 	__shared__ TLds<F> L;
 	using SL = TickLayout<F>;
+	using WP = Wave<F>; // the lanes policy of the shared steps (aec_steps.hpp): the leg is the wavefront
 	constexpr int N = 2 * F, K = F / 64;
 	// ---- which leg this wavefront serves.  Rows / per-frame entries: leg = block.  FIFO entry: the leg comes out of a list
 	// the PREVIOUS tick's launch sorted (TickOrder above) -- legs that will run two frames first, the short ones last, one
@@ -430,19 +479,7 @@ __global__ __launch_bounds__(64, F == 512 ? 1 : (F == 256 ? 2 : (F == 128 ? 3 : 
 		float far[K];
 #pragma unroll
 		for (int k = 0; k < K; ++k) far[k] = (float)ref_at(f, e0 + k);
-		float prev = __shfl_up(far[K - 1], 1);
-		if (lane == 0) prev = sc.memX;
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			xn[k] = far[k] - .9f * prev;
-			prev = far[k];
-		}
-		sc.memX = rdlane(far[K - 1], 63);
-		Sxx = WSeq<K>::inner_prod(xn, xn);
-		WSYNC();
-		store_vec<K>(L.tbuf + e0, xp);
-		store_vec<K>(L.tbuf + F + e0, xn);
-		w_rfft_forward<F>(L, a.t, X0);
+		far_end<WP>(L, a.t, far, xp, sc.memX, xn, X0, Sxx);
 	};
 
 	float2 X0[K], X0B[K]; // far-end spectrum of the frame at hand / of the frame behind it
@@ -510,28 +547,10 @@ __global__ __launch_bounds__(64, F == 512 ? 1 : (F == 256 ? 2 : (F == 128 ? 3 : 
 		// ---- near end: saturation flag, DC notch (serial IIR), pre-emphasis
 		int any_sat;
 		{
-			float input[K];
-			float fin[K];
-			bool satl = false;
+			float input[K], fin[K];
 #pragma unroll
-			for (int k = 0; k < K; ++k) {
-				const int m = mic_at(f, e0 + k);
-				fin[k] = (float)m;
-				satl |= (m <= -32000 || m >= 32000);
-			}
-			any_sat = __any(satl);
-			const float radius = a.notch_radius;
-			const float den2 = (float)(radius * radius + .7 * (1 - radius) * (1 - radius));
-			float v[K];
-			w_dc_notch<K>(fin, radius, den2, sc.notch0, sc.notch1, v);
-			float vprev = __shfl_up(v[K - 1], 1);
-			if (lane == 0) vprev = sc.memD;
-#pragma unroll
-			for (int k = 0; k < K; ++k) {
-				input[k] = v[k] - .9f * vprev;
-				vprev = v[k];
-			}
-			sc.memD = rdlane(v[K - 1], 63);
+			for (int k = 0; k < K; ++k) fin[k] = (float)mic_at(f, e0 + k);
+			any_sat = near_end<WP>(fin, a.notch_radius, sc, input);
 			store_vec<K>(L.input + e0, input);
 		}
 		sc.cancel_count++;
@@ -540,17 +559,8 @@ __global__ __launch_bounds__(64, F == 512 ? 1 : (F == 256 ? 2 : (F == 128 ? 3 : 
 		// ---- newest far-end spectrum into the ring; its power spectrum is all the rest of the frame needs of it
 		sc.xhead = head;
 		bstore_bins<K>(rX, vb8, (unsigned)head * (F * 8), X0);
-		float Xf[K], Xf_F = 0;
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			if (e0 + k == 0) {
-				Xf[k] = X0[k].x * X0[k].x;
-				Xf_F = X0[k].y * X0[k].y;
-			} else {
-				Xf[k] = X0[k].x * X0[k].x + X0[k].y * X0[k].y;
-			}
-		}
-		Xf_F = rdlane(Xf_F, 0);
+		float Xf[K], Xf_F;
+		bin_power<WP>(X0, Xf, Xf_F);
 
 		// ---- proportional step
 		if (sc.adapted) {
@@ -571,40 +581,10 @@ __global__ __launch_bounds__(64, F == 512 ? 1 : (F == 256 ? 2 : (F == 128 ? 3 : 
 		const bool do_grad = (sc.saturated == 0);
 		if (!do_grad) sc.saturated--;
 
-		// W += prop p1 conj(X) E, bin by bin (weighted_spectral_mul_conj); bin 0 = (DC, Nyquist): real products with their own steps
-		auto grad_with = [&](auto (&w)[K], const auto (&x)[K], float prop, const float2 (&E)[K], const float (&pp)[K], float pp_F) {
-#pragma unroll
-			for (int k = 0; k < K; ++k) {
-				const v2f xv = {x[k].x, x[k].y}, ev = {E[k].x, E[k].y};
-				const float Wt = prop * pp[k];
-				v2f st = pk_cmul_conj(xv, ev) * (v2f){Wt, Wt}; // Wt (x.x E.x + x.y E.y), Wt ((-x.y) E.x + x.x E.y)
-				if (k == 0) {
-					const v2f dc = (xv * ev) * (v2f){Wt, prop * pp_F}; // W0 (x.x E.x), WN (x.y E.y)
-					if (e0 == 0) st = dc;
-				}
-				const v2f r = (v2f){w[k].x, w[k].y} + st;
-				w[k].x = r.x, w[k].y = r.y;
-			}
-		};
-		auto grad = [&](auto (&w)[K], const auto (&x)[K], float prop) { grad_with(w, x, prop, Eprev, p1, p1_F); };
-
 		// ---- one streaming pass over the blocks (next block's loads in flight).  Block 0 and the round-robin block jc get
 		// the AUMDF constraint (IFFT, zero the second half, FFT) where the pass meets them: the blocks are independent of each
 		// other, only the sums over j have an order, and it stays ascending.
 		const int jc = (M > 1) ? (sc.cancel_count % (M - 1)) + 1 : -1;
-		auto constrain = [&](auto (&wv)[K]) {
-			float2 w[K];
-#pragma unroll
-			for (int k = 0; k < K; ++k) w[k] = make_float2(wv[k].x, wv[k].y);
-			w_rfft_inverse<F>(L, a.t, w);
-			float z[K];
-#pragma unroll
-			for (int k = 0; k < K; ++k) z[k] = 0.f;
-			store_vec<K>(w_time(L) + F + e0, z);
-			w_rfft_forward<F>(L, a.t, w, w_time(L));
-#pragma unroll
-			for (int k = 0; k < K; ++k) wv[k].x = w[k].x, wv[k].y = w[k].y;
-		};
 		float2 yfg[K], ybgs[K];
 #pragma unroll
 		for (int k = 0; k < K; ++k) yfg[k] = ybgs[k] = make_float2(0, 0);
@@ -639,8 +619,8 @@ __global__ __launch_bounds__(64, F == 512 ? 1 : (F == 256 ? 2 : (F == 128 ? 3 : 
 					bload_bins<K>(rWF, vb8, wsrc + (unsigned)jn * (F * 8), wl2);
 				}
 				const bool aumdf = (j == 0 || j == jc);
-				if (do_grad) grad(wl, xn, L.prop[j]);
-				if (aumdf) constrain(wl);
+				if (do_grad) gradient<WP>(wl, xn, L.prop[j], Eprev, p1, p1_F);
+				if (aumdf) constrain<WP>(L, a.t, wl);
 				if (lazy ? (aumdf || j == M - 1) : (do_grad || aumdf || carryBG || carryFG)) bstore_bins<K>(rWF, vb8, wdst + (unsigned)j * (F * 8), wl);
 				cmac_bins<K>(yfg, xj, fg, e0);
 				cmac_bins<K>(ybgs, xj, wl, e0);
@@ -693,13 +673,13 @@ __global__ __launch_bounds__(64, F == 512 ? 1 : (F == 256 ? 2 : (F == 128 ? 3 : 
 			const bool keepW1 = redo && carryFG;  // ... and then made them the foreground: they must exist in that half
 			auto block = [&](int j, v2f (&w)[K], const v2f (&xa)[K], const v2f (&xb)[K], const v2f (&xc)[K]) { // X(j), X(j+1), X(j+2)
 				if (redo && j != 0 && j != jc1 && j != M - 1) {
-					grad_with(w, xc, L.prop[32 + j], E1s, p1s, p1s_F);
+					gradient<WP>(w, xc, L.prop[32 + j], E1s, p1s, p1s_F);
 					if (keepW1) bstore_bins<K>(rWF, vb8, wo + (unsigned)j * (F * 8), w);
 				}
 				if (carryFG) cmac_bins<K>(spec2, xa, w, e0);
 				const bool aumdf = (j == 0 || j == jc);
-				if (do_grad) grad(w, xb, L.prop[j]);
-				if (aumdf) constrain(w);
+				if (do_grad) gradient<WP>(w, xb, L.prop[j], Eprev, p1, p1_F);
+				if (aumdf) constrain<WP>(L, a.t, w);
 				if (do_grad || aumdf || carryBG || carryFG || lazy1) bstore_bins<K>(rWF, vb8, wdst + (unsigned)j * (F * 8), w);
 				cmac_bins<K>(ybgs, xa, w, e0);
 				norm_of(w, j);
@@ -758,108 +738,31 @@ __global__ __launch_bounds__(64, F == 512 ? 1 : (F == 256 ? 2 : (F == 128 ? 3 : 
 		Dbf = 10 + Dbf;
 
 		// ---- two-path control
-		sc.Davg1 = .6f * sc.Davg1 + .4f * (Sff - See);
-		sc.Davg2 = .85f * sc.Davg2 + .15f * (Sff - See);
-		sc.Dvar1 = .36f * sc.Dvar1 + (.4f * Sff) * (.4f * Dbf);
-		sc.Dvar2 = .7225f * sc.Dvar2 + (.15f * Sff) * (.15f * Dbf);
-		bool update_foreground = false;
-		if ((Sff - See) * fabsf(Sff - See) > Sff * Dbf) update_foreground = true;
-		else if (sc.Davg1 * fabsf(sc.Davg1) > .5f * sc.Dvar1) update_foreground = true;
-		else if (sc.Davg2 * fabsf(sc.Davg2) > .25f * sc.Dvar2) update_foreground = true;
-		if (update_foreground) {
-			sc.fg_updates++;
-			sc.Davg1 = sc.Davg2 = 0;
-			sc.Dvar1 = sc.Dvar2 = 0;
+		if (two_path_update(sc, Sff, See, Dbf)) {
 			pendingFG = true; // the next pass over the filter (this tick's or the next one's) carries the copy out
 			WSYNC();
 			if (lane < M) fgnorm = L.wnorm[lane];
-			float h0[K], h1[K];
-			load_vec<K>(a.t.hann + e0, h0);
-			load_vec<K>(a.t.hann + F + e0, h1);
-#pragma unroll
-			for (int k = 0; k < K; ++k) efg[k] = h1[k] * efg[k] + h0[k] * ybg[k];
-		} else {
-			bool reset_background = false;
-			if ((-(Sff - See)) * fabsf(Sff - See) > 4.f * (Sff * Dbf)) reset_background = true;
-			if ((-sc.Davg1) * fabsf(sc.Davg1) > 4.f * sc.Dvar1) reset_background = true;
-			if ((-sc.Davg2) * fabsf(sc.Davg2) > 4.f * sc.Dvar2) reset_background = true;
-			if (reset_background) {
-				sc.bg_resets++;
-				pendingBG = true; // the next pass reads the foreground's blocks as the background's
-				WSYNC();
-				if (lane < M) L.wnorm[lane] = fgnorm;
-#pragma unroll
-				for (int k = 0; k < K; ++k) {
-					ybg[k] = efg[k];
-					e2[k] = input[k] - efg[k];
-				}
-				See = Sff;
-				sc.Davg1 = sc.Davg2 = 0;
-				sc.Dvar1 = sc.Dvar2 = 0;
-			}
-		}
-
-		// ---- output (serial de-emphasis) and correlations
-		int out_i[K];
-		{
-			float d[K], tout[K];
-#pragma unroll
-			for (int k = 0; k < K; ++k) d[k] = input[k] - efg[k];
-			w_deemphasis<K>(d, sc.memE, tout);
-#pragma unroll
-			for (int k = 0; k < K; ++k) out_i[k] = word2int(tout[k]);
-		}
-		float Sey, Syy, Sdd;
-		WSeq<K>::inner_prod3(e2, ybg, ybg, ybg, input, input, Sey, Syy, Sdd);
-		if (any_sat && sc.saturated == 0) sc.saturated = 1;
-
-		// ---- error / response spectra
-		float2 Ecur[K], Ycur[K];
-		{
-			float z[K];
-#pragma unroll
-			for (int k = 0; k < K; ++k) z[k] = 0.f;
+			blend_foreground<WP>(a.t.hann, efg, ybg);
+		} else if (two_path_reset(sc, Sff, See, Dbf)) {
+			pendingBG = true; // the next pass reads the foreground's blocks as the background's
 			WSYNC();
-			store_vec<K>(L.tbuf + e0, z);
-			store_vec<K>(L.tbuf + F + e0, e2);
-			w_rfft_forward<F>(L, a.t, Ecur);
-			store_vec<K>(L.tbuf + e0, z);
-			store_vec<K>(L.tbuf + F + e0, ybg);
-			w_rfft_forward<F>(L, a.t, Ycur);
+			if (lane < M) L.wnorm[lane] = fgnorm;
+			take_foreground<WP>(efg, input, Sff, ybg, e2, See);
 		}
-		float Rf[K], Yf[K], Rf_F = 0, Yf_F = 0;
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			if (e0 + k == 0) {
-				Rf[k] = Ecur[k].x * Ecur[k].x;
-				Rf_F = Ecur[k].y * Ecur[k].y;
-				Yf[k] = Ycur[k].x * Ycur[k].x;
-				Yf_F = Ycur[k].y * Ycur[k].y;
-			} else {
-				Rf[k] = Ecur[k].x * Ecur[k].x + Ecur[k].y * Ecur[k].y;
-				Yf[k] = Ycur[k].x * Ycur[k].x + Ycur[k].y * Ycur[k].y;
-			}
-		}
-		// the Nyquist powers live in lane 0; everyone needs them for the ordered sums below
-		Rf_F = rdlane(Rf_F, 0);
-		Yf_F = rdlane(Yf_F, 0);
+
+		int out_i[K];
+		float Sey, Syy, Sdd;
+		output_and_correlations<WP>(sc, input, efg, e2, ybg, any_sat, out_i, Sey, Syy, Sdd);
+
+		float2 Ecur[K], Ycur[K];
+		error_spectra<WP>(L, a.t, e2, ybg, Ecur, Ycur);
+		float Rf[K], Yf[K], Rf_F, Yf_F;
+		bin_power<WP>(Ecur, Rf, Rf_F);
+		bin_power<WP>(Ycur, Yf, Yf_F);
 #pragma unroll
 		for (int k = 0; k < K; ++k) Eprev[k] = Ecur[k];
 
-		// ---- sanity checks
-		bool zero_out = false;
-		if (!(Syy >= 0 && Sxx >= 0 && See >= 0) || !(Sff < N * 1e9 && Syy < N * 1e9 && Sxx < N * 1e9)) {
-			sc.screwed_up += 50;
-			zero_out = true;
-		} else if (Sff > Sdd + (float)(N * 10000)) {
-			sc.screwed_up++;
-		} else {
-			sc.screwed_up = 0;
-		}
-		if (zero_out) {
-#pragma unroll
-			for (int k = 0; k < K; ++k) out_i[k] = 0;
-		}
+		sanity_checks<WP>(sc, Sff, See, Sxx, Syy, Sdd, out_i);
 		int16_t *op = out_ptr(f);
 		auto emit = [&](const int (&o)[K]) { // to the post-filter phase through LDS, else straight out
 #pragma unroll
@@ -897,16 +800,7 @@ __global__ __launch_bounds__(64, F == 512 ? 1 : (F == 256 ? 2 : (F == 128 ? 3 : 
 			bstore_vec<K>(rS, vb4, SL::LASTY * 4, z);
 			bstore_vec<K>(rS, vb4, (SL::LASTY + F) * 4, z);
 			bstore_vec<K>(rS, vb4, (SL::LASTY + (2) * F) * 4, z);
-			sc.state_resets++;
-			sc.cancel_count = 0;
-			sc.screwed_up = 0;
-			sc.notch0 = sc.notch1 = 0;
-			sc.memD = sc.memE = sc.memX = 0;
-			sc.saturated = 0;
-			sc.adapted = 0;
-			sc.sum_adapt = 0;
-			sc.Pey = sc.Pyy = 1.0f;
-			sc.Davg1 = sc.Davg2 = sc.Dvar1 = sc.Dvar2 = 0;
+			reset_scalars(sc);
 			pendingFG = pendingBG = false;
 			if (f) resetf[1] = true, leakf[1] = sc.leak_estimate;
 			else resetf[0] = true, leakf[0] = sc.leak_estimate;
@@ -926,75 +820,20 @@ __global__ __launch_bounds__(64, F == 512 ? 1 : (F == 256 ? 2 : (F == 128 ? 3 : 
 		// ---- far-end power, leak estimate
 		float pw[K];
 		load_vec<K>(L.pw + e0, pw);
-#pragma unroll
-		for (int k = 0; k < K; ++k) pw[k] = a.ss_1 * pw[k] + 1 + a.ss * Xf[k];
+		far_power<WP>(a, Xf, Xf_F, pw, pw_F);
 		store_vec<K>(L.pw + e0, pw);
-		pw_F = a.ss_1 * pw_F + 1 + a.ss * Xf_F;
 		float Ehd[K], Yhd[K], Ehd_F, Yhd_F;
 		{
 			float eh[K], yh[K];
 			load_vec<K>(L.eh + e0, eh);
 			load_vec<K>(L.yh + e0, yh);
-#pragma unroll
-			for (int k = 0; k < K; ++k) {
-				Ehd[k] = Rf[k] - eh[k];
-				Yhd[k] = Yf[k] - yh[k];
-				eh[k] = (1 - a.spec_average) * eh[k] + a.spec_average * Rf[k];
-				yh[k] = (1 - a.spec_average) * yh[k] + a.spec_average * Yf[k];
-			}
+			spectral_averages<WP>(a, Rf, Rf_F, Yf, Yf_F, eh, eh_F, yh, yh_F, Ehd, Ehd_F, Yhd, Yhd_F);
 			store_vec<K>(L.eh + e0, eh);
 			store_vec<K>(L.yh + e0, yh);
 		}
-		Ehd_F = Rf_F - eh_F;
-		Yhd_F = Yf_F - yh_F;
-		eh_F = (1 - a.spec_average) * eh_F + a.spec_average * Rf_F;
-		yh_F = (1 - a.spec_average) * yh_F + a.spec_average * Yf_F;
-		float Pey = 1.0f, Pyy = 1.0f;
-		Pey = Pey + Ehd_F * Yhd_F;
-		Pyy = Pyy + Yhd_F * Yhd_F;
-		WSeq<K>::dot_desc2(Pey, Ehd, Yhd, Pyy, Yhd, Yhd, Pey, Pyy);
-		Pyy = sqrt_via_double(Pyy);
-		Pey = Pey / Pyy;
-		float tmp32 = a.beta0 * Syy;
-		if (tmp32 > a.beta_max * See) tmp32 = a.beta_max * See;
-		const float alpha = tmp32 / See;
-		const float alpha_1 = 1.0f - alpha;
-		sc.Pey = alpha_1 * sc.Pey + alpha * Pey;
-		sc.Pyy = alpha_1 * sc.Pyy + alpha * Pyy;
-		if (sc.Pyy < 1.0f) sc.Pyy = 1.0f;
-		if (sc.Pey < .005f * sc.Pyy) sc.Pey = .005f * sc.Pyy;
-		if (sc.Pey > sc.Pyy) sc.Pey = sc.Pyy;
-		sc.leak_estimate = sc.Pey / sc.Pyy;
-		float RER = (float)((.0001 * Sxx2 + 3. * (sc.leak_estimate * Syy)) / See);
-		if (RER < Sey * Sey / (1 + See * Syy)) RER = Sey * Sey / (1 + See * Syy);
-		if (RER > .5) RER = .5;
-		int m_here = M; // (converted HERE: hoisted to the kernel's entry the float lived -- spilled to scratch -- through the whole tick)
+		int m_here = M; // (converted by the step, HERE: hoisted to the kernel's entry the float lived -- spilled to scratch -- through the whole tick)
 		asm volatile("" : "+s"(m_here));
-		if (!sc.adapted && sc.sum_adapt > (float)m_here && sc.leak_estimate * Syy > .03f * Syy) sc.adapted = 1;
-
-		auto step = [&](float Yfv, float Rfv, float pwv) -> float {
-			float r = sc.leak_estimate * Yfv;
-			const float e = Rfv + 1;
-			if (r > .5 * e) r = (float)(.5 * e);
-			r = .7f * r + .3f * (float)(RER * e);
-			return r / (e * (pwv + 10));
-		};
-		if (sc.adapted) {
-#pragma unroll
-			for (int k = 0; k < K; ++k) p1[k] = step(Yf[k], Rf[k], pw[k]);
-			p1_F = step(Yf_F, Rf_F, pw_F);
-		} else {
-			float adapt_rate = 0;
-			if (Sxx2 > (float)(N * 1000)) {
-				tmp32 = .25f * Sxx2;
-				if (tmp32 > .25 * See) tmp32 = (float)(.25 * See);
-				adapt_rate = tmp32 / See;
-			}
-#pragma unroll
-			for (int k = 0; k < K; ++k) p1[k] = adapt_rate / (pw[k] + 10);
-			p1_F = adapt_rate / (pw_F + 10);
-			sc.sum_adapt = sc.sum_adapt + adapt_rate;
-		}
+		leak_and_steps<WP>(a, sc, m_here, Sxx2, See, Syy, Sey, Ehd, Ehd_F, Yhd, Yhd_F, Rf, Rf_F, Yf, Yf_F, pw, pw_F, p1, p1_F);
 
 		// ---- echo estimate of this frame for the residual-echo stage (ring of three frames)
 		{
@@ -1054,251 +893,35 @@ __global__ __launch_bounds__(64, F == 512 ? 1 : (F == 256 ? 2 : (F == 128 ? 3 : 
 	}
 	WSYNC(); // the parked arrays are re-used from here on
 
-	// per-bin state of the tick, in registers
-	float en[K], inb[K], S[K], Smin[K], Stmp[K], noise[K], old_ps[K], zeta[K], ob[K], wl[K], wr[K], h0[K], h1[K], w0[K], w1[K];
-	bload_vec<K>(rS, vb4, SL::ECHON * 4, en);
-	bload_vec<K>(rS, vb4, SL::INBUF * 4, inb);
-	bload_vec<K>(rS, vb4, SL::S_ * 4, S);
-	bload_vec<K>(rS, vb4, SL::SMIN * 4, Smin);
-	bload_vec<K>(rS, vb4, SL::STMP * 4, Stmp);
-	bload_vec<K>(rS, vb4, SL::NOISE * 4, noise);
-	bload_vec<K>(rS, vb4, SL::OLDPS * 4, old_ps);
-	bload_vec<K>(rS, vb4, SL::ZETA * 4, zeta);
-	bload_vec<K>(rS, vb4, SL::OUTBUF * 4, ob);
-	load_vec<K>(a.t.bfl + e0, wl);
-	load_vec<K>(a.t.bfr + e0, wr);
-	load_vec<K>(a.t.hann + e0, h0);
-	load_vec<K>(a.t.hann + F + e0, h1);
-	load_vec<K>(a.t.pwin + e0, w0);
-	load_vec<K>(a.t.pwin + F + e0, w1);
-	float old_ps_b = 0, zeta_b = 0;
+	// ---- the tail phase: the residual-echo / noise post-filter of the tick's frames, per-bin state in registers, band b in lane b
+	PfState<WP> pf;
+	pf_load<WP>(rS, vb4, a.t, pf);
+	pf.old_ps_b[0] = pf.zeta_b[0] = 0;
 	if (lane < NB_BANDS) {
-		old_ps_b = sm[SL::OLDPS_B + lane];
-		zeta_b = sm[SL::ZETA_B + lane];
+		pf.old_ps_b[0] = sm[SL::OLDPS_B + lane];
+		pf.zeta_b[0] = sm[SL::ZETA_B + lane];
 	}
-	float *pl = L.spec, *pr = L.spec + F;
-	float *bandv = L.band();
-	float *lvec = L.vec();
-
 	for (int f = 0; f < nf; ++f) {
-		sc.nb_adapt++;
-		if (sc.nb_adapt > 20000) sc.nb_adapt = 20000;
-		sc.min_count++;
-		float beta = 1.0f / sc.nb_adapt;
-		if (beta < .03f) beta = .03f;
-		const float beta_1 = 1.0f - beta;
-		const float leak = f ? leakf[1] : leakf[0];
-		const bool was_reset = f ? resetf[1] : resetf[0];
-
-		// residual echo spectrum (speex_echo_get_residual)
 		{
 			float lo[K], ln[K];
 			load_vec<K>(L.ly[f] + e0, lo);
 			load_vec<K>(L.ly[f + 1] + e0, ln);
-#pragma unroll
-			for (int k = 0; k < K; ++k) lo[k] = h0[k] * (was_reset ? 0.f : lo[k]), ln[k] = h1[k] * ln[k];
-			WSYNC();
-			store_vec<K>(L.tbuf + e0, lo);
-			store_vec<K>(L.tbuf + F + e0, ln);
+			residual_echo<WP>(L, a.t, pf, lo, ln, f ? resetf[1] : resetf[0], f ? leakf[1] : leakf[0]);
 		}
-		float2 Yr[K];
-		w_rfft_forward<F>(L, a.t, Yr);
-		const float leak2 = (leak > .5) ? 1.f : 2 * leak;
-		float res[K];
+		float xcur[K];
 #pragma unroll
-		for (int k = 0; k < K; ++k) {
-			const float r = (e0 + k == 0) ? Yr[k].x * Yr[k].x : Yr[k].x * Yr[k].x + Yr[k].y * Yr[k].y;
-			res[k] = (float)(int32_t)(leak2 * r);
-		}
-		const float res0 = rdlane(res[0], 0);
-		const bool bad = !(res0 >= 0 && res0 < F * 1e9f);
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			const float rr = bad ? 0.f : res[k];
-			const float c = .6f * en[k];
-			en[k] = c > rr ? c : rr;
-			pl[e0 + k] = wl[k] * en[k];
-			pr[e0 + k] = wr[k] * en[k];
-		}
-		// analysis frame [inbuf, x] * window
+		for (int k = 0; k < K; ++k) xcur[k] = (float)L.outf[f][e0 + k];
+		int out_f[K];
+		postfilter_frame<WP>(L, a.t, a.t, L.vec(), L.band(), sc, pf, xcur, out_f);
 		int16_t *op = out_ptr(f);
-		{
-			float xcur[K], a0[K], a1[K];
 #pragma unroll
-			for (int k = 0; k < K; ++k) {
-				xcur[k] = (float)L.outf[f][e0 + k];
-				a0[k] = inb[k] * w0[k];
-				a1[k] = xcur[k] * w1[k];
-				inb[k] = xcur[k];
-			}
-			store_vec<K>(L.tbuf + e0, a0);
-			store_vec<K>(L.tbuf + F + e0, a1);
-		}
-		float2 ft[K];
-		w_rfft_forward<F>(L, a.t, ft);
-		float ps[K];
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			ps[k] = (e0 + k == 0) ? ft[k].x * ft[k].x : ft[k].x * ft[k].x + ft[k].y * ft[k].y;
-			lvec[e0 + k] = ps[k];
-			L.tbuf[e0 + k] = wl[k] * ps[k];     // the analysis transform is done with its input: the frame's filterbank
-			L.tbuf[F + e0 + k] = wr[k] * ps[k]; // products wait there (left halves, right halves) for the fused band sums
-		}
-		WSYNC();
-		// update_noise_prob
-		int min_range;
-		if (sc.nb_adapt < 100) min_range = 15;
-		else if (sc.nb_adapt < 1000) min_range = 50;
-		else if (sc.nb_adapt < 10000) min_range = 150;
-		else min_range = 300;
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			const int b = e0 + k;
-			if (b == 0 || b == F - 1) S[k] = .8f * S[k] + .2f * ps[k];
-			else S[k] = .8f * S[k] + .05f * lvec[b - 1] + .1f * ps[k] + .05f * lvec[b + 1];
-			if (sc.nb_adapt == 1) Smin[k] = Stmp[k] = 0;
-			if (sc.min_count > min_range) {
-				Smin[k] = Stmp[k] < S[k] ? Stmp[k] : S[k];
-				Stmp[k] = S[k];
-			} else {
-				Smin[k] = Smin[k] < S[k] ? Smin[k] : S[k];
-				Stmp[k] = Stmp[k] < S[k] ? Stmp[k] : S[k];
-			}
-			const int update_prob = (.4f * S[k] > Smin[k]) ? 1 : 0;
-			if (!update_prob || ps[k] < noise[k]) {
-				const float v = beta_1 * noise[k] + beta * ps[k];
-				noise[k] = v > 0 ? v : 0;
-			}
-		}
-		if (sc.min_count > min_range) sc.min_count = 0;
-		{
-			float *np = w_time(L); // free between the analysis and the synthesis transform
-#pragma unroll
-			for (int k = 0; k < K; ++k) {
-				np[e0 + k] = wl[k] * noise[k];
-				np[F + e0 + k] = wr[k] * noise[k];
-			}
-			WSYNC();
-			// echo estimate (products in L.spec since the start of the frame), frame, noise: three band sums in one loop
-			if (lane < NB_BANDS) band_sum3<F>(a.t, lane, L.spec, L.tbuf, np, bandv[lane], bandv[NB_BANDS + lane], bandv[2 * NB_BANDS + lane]);
-		}
-		WSYNC();
-
-		auto snr = [&](float psv, float noisev, float echov, float oldps, float &post, float &prior) {
-			const float tot_noise = 1.f + noisev + echov + 0.f;
-			post = psv / tot_noise - 1.f;
-			if (post > 100.f) post = 100.f;
-			const float t = oldps / (oldps + tot_noise);
-			const float gamma = .1f + .89f * (t * t);
-			prior = gamma * (post > 0 ? post : 0) + (1.0f - gamma) * (oldps / tot_noise);
-			if (prior > 100.f) prior = 100.f;
-		};
-		float post[K], prior[K];
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			if (sc.nb_adapt == 1) old_ps[k] = ps[k];
-			snr(ps[k], noise[k], en[k], old_ps[k], post[k], prior[k]);
-			lvec[e0 + k] = prior[k];
-		}
-		float post_b = 0, prior_b = 0, ps_b = 0;
-		if (lane < NB_BANDS) {
-			ps_b = bandv[NB_BANDS + lane];
-			if (sc.nb_adapt == 1) old_ps_b = ps_b;
-			snr(ps_b, bandv[2 * NB_BANDS + lane], bandv[lane], old_ps_b, post_b, prior_b);
-		}
-		WSYNC();
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			const int b = e0 + k;
-			if (b == 0 || b >= F - 1) zeta[k] = .7f * zeta[k] + .3f * prior[k];
-			else zeta[k] = .7f * zeta[k] + .15f * prior[k] + .075f * lvec[b - 1] + .075f * lvec[b + 1];
-		}
-		if (lane < NB_BANDS) zeta_b = .7f * zeta_b + .3f * prior_b;
-		float Zframe = 0;
-#pragma unroll
-		for (int i = 0; i < NB_BANDS; ++i) Zframe = Zframe + rdlane(zeta_b, i);
-		const float Pframe = .1f + .899f * qcurve(Zframe / NB_BANDS);
-		const int eff_echo = (int)((1.0f - Pframe) * -40 + Pframe * -15);
-		if (lane < NB_BANDS) {
-			const float noise_floor = (float)exp((double)(.2302585f * -15));
-			const float echo_floor = (float)exp((double)(.2302585f * eff_echo));
-			const float nb = bandv[2 * NB_BANDS + lane], eb = bandv[lane];
-			const float gfloor = (float)(sqrt((double)(noise_floor * nb + echo_floor * eb)) / sqrt((double)(1 + nb + eb)));
-			const float prior_ratio = prior_b / (prior_b + 1.f);
-			const float theta = prior_ratio * (1.f + post_b);
-			const float MM = hypergeom_gain(theta);
-			float g = prior_ratio * MM;
-			if (g > 1.f) g = 1.f;
-			old_ps_b = .2f * old_ps_b + (.8f * (g * g)) * ps_b;
-			const float P1 = .199f + .8f * qcurve(zeta_b);
-			const float q = 1.0f - Pframe * P1;
-			const float g2 = (float)(1 / (1.f + (q / (1.f - q)) * (1 + prior_b) * exp((double)(-theta))));
-			bandv[lane] = g2;
-			bandv[NB_BANDS + lane] = g;
-			bandv[2 * NB_BANDS + lane] = gfloor;
-		}
-		WSYNC();
-		float gain2[K];
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			const int bl = a.t.bleft[e0 + k], br = bl + 1;
-			auto psd = [&](const float *mel) -> float {
-				float t = mel[bl] * wl[k];
-				t += mel[br] * wr[k];
-				return t;
-			};
-			const float p = psd(bandv);
-			const float gain_bark = psd(bandv + NB_BANDS);
-			const float gfl = psd(bandv + 2 * NB_BANDS);
-			const float prior_ratio = prior[k] / (prior[k] + 1.f);
-			const float theta = prior_ratio * (1.f + post[k]);
-			const float MM = hypergeom_gain(theta);
-			float g = prior_ratio * MM;
-			if (g > 1.f) g = 1.f;
-			if (.333f * g > gain_bark) g = 3 * gain_bark;
-			float gain = g;
-			old_ps[k] = .2f * old_ps[k] + (.8f * (gain * gain)) * ps[k];
-			if (gain < gfl) gain = gfl;
-			const float tmp = p * sqrt_via_double(gain) + (1.0f - p) * sqrt_via_double(gfl);
-			gain2[k] = tmp * tmp;
-		}
-		const float g_last = rdlane(gain2[K - 1], 63); // gain2[F-1] scales the Nyquist term
-#pragma unroll
-		for (int k = 0; k < K; ++k) {
-			if (e0 + k == 0) {
-				ft[k].x = gain2[k] * ft[k].x;
-				ft[k].y = g_last * ft[k].y;
-			} else {
-				ft[k].x = gain2[k] * ft[k].x;
-				ft[k].y = gain2[k] * ft[k].y;
-			}
-		}
-		w_rfft_inverse<F>(L, a.t, ft);
-		{
-			float lo[K], hi[K];
-			load_vec<K>(w_time(L) + e0, lo);
-			load_vec<K>(w_time(L) + F + e0, hi);
-#pragma unroll
-			for (int k = 0; k < K; ++k) {
-				op[k] = word2int(ob[k] + lo[k] * w0[k]);
-				ob[k] = hi[k] * w1[k];
-			}
-		}
+		for (int k = 0; k < K; ++k) op[k] = (int16_t)out_f[k];
 		WSYNC();
 	}
-
-	bstore_vec<K>(rS, vb4, SL::ECHON * 4, en);
-	bstore_vec<K>(rS, vb4, SL::INBUF * 4, inb);
-	bstore_vec<K>(rS, vb4, SL::S_ * 4, S);
-	bstore_vec<K>(rS, vb4, SL::SMIN * 4, Smin);
-	bstore_vec<K>(rS, vb4, SL::STMP * 4, Stmp);
-	bstore_vec<K>(rS, vb4, SL::NOISE * 4, noise);
-	bstore_vec<K>(rS, vb4, SL::OLDPS * 4, old_ps);
-	bstore_vec<K>(rS, vb4, SL::ZETA * 4, zeta);
-	bstore_vec<K>(rS, vb4, SL::OUTBUF * 4, ob);
+	pf_store<WP>(rS, vb4, pf);
 	if (lane < NB_BANDS) {
-		sm[SL::OLDPS_B + lane] = old_ps_b;
-		sm[SL::ZETA_B + lane] = zeta_b;
+		sm[SL::OLDPS_B + lane] = pf.old_ps_b[0];
+		sm[SL::ZETA_B + lane] = pf.zeta_b[0];
 	}
 
 	sc.fg_pending = pendingFG ? 1 : 0, sc.bg_pending = pendingBG ? 1 : 0;

@@ -30,6 +30,7 @@ def test_tick_kernel_registers_and_lds(build):
     assert len(big) == 3, [n for n, _ in big]
     for name, u in big:
         assert int(u["VGPRs"]) <= 256 and int(u["VGPRs Spill"]) == 0, (name, u)
+        assert int(u["ScratchSize [bytes/lane]"]) == 0, (name, u)  # (a scalar spilled to memory shows here alone, not as a VGPR spill)
         assert int(u["Occupancy [waves/SIMD]"]) == 2, (name, u)
         assert int(u["LDS Size [bytes/block]"]) <= 20480, (name, u)  # one wave per block: 8 per CU
     for k in ("aec_tick_kernelILi128E", "aec_tick_kernelILi64E"):
