@@ -60,10 +60,25 @@
  * (tests/test_gpu_bridge_rational.py).  Rows, MSVolume, absent legs and pins without MI_MIX_OUTPUT as with
  * mi_bridge_create_endpoints; cfg.plc as with mi_bridge_create_concealed.
  *
+ * Every pair of the VoIP rates 8 - 48 kHz (mi_bridge_create_ratios): the codecs mediastreamer2 plumbs into conferences run
+ * at 8, 12, 16, 24, 32 and 48 kHz, and on that grid 8 : 32 and 12 : 48 (ratio 4), 12 : 16 and 24 : 32 (3/4 and 4/3) and
+ * 12 : 32 (3/8 and 8/3) were left.  The constructor takes mi_bridge_create_rational's arguments and rules, and a leg may also
+ * be at 4 or 1/4 of the mix -- the ratio-4 tile kernels of the resampler, bit for bit mi_resampler_process_masked where that
+ * runs them: ticks of at most 576 samples on the wider side -- or stand a : b to it, leg rate : conference rate in lowest
+ * terms, wherever both its resamplers have a direct table of at most 128 taps by the resampler's own design rule: a, b <= 8
+ * and a ratio of at most 8/3 -- 4 : 3, 5 : 4, 5 : 3, 5 : 2, 6 : 5, 7 : 3 ... 8 : 3 and their inverses.  Such a leg runs the
+ * resampler's generic-order arithmetic (one fused multiply-add chain per output over the taps of its polyphase row) inside
+ * the tick, bit for bit mi_resampler_process_masked at every shape.  All of it shares one conference and one launch per tick
+ * with the older forms (bridge_ratios_kernel, csrc/bridge_ratios.hip, run only by a bridge with such a leg;
+ * tests/test_gpu_bridge_ratios.py).  Rows, MSVolume, absent legs and pins without MI_MIX_OUTPUT as with
+ * mi_bridge_create_endpoints; cfg.plc as with mi_bridge_create_concealed.
+ *
  * Out of scope, on purpose:
- *   - ratios that are no whole number other than 3/2 and 2/3 (44.1 kHz; 4/3: 32 kHz in 24 kHz) and whole ratios other than
- *     2, 3 and 6 (4: 32 kHz in 8 kHz), in either direction: refused with MI_ENOTSUP -- mi_session and the MSFilter plugin
- *     resample those; 3/2 and 2/3 through the five older constructors, which keep refusing them;
+ *   - rates off the 800 Hz grid (44.1 kHz: its tick is not whole groups of eight samples); whole ratios other than 2, 3, 4
+ *     and 6 (5, 7, 8 and up: a down-sampler of 240 taps or more); a : b with a or b above 8 or a ratio above 8/3 (7 : 2,
+ *     9 : 8: an interpolated table or more than 128 taps), in either direction: refused with MI_ENOTSUP -- mi_session and the
+ *     MSFilter plugin resample those; 3/2 and 2/3 through the five oldest constructors and 4, 1/4 and a : b through the six
+ *     older ones, which keep refusing them;
  *   - jitter buffering and flow control: the host's, as with mi_session -- a leg whose packet is missing at the tick is
  *     flagged absent (or concealed, cfg.plc);
  *   - cfg.plc with legs that differ in rate or codec through the four older constructors: they keep refusing it with
@@ -146,6 +161,20 @@ int mi_bridge_create_concealed(mi_ctx *ctx, const mi_bridge_config *cfg, const m
  * do not fit the 64 KB of LDS the kernel allows itself (32 kHz legs in a 48 kHz conference: up to 43 members; 24 kHz legs in
  * a 16 kHz room that also holds 48 kHz members: up to 45). */
 int mi_bridge_create_rational(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */, mi_bridge **out);
+/* The same with legs at 4 or 1/4 of the mix's rate and at a : b of it as well.  The arguments and every rule are
+ * mi_bridge_create_rational's.  Write a : b for leg rate : cfg->rate in lowest terms (both rates multiples of 800, as ever): a
+ * leg may also have a : b == 4 : 1 or 1 : 4, or any a : b that is no whole ratio with a <= 8, b <= 8 and
+ * max(a, b) / min(a, b) <= 8/3 -- where the resampler's design rule gives both directions a direct polyphase table of at most
+ * 128 taps.  h_legs == NULL, or no such leg: mi_bridge_create_rational's bridge exactly, the same kernels, pitch and tick
+ * bytes.  With such a leg the host rows are byte rows whether the codecs differ or not, and mi_bridge_reset_streams and
+ * mi_bridge_add_member zero both its resamplers' histories: 191 and 47 samples at ratio 4; at a : b the 47 of the one that
+ * goes up and the filter length - 1 (up to 127 at 8 : 3) of the one that goes down, on whichever side of the pin each sits.
+ * MI_ENOTSUP, the message naming the leg, both rates and the ratio, before anything is allocated: what
+ * mi_bridge_create_rational refuses but for these ratios; a rate off the 800 Hz grid (44.1 kHz); whole ratios 5, 7, 8 and up;
+ * a : b beyond the rule (7 : 2, 9 : 8); a conference whose rows, sum row and resampler scratch do not fit the 64 KB of LDS the
+ * kernel allows itself (12 kHz legs in a 16 kHz room that also holds 48 kHz members: up to 45 members; 32 kHz legs in a
+ * 24 kHz conference need 42 640 bytes at the mixer's own limit of 50 members, so there the limit is the mixer's). */
+int mi_bridge_create_ratios(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */, mi_bridge **out);
 void mi_bridge_destroy(mi_bridge *b);
 int mi_bridge_leg_rate(const mi_bridge *b, int stream); /* the leg's rate in Hz, or MI_EINVAL */
 /* the leg's codecs and its own tick in bytes (rate / 100 x 1 or 2), on any bridge; either pointer may be NULL.

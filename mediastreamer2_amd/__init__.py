@@ -886,7 +886,7 @@ class Bridge(_ConferenceBatch):
     _destroy, _prefix = "mi_bridge_destroy", "bridge"
 
     def __init__(self, ctx, nstreams, members=32, rate=8000, in_codec=MI_SESSION_PCMU, out_codec=MI_SESSION_PCMU, plc=False, device=0,
-                 leg_rates=None, legs=None, endpoints=None, concealed=None, rational=None):
+                 leg_rates=None, legs=None, endpoints=None, concealed=None, rational=None, ratios=None):
         """leg_rates: the rate of every leg's code words or PCM [nstreams] (mi_bridge_create_rated: rate / leg rate in
         {1, 2, 3, 6}); None: every leg at `rate`.
         legs: every leg's (rate, in_codec, out_codec) [nstreams], a sequence of triples or a structured array with those
@@ -897,7 +897,10 @@ class Bridge(_ConferenceBatch):
         concealed: the same triples for mi_bridge_create_concealed: endpoints= whose plc=True holds for legs of any rate and
         codec (a concealer per leg behind its own decoder); plc is passed as given, geometry and views are endpoints='.
         rational: the same triples for mi_bridge_create_rational: concealed= where a leg may also be at 3/2 or 2/3 of `rate`
-        (a 32 kHz member of a 48 kHz conference, a 24 kHz member of a 16 kHz one); geometry and views are endpoints='."""
+        (a 32 kHz member of a 48 kHz conference, a 24 kHz member of a 16 kHz one); geometry and views are endpoints='.
+        ratios: the same triples for mi_bridge_create_ratios: rational= where a leg may also be at 4 or 1/4 of `rate`, or
+        stand a : b to it with a, b <= 8 and a ratio of at most 8/3 (a 32 kHz member of an 8, 12 or 24 kHz conference, a
+        12 kHz member of a 16 kHz one); geometry and views are endpoints='."""
         self._own_ctx = ctx is None
         self.ctx = ctx = Context(device) if ctx is None else ctx
         cfg = BridgeConfig()
@@ -906,10 +909,10 @@ class Bridge(_ConferenceBatch):
         cfg.in_codec, cfg.out_codec, cfg.plc = in_codec, out_codec, int(plc)
         h = C.c_void_p()
         by_leg = {"mi_bridge_create_legs": legs, "mi_bridge_create_endpoints": endpoints, "mi_bridge_create_concealed": concealed,
-                  "mi_bridge_create_rational": rational}
+                  "mi_bridge_create_rational": rational, "mi_bridge_create_ratios": ratios}
         given = [(getattr(ctx.L, entry), v) for entry, v in by_leg.items() if v is not None]
         if given:
-            assert len(given) == 1, "one of legs=, endpoints=, concealed= and rational="
+            assert len(given) == 1, "one of legs=, endpoints=, concealed=, rational= and ratios="
             create, lg = given[0][0], np.asarray(given[0][1])
             if lg.dtype.names:
                 lg = np.stack([lg[k] for k in ("rate", "in_codec", "out_codec")], axis=-1)

@@ -67,6 +67,7 @@ BRIDGE_EXPORTS = [
     "mi_bridge_create_endpoints",
     "mi_bridge_create_concealed",
     "mi_bridge_create_rational",
+    "mi_bridge_create_ratios",
 ]
 
 
@@ -278,6 +279,7 @@ def load():
     L.mi_bridge_create_endpoints.argtypes = [vp, vp, vp, pp]
     L.mi_bridge_create_concealed.argtypes = [vp, vp, vp, pp]
     L.mi_bridge_create_rational.argtypes = [vp, vp, vp, pp]
+    L.mi_bridge_create_ratios.argtypes = [vp, vp, vp, pp]
     L.mi_bridge_leg_codec.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.mi_bridge_leg_bytes.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.mi_bridge_set_volume_params.argtypes = [vp, i32, i32, C.POINTER(VolumeParams)]

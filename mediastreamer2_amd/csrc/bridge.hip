@@ -30,7 +30,8 @@
 // are data: one conference holds 8, 16 and 48 kHz legs, A-law and mu-law trunks and PCM members side by side.  The rows in
 // LDS are as wide as the widest leg's tick; a narrower leg's tick sits at the head of its row until its up-sampler has run.
 // The five kernels below differ in which forms they are built for, so that a bridge pays only for what its legs need:
-// compile-time codecs or per-leg ones, no resamplers, those of legs below the mix, above it, at 3/2 and 2/3 of it.
+// compile-time codecs or per-leg ones, no resamplers, those of legs below the mix, above it, at 3/2 and 2/3 of it.  A sixth,
+// for legs at 4, 1/4 and a : b of the mix (mi_bridge_create_ratios), is a unit of its own: bridge_ratios.hip.
 //
 // Geometry: an 8 kHz conference of 32 is 5.4 KB of LDS and four waves, so eight such workgroups share a CU (32 waves);
 // 1000 conferences are 1000 workgroups dealt over the 256 CUs, about four per CU = one wave per SIMD and conference
@@ -43,6 +44,9 @@
 #include "bridge_phases.hpp"
 
 #pragma clang fp contract(off)
+
+// bridge_ratios.hip: bridge_ratios_kernel on `nconf` workgroups; args: a RatiosArgs, as bytes
+int mi_bridge_ratios_launch(const void *args, size_t bytes, int nconf, size_t lds, hipStream_t stream);
 
 namespace {
 
@@ -288,7 +292,7 @@ __global__ __launch_bounds__(BT) void bridge_rational_kernel(RationalArgs qa) {
 struct mi_bridge {
 	mi_ctx *ctx = nullptr;
 	Plan plan;              // what creation decided: geometry, family, the legs' rates, codecs and ratio bytes
-	RationalArgs args = {}; // the widest kernel's arguments, filled at creation (fill_args, build_tables) but for in, present, out
+	RatiosArgs args = {};   // the widest kernel's arguments, filled at creation (fill_args, build_tables) but for in, present, out
 	mi_volume *vol = nullptr; // the meters: parameters, state, one-second windows
 	mi_mixer *mix = nullptr;  // the pins' controls
 	mi_plc *plc = nullptr;    // plan.leg_plc: mi_plc_create_legs', with the decoders; else mi_plc_create's at the legs' one rate
@@ -302,6 +306,7 @@ struct mi_bridge {
 	uint8_t *d_ratio = nullptr;
 	int16_t *d_hist_in = nullptr, *d_hist_out = nullptr;
 	float *d_tab = nullptr;
+	int2 *d_gen = nullptr; // plan.generic: RatiosArgs::gen_tab
 	uint8_t *d_codec = nullptr; // the codecs as data ([n]; [2][n] with plc: the second row names PCM in, behind the concealer)
 };
 
@@ -318,7 +323,7 @@ void (*const RATED_KERNELS[3][3])(RatedArgs) = CODEC_TABLE(bridge_rated_kernel);
 // mi_volume_create / mi_mixer_create allocate and only their destroy frees; no setter reallocates them.
 void fill_args(mi_bridge *b) {
 	const Plan &pl = b->plan;
-	LegsArgs &la = b->args.u.l;
+	LegsArgs &la = b->args.q.u.l;
 	RatedArgs &ra = la.r;
 	BridgeArgs &a = ra.b;
 	VolumeView vv;
@@ -334,14 +339,16 @@ void fill_args(mi_bridge *b) {
 		la.codec = b->plc ? b->d_codec + pl.n : b->d_codec;
 		la.in_pitch = b->plc ? pl.pitch * 2 : (int)pl.in_bytes, la.out_pitch = (int)pl.out_bytes;
 	}
-	b->args.u.wide = pl.wide, b->args.u.hin_stride = pl.hin_stride;
+	b->args.q.u.wide = pl.wide, b->args.q.u.hin_stride = pl.hin_stride;
+	b->args.gen_tab = b->d_gen;
 }
 
 int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's stream
 	const Plan &pl = b->plan;
 	const mi_bridge_config &cf = pl.cfg;
 	int rc, in_kind = cf.in_codec;
-	RationalArgs qa = b->args; // each kernel is passed the part that is its own
+	RatiosArgs ga = b->args; // each kernel is passed the part that is its own
+	RationalArgs &qa = ga.q;
 	BridgeArgs &a = qa.u.l.r.b;
 	a.in = b->d_in[slot], a.present = b->d_present[slot], a.out = b->d_out[slot];
 	if (pl.leg_plc) { // every leg's decoder and MSGenericPLC in the concealer's three launches: byte rows in, PCM rows out
@@ -360,6 +367,7 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 	}
 	auto launch = [&](auto kernel, const auto &args) { hipLaunchKernelGGL(kernel, dim3((unsigned)pl.nconf), dim3(BT), pl.lds, b->ctx->stream, args); };
 	switch (pl.family) {
+	case Plan::RATIOS: return mi_bridge_ratios_launch(&ga, sizeof(ga), pl.nconf, pl.lds, b->ctx->stream);
 	case Plan::RATIONAL: launch(bridge_rational_kernel, qa); break;
 	case Plan::UPDOWN: launch(bridge_updown_kernel, qa.u); break;
 	case Plan::LEGS_RATED: launch(bridge_legs_kernel<true>, qa.u.l); break;
@@ -383,37 +391,42 @@ int reset_resamplers(mi_bridge *b, int first, int count) {
 }
 
 // the polyphase table of mi_resampler's own design code (quality 3, what msresample.c uses) for in_rate -> out_rate
-int design_table(mi_ctx *ctx, int in_rate, int out_rate, std::vector<float> &table) {
+// filt_len, direct: mi_resampler_info's verdict on that design
+int design_table(mi_ctx *ctx, int in_rate, int out_rate, std::vector<float> &table, int *filt_len = nullptr, int *direct = nullptr) {
 	mi_resampler *r = nullptr;
 	int rc = mi_resampler_create(ctx, 1, (uint32_t)in_rate, (uint32_t)out_rate, 3, &r);
 	if (rc != MI_OK) return rc;
 	table.resize((size_t)mi_resampler_get_table(r, nullptr, 0));
 	mi_resampler_get_table(r, table.data(), (int)table.size());
+	rc = mi_resampler_info(r, filt_len, nullptr, nullptr, direct);
 	mi_resampler_destroy(r);
-	return MI_OK;
+	return rc;
 }
 
 // one table per distinct ratio and direction, built once and back to back in d_tab, its float offset noted in b->args.  A table
 // is designed as [L][taps] polyphase rows for in_rate : out_rate = M : L and laid out as its reader wants it: AS_DESIGNED, an
 // up-sampler by r: [r][48]; PHASE_MAJOR, a down-sampler by r: tap r * i + p at [p][i]; REARRANGED, x 3/2 and x 2/3: [L][24 * M]
 // into the rows rational_run's lanes read, [r * M + p'][k] = table[(r * M) % L][k * M + p'].  size: the floats mi_resampler
-// designs; anything else is a design this unit was not written for
+// designs; anything else is a design this unit was not written for.  A leg at a : b (generic_run) reads both its tables
+// AS_DESIGNED, [L][filt_len]: filt_len is the plan's (filter_rule), and mi_resampler_info must agree with it and call the table
+// direct -- the plan accepted the leg on that rule alone
 enum Layout { AS_DESIGNED, PHASE_MAJOR, REARRANGED };
-struct Table { int in_rate, out_rate; size_t size; Layout layout; int *offset; };
+struct Table { int in_rate, out_rate; size_t size; Layout layout; int *offset; int filt_len = 0; };
 
 int build_tables(mi_bridge *b) {
 	const Plan &pl = b->plan;
-	UpdownArgs &ua = b->args.u;
+	UpdownArgs &ua = b->args.q.u;
+	RationalArgs &qa = b->args.q;
 	RatedArgs &ra = ua.l.r;
 	const int conf = pl.cfg.rate;
 	std::vector<Table> want;
 	if (pl.r32_above) { // the in_resampler's, then the out_resampler's
-		want.push_back({conf / 2 * 3, conf, 6 * RQ_FT, REARRANGED, &b->args.tab_above_in});
-		want.push_back({conf, conf / 2 * 3, 6 * RQ_FT, REARRANGED, &b->args.tab_above_out});
+		want.push_back({conf / 2 * 3, conf, 6 * RQ_FT, REARRANGED, &qa.tab_above_in});
+		want.push_back({conf, conf / 2 * 3, 6 * RQ_FT, REARRANGED, &qa.tab_above_out});
 	}
 	if (pl.r32_below) {
-		want.push_back({conf / 3 * 2, conf, 6 * RQ_FT, REARRANGED, &b->args.tab_below_in});
-		want.push_back({conf, conf / 3 * 2, 6 * RQ_FT, REARRANGED, &b->args.tab_below_out});
+		want.push_back({conf / 3 * 2, conf, 6 * RQ_FT, REARRANGED, &qa.tab_below_in});
+		want.push_back({conf, conf / 3 * 2, 6 * RQ_FT, REARRANGED, &qa.tab_below_out});
 	}
 	for (int r = 2; r < 7; ++r) {
 		const size_t size = (size_t)r * RS_FILT;
@@ -426,10 +439,23 @@ int build_tables(mi_bridge *b) {
 			want.push_back({conf, conf / r, size, PHASE_MAJOR, &ra.tab_down[r]});
 		}
 	}
+	std::vector<int2> gen(64, make_int2(0, 0));
+	for (const uint8_t rb : pl.generic) { // conf = cb * unit, the leg's rate la * unit
+		const int la = gen_a(rb), cb = gen_b(rb), unit = conf / cb, fin = filter_rule(la, cb).filt_len, fout = filter_rule(cb, la).filt_len;
+		want.push_back({la * unit, conf, (size_t)cb * fin, AS_DESIGNED, &gen[(size_t)gen_code(rb)].x, fin});
+		want.push_back({conf, la * unit, (size_t)la * fout, AS_DESIGNED, &gen[(size_t)gen_code(rb)].y, fout});
+	}
 	std::vector<float> all, t;
 	for (const Table &w : want) {
-		const int rc = design_table(b->ctx, w.in_rate, w.out_rate, t);
+		int filt_len = 0, direct = 0;
+		const int rc = design_table(b->ctx, w.in_rate, w.out_rate, t, &filt_len, &direct);
 		if (rc != MI_OK) return rc;
+		if (w.filt_len && (filt_len != w.filt_len || !direct)) {
+			mi::set_error("mi_bridge: the plan's filter for %d -> %d Hz (%d taps, direct) is not mi_resampler's (%d taps, %s): "
+			              "filter_rule (bridge_plan.hpp) and design_filter (resample.hip) disagree",
+			              w.in_rate, w.out_rate, w.filt_len, filt_len, direct ? "direct" : "interpolated");
+			return MI_ENOTSUP;
+		}
 		if (t.size() != w.size) return MI_ENOTSUP;
 		*w.offset = (int)all.size();
 		const int g = std::min(w.in_rate, w.out_rate) / (w.layout == REARRANGED ? 2 : 1); // the rates are M * g and L * g
@@ -445,6 +471,9 @@ int build_tables(mi_bridge *b) {
 	}
 	if (!(b->d_tab = (float *)mi_dev_alloc(b->ctx, all.size() * sizeof(float)))) return MI_ENOMEM;
 	MI_HIP(hipMemcpy(b->d_tab, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
+	if (pl.generic.empty()) return MI_OK;
+	if (!(b->d_gen = (int2 *)mi_dev_alloc(b->ctx, gen.size() * sizeof(int2)))) return MI_ENOMEM;
+	MI_HIP(hipMemcpy(b->d_gen, gen.data(), gen.size() * sizeof(int2), hipMemcpyHostToDevice));
 	return MI_OK;
 }
 
@@ -472,7 +501,7 @@ void mi_bridge_destroy(mi_bridge *b) {
 		for (uint8_t *p : {b->d_in[i], b->d_present[i], b->d_ev[i], b->d_out[i]})
 			if (p) mi_dev_free(c, p);
 	}
-	void *const rest[] = {b->d_ratio, b->d_hist_in, b->d_hist_out, b->d_tab, b->d_codec, b->d_pcm, b->d_evlen};
+	void *const rest[] = {b->d_ratio, b->d_hist_in, b->d_hist_out, b->d_tab, b->d_gen, b->d_codec, b->d_pcm, b->d_evlen};
 	for (void *p : rest)
 		if (p) mi_dev_free(c, p);
 	if (b->plc) mi_plc_destroy(b->plc);
@@ -572,6 +601,9 @@ int mi_bridge_create_concealed(mi_ctx *ctx, const mi_bridge_config *cfg, const m
 }
 int mi_bridge_create_rational(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
 	return create(RULES_RATIONAL, ctx, cfg, nullptr, h_legs, out);
+}
+int mi_bridge_create_ratios(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
+	return create(RULES_RATIOS, ctx, cfg, nullptr, h_legs, out);
 }
 
 int mi_bridge_leg_codec(const mi_bridge *b, int stream, int *in_codec, int *out_codec) {

@@ -1,6 +1,6 @@
 // bridge_phases.hpp -- the phases of a conference tick (the head of bridge.hip describes them), each written ONCE as a
-// __device__ __forceinline__ function; bridge.hip's five kernels are compositions of them with the barriers in between
-// (bridge_tick_kernel keeps three of them written out, for its pinned register figures: see its head).
+// __device__ __forceinline__ function; bridge.hip's five kernels and bridge_ratios.hip's one are compositions of them with
+// the barriers in between (bridge_tick_kernel keeps three of them written out, for its pinned register figures: see its head).
 // What differs between the kernels is a template parameter or data here:
 //   FORMS  which resamplers a kernel has (Forms below), and with it how a member's ratio byte is read (leg_span);
 //   SRC    where (A) takes a group from: FixedSrc<IN>, one compile-time codec on rows of samples, or LegSrc, every leg's own
@@ -75,12 +75,20 @@ struct RationalArgs {
 	int tab_above_in, tab_above_out, tab_below_in, tab_below_out;
 };
 
+struct RatiosArgs {
+	RationalArgs q;
+	// [64] by gen_code of a leg's ratio byte: the float offsets in `tab` of its in_resampler's table (leg -> conference, b rows)
+	// and its out_resampler's (conference -> leg, a rows), polyphase rows as mi_resampler designs them
+	const int2 *gen_tab;
+};
+
 // ---- a member's ratio byte (bridge_plan.hpp writes it).  A kernel meets only the forms it was built for:
 enum Forms {
 	F_SAME,  // every leg at the conference's rate: no ratio byte, no resampler
 	F_BELOW, // legs at or below the mix
 	F_ABOVE, // and above it
 	F_R32,   // and at 3/2 or 2/3 of it
+	F_GEN,   // and at a : b of it in the generic order (UD_GEN); at 4 and 1/4 through the forms above
 };
 
 // The one place where a ratio byte becomes a length or a rate: the leg's share of `conf` -- groups, words or samples of the
@@ -88,6 +96,7 @@ enum Forms {
 template <int FORMS>
 __device__ __forceinline__ int leg_span(int r, int conf) {
 	if (FORMS == F_SAME) return conf;
+	if (FORMS >= F_GEN && (r & UD_GEN)) return conf / gen_b(r) * gen_a(r);
 	if (FORMS >= F_R32 && (r & UD_R32)) return (r & UD_ABOVE) ? conf / 2 * 3 : conf / 3 * 2;
 	if (FORMS >= F_ABOVE && (r & UD_ABOVE)) return conf * (r & 7);
 	return conf / r;
@@ -569,6 +578,38 @@ __device__ __forceinline__ void rational_run(float *xp, int16_t *row, int16_t *h
 	wave_sync(); // xp is read out before the wave's next member stages over it
 }
 
+// One member's resampler at num : den (in : out, lowest terms) in mi_resampler's GENERIC order: resample_generic_kernel's
+// arithmetic (resample.hip) with a direct table.  History ++ tick staged as floats; output k is ONE __builtin_fmaf chain from
+// 0.f over taps j = 0 .. filt - 1 of table row (k * num) % den against x[(k * num) / den + j], then rs_word2int; the last
+// filt - 1 samples of history ++ tick are the new history (a tick shorter than the history keeps part of the old one).  A
+// tick is whole periods of `num` samples, so mi_resampler's position state is (0, 0) at every tick's start and the bridge
+// keeps none.  The in_len samples at the head of `row` are the input, the in_len / num * den outputs go back over the row
+// once the whole tick is staged, as rational_run's.  The taps are read from LDS: the `den` rows of the table, staged per
+// member behind x at a pitch of filt + 1 floats (lanes of different phases would meet on one bank at a pitch of 48 .. 128);
+// generic_scratch (bridge_plan.hpp) budgets both.  x reads run at a stride of num / den floats across the lanes.
+__device__ __forceinline__ void generic_run(float *x, int16_t *row, int16_t *hist, const float *tab, int num, int den, int filt, int in_len,
+                                            int lane) {
+	const int hl = filt - 1, pitch = filt + 1, out_len = in_len / num * den;
+	float *taps = x + generic_xlen(filt, in_len);
+	for (int i = lane; i < hl; i += 64) x[i] = (float)hist[i];
+	for (int i = lane; i < in_len; i += 64) x[hl + i] = (float)row[i];
+	for (int i = lane; i < den * filt; i += 64) {
+		const int r = i / filt;
+		taps[r * pitch + (i - r * filt)] = tab[i];
+	}
+	wave_sync(); // the whole tick is staged before the first output lands on the row
+	for (int k = lane; k < out_len; k += 64) {
+		const int t = k * num, last = t / den, frac = t - last * den;
+		const float *sc = taps + frac * pitch, *ip = x + last;
+		float sum = 0.f;
+#pragma unroll 8
+		for (int j = 0; j < filt; ++j) sum = __builtin_fmaf(sc[j], ip[j], sum);
+		row[k] = rs_word2int(sum);
+	}
+	for (int i = lane; i < hl; i += 64) hist[i] = (int16_t)x[in_len + i];
+	wave_sync(); // x is read out before the wave's next member stages over it
+}
+
 // what an up-sampler behind a pin left on the member's row -- its out_resampler's `len` leg-rate samples -- through the leg's
 // store or encoder, 16 bytes of PCM or 8 code words per lane
 __device__ __forceinline__ void store_row(const int16_t *row, uint8_t *out, int kind, int len, int lane) {
@@ -596,16 +637,18 @@ __device__ __forceinline__ int wave_ratio(const Conf &k, int m) {
 // ---- (U) one wavefront per member, the four waves taking members in turn: the in_resampler of a present, plumbed leg (the
 // run mask present & linked of mi_resampler_process_masked; any other keeps its history), from the head of the row back over
 // it -- rated_up for a leg below the mix, resample_down for one above it, rational_run (x 3/2 below, x 2/3 above) for
-// UD_R32.  ua, qa: null in a kernel without those forms.
+// UD_R32, generic_run for UD_GEN (a loop of its own as well).  ua, qa, ga: null in a kernel without those forms.
 // The legs at 3/2 and 2/3 have a loop of their own, here and in (W): what a helper keeps per lane stays live over its own
 // loop only, and one loop over all forms is how a kernel goes past 128 VGPRs.
 template <int FORMS>
-__device__ __forceinline__ void resample_in(const Conf &k, const RatedArgs &ra, const UpdownArgs *ua, const RationalArgs *qa, float *scr) {
+__device__ __forceinline__ void resample_in(const Conf &k, const RatedArgs &ra, const UpdownArgs *ua, const RationalArgs *qa, float *scr,
+                                            const RatiosArgs *ga = nullptr) {
 	const int wave = k.t >> 6, lane = k.t & 63, ns = k.ns;
 	const int hin = FORMS >= F_ABOVE ? ua->hin_stride : RS_FILT;
 	for (int m = wave; m < k.mm; m += BT / 64) {
 		const int r = wave_ratio<FORMS>(k, m), n = FORMS >= F_ABOVE ? r & 7 : r;
-		if (r == 1 || (FORMS >= F_R32 && (r & UD_R32)) || !k.s_on[m] || !((unsigned)k.s_par[m].x & MI_MIX_LINKED)) continue;
+		if (r == 1 || (FORMS >= F_R32 && (r & UD_R32)) || (FORMS >= F_GEN && (r & UD_GEN)) || !k.s_on[m] || !((unsigned)k.s_par[m].x & MI_MIX_LINKED))
+			continue;
 		int16_t *row = reinterpret_cast<int16_t *>(k.rows + m * k.row_w), *hist = ra.hist_in + (size_t)(k.s0 + m) * hin;
 		if (FORMS >= F_ABOVE && (r & UD_ABOVE))
 			resample_down<ON_ROW>(scr, row, hist, ra.tab + ua->tab_down_in[n], n, ns * n, updown_plen(n, ns * n), lane, reinterpret_cast<uint8_t *>(row), 0);
@@ -614,23 +657,32 @@ __device__ __forceinline__ void resample_in(const Conf &k, const RatedArgs &ra, 
 	if (FORMS < F_R32) return;
 	for (int m = wave; m < k.mm; m += BT / 64) {
 		const int r = __builtin_amdgcn_readfirstlane(k.s_rt[m]);
-		if (!(r & UD_R32) || !k.s_on[m] || !((unsigned)k.s_par[m].x & MI_MIX_LINKED)) continue;
+		if (!(r & UD_R32) || (FORMS >= F_GEN && (r & UD_GEN)) || !k.s_on[m] || !((unsigned)k.s_par[m].x & MI_MIX_LINKED)) continue;
 		int16_t *row = reinterpret_cast<int16_t *>(k.rows + m * k.row_w), *hist = ra.hist_in + (size_t)(k.s0 + m) * hin;
 		if (r & UD_ABOVE) rational_run<2, 3>(scr, row, hist, ra.tab + qa->tab_above_in, ns / 2 * 3, lane);
 		else rational_run<3, 2>(scr, row, hist, ra.tab + qa->tab_below_in, ns / 3 * 2, lane);
+	}
+	if (FORMS < F_GEN) return;
+	for (int m = wave; m < k.mm; m += BT / 64) { // (a : b: leg -> conference is a : b, in : out)
+		const int r = __builtin_amdgcn_readfirstlane(k.s_rt[m]);
+		if (!(r & UD_GEN) || !k.s_on[m] || !((unsigned)k.s_par[m].x & MI_MIX_LINKED)) continue;
+		int16_t *row = reinterpret_cast<int16_t *>(k.rows + m * k.row_w), *hist = ra.hist_in + (size_t)(k.s0 + m) * hin;
+		const int la = gen_a(r), cb = gen_b(r);
+		generic_run(scr, row, hist, ra.tab + ga->gen_tab[gen_code(r)].x, la, cb, filter_rule(la, cb).filt_len, ns / cb * la, lane);
 	}
 }
 
 // ---- (W) one wavefront per member: the out_resampler of a pin with its output on, then the leg's store or encoder --
 // resample_down for a leg below the mix; for one above it rated_up, for UD_R32 rational_run the other way, from the head of
-// the row back over the row (which held the leg's input, so it is wide enough), then store_row.  OUT as in (D).
+// the row back over the row (which held the leg's input, so it is wide enough), for UD_GEN generic_run likewise, then
+// store_row.  OUT as in (D).
 template <int FORMS, int OUT>
 __device__ __forceinline__ void resample_out(const Conf &k, const RatedArgs &ra, const UpdownArgs *ua, const RationalArgs *qa, float *scr,
-                                             uint8_t *out, int pitch) {
+                                             uint8_t *out, int pitch, const RatiosArgs *ga = nullptr) {
 	const int wave = k.t >> 6, lane = k.t & 63, ns = k.ns;
 	for (int m = wave; m < k.mm; m += BT / 64) {
 		const int r = wave_ratio<FORMS>(k, m), n = FORMS >= F_ABOVE ? r & 7 : r;
-		if (r == 1 || (FORMS >= F_R32 && (r & UD_R32)) || !((unsigned)k.s_par[m].x & MI_MIX_OUTPUT)) continue;
+		if (r == 1 || (FORMS >= F_R32 && (r & UD_R32)) || (FORMS >= F_GEN && (r & UD_GEN)) || !((unsigned)k.s_par[m].x & MI_MIX_OUTPUT)) continue;
 		int16_t *row = reinterpret_cast<int16_t *>(k.rows + m * k.row_w), *hist = ra.hist_out + (size_t)(k.s0 + m) * ra.hout_stride;
 		const int kind = OUT == BY_KIND ? __builtin_amdgcn_readfirstlane(k.s_cd[m] >> 2) : OUT;
 		const size_t at = (size_t)(k.s0 + m) * pitch;
@@ -644,10 +696,19 @@ __device__ __forceinline__ void resample_out(const Conf &k, const RatedArgs &ra,
 	if (FORMS < F_R32) return;
 	for (int m = wave; m < k.mm; m += BT / 64) {
 		const int r = __builtin_amdgcn_readfirstlane(k.s_rt[m]);
-		if (!(r & UD_R32) || !((unsigned)k.s_par[m].x & MI_MIX_OUTPUT)) continue;
+		if (!(r & UD_R32) || (FORMS >= F_GEN && (r & UD_GEN)) || !((unsigned)k.s_par[m].x & MI_MIX_OUTPUT)) continue;
 		int16_t *row = reinterpret_cast<int16_t *>(k.rows + m * k.row_w), *hist = ra.hist_out + (size_t)(k.s0 + m) * ra.hout_stride;
 		if (r & UD_ABOVE) rational_run<3, 2>(scr, row, hist, ra.tab + qa->tab_above_out, ns, lane);
 		else rational_run<2, 3>(scr, row, hist, ra.tab + qa->tab_below_out, ns, lane);
+		store_row(row, out + (size_t)(k.s0 + m) * pitch, __builtin_amdgcn_readfirstlane(k.s_cd[m] >> 2), leg_span<FORMS>(r, ns), lane);
+	}
+	if (FORMS < F_GEN) return;
+	for (int m = wave; m < k.mm; m += BT / 64) { // (conference -> leg is b : a)
+		const int r = __builtin_amdgcn_readfirstlane(k.s_rt[m]);
+		if (!(r & UD_GEN) || !((unsigned)k.s_par[m].x & MI_MIX_OUTPUT)) continue;
+		int16_t *row = reinterpret_cast<int16_t *>(k.rows + m * k.row_w), *hist = ra.hist_out + (size_t)(k.s0 + m) * ra.hout_stride;
+		const int la = gen_a(r), cb = gen_b(r);
+		generic_run(scr, row, hist, ra.tab + ga->gen_tab[gen_code(r)].y, cb, la, filter_rule(cb, la).filt_len, ns, lane);
 		store_row(row, out + (size_t)(k.s0 + m) * pitch, __builtin_amdgcn_readfirstlane(k.s_cd[m] >> 2), leg_span<FORMS>(r, ns), lane);
 	}
 }

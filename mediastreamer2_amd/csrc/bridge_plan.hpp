@@ -41,11 +41,39 @@ MI_PLAN_HD inline int rational_plen(int m, int in_len) { return (((RQ_FT * m - 1
 // bytes of a wavefront's scratch for it: two copies of M phase arrays
 MI_PLAN_HD inline size_t rational_scratch(int m, int in_len) { return (size_t)2 * m * rational_plen(m, in_len) * sizeof(float); }
 
-// ---- a member's ratio byte.  Conference rate / leg rate (1, 2, 3 or 6) for a leg at or below the mix; with UD_ABOVE the
-// leg is above it and the low three bits are leg rate / conference rate; with UD_R32 the ratio is 3/2 (the whole part: 1),
-// UD_ABOVE still giving the direction.  The kernels read it through leg_span (bridge_phases.hpp).
-constexpr unsigned UD_ABOVE = 0x80, UD_R32 = 0x40;
+// of a resampler in mi_resampler's generic order (generic_run, bridge_phases.hpp): history ++ tick as floats, then the `den`
+// polyphase rows of `filt` taps at a pitch of filt + 1 floats -- the filters are 48 .. 128 taps, multiples of 8, and rows at
+// that pitch would all start on one LDS bank
+MI_PLAN_HD inline int generic_xlen(int filt, int in_len) { return (filt - 1 + in_len + 3) & ~3; }
+MI_PLAN_HD inline size_t generic_scratch(int filt, int den, int in_len) {
+	return ((size_t)generic_xlen(filt, in_len) + (size_t)den * (filt + 1)) * sizeof(float);
+}
+
+// design_filter's rule (resample.hip) at quality 3 for in : out = num : den in lowest terms: 48 taps, stretched by num / den
+// and rounded up to eight where the resampler goes down, the table's oversampling halved past every power of two of that
+// ratio; the table is direct -- den rows of filt_len taps -- where filt_len * den <= filt_len * oversample + 8
+struct FilterRule { int filt_len; bool direct; };
+MI_PLAN_HD inline FilterRule filter_rule(int num, int den) {
+	int len = RS_FILT, over = 8;
+	if (num > den) len = ((RS_FILT * num / den - 1) & ~7) + 8;
+	for (int k = 2; k <= 16 && num > den; k *= 2) over = k * den < num ? over >> 1 : over;
+	return {len, len * den <= len * (over < 1 ? 1 : over) + 8};
+}
+constexpr int GENERIC_MAX_FILT = 128, GENERIC_MAX_TERM = 8; // the longest filter generic_run takes; a and b of a : b in the byte
+
+// ---- a member's ratio byte.  Conference rate / leg rate (1, 2, 3 or 6; 4 under mi_bridge_create_ratios) for a leg at or
+// below the mix; with UD_ABOVE the leg is above it and the low three bits are leg rate / conference rate; with UD_R32 the
+// ratio is 3/2 (the whole part: 1), UD_ABOVE still giving the direction.  With UD_GEN the leg stands a : b to the mix, any
+// other non-whole ratio of mi_bridge_create_ratios: a - 1 in bits 0-2, b - 1 in bits 3, 4 and 6, UD_ABOVE where a > b.  The
+// kernels read it through leg_span (bridge_phases.hpp).
+constexpr unsigned UD_ABOVE = 0x80, UD_R32 = 0x40, UD_GEN = 0x20;
 constexpr int NO_WHOLE_RATIO = -1, RATIO_NOT_SERVED = -2;
+MI_PLAN_HD inline int gen_a(int rb) { return (rb & 7) + 1; }
+MI_PLAN_HD inline int gen_b(int rb) { return ((rb >> 3) & 3) + ((rb >> 4) & 4) + 1; }
+MI_PLAN_HD inline int gen_code(int rb) { return (gen_a(rb) - 1) | (gen_b(rb) - 1) << 3; } // 0 .. 63: the index of its tables
+inline int gen_byte(int a, int b) {
+	return (int)(UD_GEN | (a > b ? UD_ABOVE : 0u) | (unsigned)(a - 1) | ((unsigned)(b - 1) & 3u) << 3 | ((unsigned)(b - 1) & 4u) << 4);
+}
 
 // The one place where two rates become a ratio byte, or one of the two reasons why there is none.  3/2 or 2/3, both rates
 // multiples of 800: leg and mix are 2400 k and 1600 k Hz, their ticks 24 k and 16 k samples -- 8 k periods of 3 samples against
@@ -66,23 +94,28 @@ struct Rules {
 	const char *fn, *rates_fn;
 	// above: a leg may be above the mix (and brings the codecs as data and byte rows); leg_plc: cfg->plc with legs that differ in
 	// rate or codec is served by the per-leg concealer, not refused; rational: a leg may be at 3/2 or 2/3 of the mix
-	bool above, leg_plc, rational;
+	// ratios: a leg may be at 4 or 1/4 of the mix, or stand a : b to it wherever both its resamplers have a direct table of at
+	// most 128 taps
+	bool above, leg_plc, rational, ratios;
 };
 constexpr Rules RULES_RATED = {"mi_bridge_create_rated", "mi_bridge_create_rated", false, false, false};
 constexpr Rules RULES_LEGS = {"mi_bridge_create_legs", "mi_bridge_create_rated", false, false, false};
 constexpr Rules RULES_ENDPOINTS = {"mi_bridge_create_endpoints", "mi_bridge_create_endpoints", true, false, false};
 constexpr Rules RULES_CONCEALED = {"mi_bridge_create_concealed", "mi_bridge_create_endpoints", true, true, false};
 constexpr Rules RULES_RATIONAL = {"mi_bridge_create_rational", "mi_bridge_create_rational", true, true, true};
+constexpr Rules RULES_RATIOS = {"mi_bridge_create_ratios", "mi_bridge_create_ratios", true, true, true, true};
 
 struct Plan {
 	// which kernel a tick launches, chosen once: compile-time codecs without and with resamplers, per-leg codecs without and
-	// with them, a leg above the mix, a leg at 3/2 or 2/3 of it
-	enum Family { TICK, RATED, LEGS, LEGS_RATED, UPDOWN, RATIONAL } family = TICK;
+	// with them, a leg above the mix, a leg at 3/2 or 2/3 of it, a leg at 4, 1/4 or a : b
+	enum Family { TICK, RATED, LEGS, LEGS_RATED, UPDOWN, RATIONAL, RATIOS } family = TICK;
 	mi_bridge_config cfg = {}; // in_codec, out_codec: leg 0's where the legs were given
 	int n = 0, nconf = 0, mm = 0, len = 0;
 	// a leg not at the conference's rate (ratio bytes, resamplers, tables); one above the mix by a whole ratio; one at 3/2 or 2/3 of
 	// it; the concealer is the per-leg one, behind every leg's own decoder
 	bool rated = false, updown = false, rational = false, leg_plc = false;
+	bool ratios = false;          // a leg at 4 or 1/4 of the mix, or at a : b: only mi_bridge_create_ratios plans one
+	std::vector<uint8_t> generic; // the distinct UD_GEN ratio bytes of the legs: a pair of tables each (gen_code)
 	bool used[7] = {}, above[7] = {};         // the whole ratios of legs below the mix, and of legs above it
 	bool r32_above = false, r32_below = false; // a leg at 3/2 of the mix, a leg at 2/3
 	int max_ratio = 1, common = 0; // common: the first leg's rate, the one concealer batch's
@@ -130,6 +163,22 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 		const bool up = lr > cfg->rate;
 		int rb = ratio_byte(lr, cfg->rate);
 		if (rb >= 0 && (rb & UD_R32) && !rules.rational) rb = NO_WHOLE_RATIO;
+		bool added = false; // a form only mi_bridge_create_ratios plans
+		if (rules.ratios && rb == RATIO_NOT_SERVED && std::max(lr, cfg->rate) / std::min(lr, cfg->rate) == 4)
+			rb = (int)((up ? UD_ABOVE : 0u) | 4u), added = true;
+		if (rules.ratios && rb == NO_WHOLE_RATIO) {
+			int g = lr, h = cfg->rate;
+			while (h) { const int t = g % h; g = h, h = t; }
+			const int la = lr / g, cb = cfg->rate / g; // a : b
+			const FilterRule in = filter_rule(la, cb), out = filter_rule(cb, la);
+			if (la > GENERIC_MAX_TERM || cb > GENERIC_MAX_TERM || !in.direct || !out.direct || in.filt_len > GENERIC_MAX_FILT || out.filt_len > GENERIC_MAX_FILT)
+				MI_REFUSE("%s: leg %d at %d Hz in a %d Hz conference is %d : %d (%.3f), a ratio whose resamplers have no direct table "
+				          "of at most %d taps (%d taps%s one way, %d%s the other); supported: whole ratios 1, 2, 3, 4, 6 either way, and a : b "
+				          "with a, b <= %d and a ratio of at most 8/3",
+				          fn, s, lr, cfg->rate, la, cb, (double)std::max(la, cb) / std::min(la, cb), GENERIC_MAX_FILT, in.filt_len,
+				          in.direct ? "" : ", interpolated,", out.filt_len, out.direct ? "" : ", interpolated,", GENERIC_MAX_TERM);
+			rb = gen_byte(la, cb), added = true;
+		}
 		if (up && !rules.above)
 			MI_REFUSE("mi_bridge_create_rated: leg %d at %d Hz is above its conference's %d Hz (only legs at or below the mix are resampled)",
 			          s, lr, cfg->rate);
@@ -138,8 +187,8 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 			MI_REFUSE("%s: leg %d at %d Hz in a %d Hz conference is no whole ratio (%.3f); supported: 1, 2, 3, 6%s", fn, s, lr, cfg->rate,
 			          (double)hi / lo, rules.rational ? ", and 3/2 either way" : "");
 		if (rb == RATIO_NOT_SERVED)
-			MI_REFUSE("%s: leg %d at %d Hz in a %d Hz conference is ratio %d; supported: 1, 2, 3, 6%s", fn, s, lr, cfg->rate, hi / lo,
-			          rules.rational ? ", and 3/2 either way" : "");
+			MI_REFUSE("%s: leg %d at %d Hz in a %d Hz conference is ratio %d; supported: 1, 2, 3, %s6%s", fn, s, lr, cfg->rate, hi / lo,
+			          rules.ratios ? "4, " : "", rules.ratios ? ", and a : b with a, b <= 8 up to 8/3 either way" : rules.rational ? ", and 3/2 either way" : "");
 		// what holds for a leg of any ratio, checked once that ratio is known to be served: a tick of whole groups, and one rate
 		// for the one concealer batch
 		if (lr % 800 != 0)
@@ -148,21 +197,24 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 			MI_REFUSE("%s: plc with legs at %d Hz and %d Hz: the concealer batch has one rate", fn, p->common, lr);
 		if (!p->common) p->common = lr;
 		widest = std::max(widest, lr);
-		if (rb & UD_R32) {
+		p->ratios |= added;
+		if (rb & UD_GEN) {
+			if (std::find(p->generic.begin(), p->generic.end(), (uint8_t)rb) == p->generic.end()) p->generic.push_back((uint8_t)rb);
+		} else if (rb & UD_R32) {
 			(up ? p->r32_above : p->r32_below) = true;
 		} else {
 			(up ? p->above : p->used)[rb & 7] = true;
 			p->updown |= up;
 			p->max_ratio = std::max(p->max_ratio, rb & 7);
 		}
-		data |= codec && (rb & (UD_ABOVE | UD_R32)); // (such a leg brings the codecs as data, whether they differ or not)
+		data |= codec && ((rb & (UD_ABOVE | UD_R32 | UD_GEN)) || added); // (such a leg brings the codecs as data, whether they differ or not)
 		p->ratio.push_back((uint8_t)rb);
 	}
 	p->rational = p->r32_above || p->r32_below; // without such a leg: mi_bridge_create_concealed's bridge exactly
-	p->rated = p->max_ratio > 1 || p->rational;
+	p->rated = p->max_ratio > 1 || p->rational || !p->generic.empty();
 	if (!p->rated) p->ratio.clear();
 	// ---- the LDS of a launch.  Samples per row: the widest leg's tick where one is above the mix
-	p->wide = p->updown ? widest / 100 : p->rational ? std::max(len, widest / 100) : len;
+	p->wide = p->updown ? widest / 100 : p->rational || !p->generic.empty() ? std::max(len, widest / 100) : len;
 	p->row_w = (p->wide >> 2) | 1;
 	p->sum_off = (int)up16((size_t)mm * p->row_w * 8);
 	p->nslice = std::max(1, std::min(mm, BT / (len >> 2)));
@@ -187,17 +239,27 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 		// its tick, x 2/3 from the mix's
 		if (p->r32_above) scratch = std::max(scratch, std::max(rational_scratch(3, len / 2 * 3), rational_scratch(2, len)));
 		if (p->r32_below) scratch = std::max(scratch, std::max(rational_scratch(2, len / 3 * 2), rational_scratch(3, len)));
+		// a leg at a : b in mi_resampler's generic order: leg -> mix from its tick in front of the pin (b rows of taps), mix -> leg
+		// from the mix's behind it (a rows); its histories are filt_len - 1 samples, kept at mi_resampler's stride
+		int generic_hist = 0;
+		for (const uint8_t rb : p->generic) {
+			const int la = gen_a(rb), cb = gen_b(rb), fin = filter_rule(la, cb).filt_len, fout = filter_rule(cb, la).filt_len;
+			scratch = std::max(scratch, up16(std::max(generic_scratch(fin, cb, len / cb * la), generic_scratch(fout, la, len))));
+			generic_hist = std::max(generic_hist, (std::max(fin, fout) - 1 + 7) & ~7);
+		}
 		const size_t scratch_off = up16(lds);
 		lds = scratch_off + (BT / 64) * scratch;
 		if (lds + RATED_STATIC_LDS > BRIDGE_LDS_MAX)
 			MI_REFUSE("%s: a conference's tick and its resamplers' scratch must fit %zu bytes of LDS (%d members x %d samples "
 			          "= %zu, + %d wavefronts x %zu for ratio %d%s, + %zu of the kernel's own: %zu)",
-			          fn, BRIDGE_LDS_MAX, mm, p->wide, scratch_off, BT / 64, scratch, p->max_ratio, p->rational ? " and 3/2" : "", RATED_STATIC_LDS,
+			          fn, BRIDGE_LDS_MAX, mm, p->wide, scratch_off, BT / 64, scratch, p->max_ratio,
+			          !p->generic.empty() ? " and a : b" : p->rational ? " and 3/2" : "", RATED_STATIC_LDS,
 			          lds + RATED_STATIC_LDS);
 		p->scratch_off = (int)scratch_off, p->scratch_per_wave = (int)scratch;
 		p->hout_stride = p->max_ratio * RS_FILT; // mi_resampler's round_up(filt_len - 1, 8) of the longest filter
 		if (p->rational) p->hout_stride = std::max(p->hout_stride, 3 * RQ_FT); // x 2/3 keeps 71 samples (x 3/2: 47)
-		if (p->updown || p->rational) p->hin_stride = p->hout_stride;          // a down-sampler's history on either side of the pin
+		p->hout_stride = std::max(p->hout_stride, generic_hist);               // up to 127 samples
+		if (p->updown || p->rational || generic_hist) p->hin_stride = p->hout_stride; // a down-sampler's history on either side of the pin
 	} else if (lds > BRIDGE_LDS_MAX)
 		MI_REFUSE("mi_bridge_create: a conference's tick must fit %zu bytes of LDS (%d members x %d samples need %zu)", BRIDGE_LDS_MAX, mm, len, lds);
 	p->lds = lds;
@@ -216,7 +278,7 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 	}
 	if (rates) p->leg_rate.assign(rates, rates + n);
 	// the widest form a leg needs: the order matters
-	p->family = p->rational ? Plan::RATIONAL : p->updown ? Plan::UPDOWN : data ? (p->rated ? Plan::LEGS_RATED : Plan::LEGS)
+	p->family = p->ratios ? Plan::RATIOS : p->rational ? Plan::RATIONAL : p->updown ? Plan::UPDOWN : data ? (p->rated ? Plan::LEGS_RATED : Plan::LEGS)
 	            : p->rated  ? Plan::RATED : Plan::TICK;
 	return MI_OK;
 }
