@@ -73,7 +73,21 @@
  * tests/test_gpu_bridge_ratios.py).  Rows, MSVolume, absent legs and pins without MI_MIX_OUTPUT as with
  * mi_bridge_create_endpoints; cfg.plc as with mi_bridge_create_concealed.
  *
+ * Seats that change hands (mi_bridge_create_open, mi_bridge_change_members): a conference server is defined by its churn --
+ * callers arrive with whatever codec they negotiated, and they leave; ms_audio_conference_add_member -> plumb_to_conf hangs the
+ * new endpoint's own decoder, encoder and two fresh resamplers on whichever pin find_free_pin returns
+ * (audioconference.c:198-257, :322-345).  mi_bridge_create_open takes mi_bridge_create_ratios' arguments and rules plus the
+ * KINDS that may ever take a seat and plans the bridge once for all of them; mi_bridge_change_members then lets members join,
+ * leave and change kind without waiting for the device: the changes travel with the next tick submitted and are applied in
+ * stream order ahead of that tick's kernels (bridge_roster_kernel, csrc/bridge_roster.hip; the concealer's part in
+ * csrc/plc.hip), ticks in flight untouched, no other member's meter, resampler histories or concealer disturbed.  On a bridge
+ * from any older constructor the call is mi_bridge_add_member / _remove_member without the drain.  Bit for bit the parts called
+ * one by one with batches for every admitted rate (tests/test_gpu_bridge_open.py).
+ *
  * Out of scope, on purpose:
+ *   - per membership change: mi_volume_params and the pin's input gain (mi_bridge_set_volume_params and mi_bridge_set_controls,
+ *     which wait, set them); growing nstreams; kinds outside mi_bridge_create_ratios' rules; mi_session, whose membership calls
+ *     keep their waits;
  *   - rates off the 800 Hz grid (44.1 kHz: its tick is not whole groups of eight samples); whole ratios other than 2, 3, 4
  *     and 6 (5, 7, 8 and up: a down-sampler of 240 taps or more); a : b with a or b above 8 or a ratio above 8/3 (7 : 2,
  *     9 : 8: an interpolated table or more than 128 taps), in either direction: refused with MI_ENOTSUP -- mi_session and the
@@ -175,6 +189,19 @@ int mi_bridge_create_rational(mi_ctx *ctx, const mi_bridge_config *cfg, const mi
  * kernel allows itself (12 kHz legs in a 16 kHz room that also holds 48 kHz members: up to 45 members; 32 kHz legs in a
  * 24 kHz conference need 42 640 bytes at the mixer's own limit of 50 members, so there the limit is the mixer's). */
 int mi_bridge_create_ratios(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */, mi_bridge **out);
+/* The same with seats that may change hands.  h_legs [nstreams]: who sits there at creation.  h_admit [nadmit]: the KINDS of
+ * endpoint (rate, in_codec, out_codec) that may ever take a seat, besides the kinds of h_legs themselves.  The arguments and
+ * every rule are mi_bridge_create_ratios', held for the union of the two: the bridge is planned ONCE -- kernel, LDS, row pitch,
+ * history strides, resampler tables, the concealer's rate classes -- for every kind that may come, so that
+ * mi_bridge_change_members never allocates.  It is the plan of the closed bridge that holds h_legs followed by a whole
+ * conference of each admitted kind: mi_bridge_tick_bytes gives the union's pitch, wider than the initial legs' where a wider
+ * kind is admitted.  nadmit == 0 (h_admit NULL or not): mi_bridge_create_ratios' bridge exactly, the same kernels, pitch and
+ * tick bytes.  MI_ENOTSUP before anything is allocated: what mi_bridge_create_ratios refuses, the message saying
+ * "admitted kind k" where h_admit[k] is the offender (a conference that does not fit the LDS with an admitted kind in it is
+ * refused though the initial legs alone would fit); with cfg->plc every admitted rate must be one the concealer serves, and
+ * the distinct rates of the union may be seven at most (the message names the count). */
+int mi_bridge_create_open(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */,
+                          const mi_bridge_leg *h_admit /* [nadmit] */, int nadmit, mi_bridge **out);
 void mi_bridge_destroy(mi_bridge *b);
 int mi_bridge_leg_rate(const mi_bridge *b, int stream); /* the leg's rate in Hz, or MI_EINVAL */
 /* the leg's codecs and its own tick in bytes (rate / 100 x 1 or 2), on any bridge; either pointer may be NULL.
@@ -218,6 +245,38 @@ int mi_bridge_reset_streams(mi_bridge *b, int first, int count);
  * created full; remove unplumbs the pin and clears its output row, add plumbs it for a NEW endpoint (fresh meter) */
 int mi_bridge_add_member(mi_bridge *b, int stream);
 int mi_bridge_remove_member(mi_bridge *b, int stream);
+/* The same membership WITHOUT waiting for the device, and with the seat's kind its own: ms_audio_conference_add_member hangs
+ * the new endpoint's own decoder, encoder and two fresh resamplers on whichever pin is free (audioconference.c:198-257,
+ * :322-345).  The changes travel with the NEXT tick submitted -- the tick being filled, if one is acquired -- and the device
+ * applies them in stream order ahead of that tick's kernels: that tick's rows are read with the new kinds, ticks submitted
+ * earlier are untouched, collected or not.  The call contains no stream, event or device synchronise and no blocking copy.
+ * Several calls before one submit merge per seat, the last one wins.  mi_bridge_leg_rate / _codec / _bytes,
+ * mi_bridge_member_count and the election's joining order answer for the new roster as soon as the call returns.
+ *   MI_BRIDGE_JOIN: a new endpoint brings a fresh meter (state, one-second window), both resamplers' histories zero, a fresh
+ *     concealer (cfg.plc), the pin's flags MI_MIX_LINKED | MI_MIX_ACTIVE | MI_MIX_OUTPUT; the pin's input gain and the seat's
+ *     mi_volume_params stay as they are, as with mi_bridge_add_member.
+ *   MI_BRIDGE_LEAVE: the pin's flags 0, its output row zero from that tick on.
+ * Admitted kinds: on a bridge from mi_bridge_create_open with nadmit > 0, the kinds of its initial legs and its admitted
+ * kinds, on every seat; on any other bridge, for each seat that seat's own kind only -- there the call is
+ * mi_bridge_add_member / _remove_member without the drain.
+ * Nothing of a refused call is applied, and the message names the entry.  MI_ENOTSUP: a JOIN whose kind is not admitted (the
+ * message names seat, rate and codecs and says how many kinds are admitted).  MI_EINVAL: a LEAVE of a seat that is no member,
+ * a stream out of range, an op outside the two, one stream twice in one call.
+ * mi_bridge_add_member, _remove_member, _reset_streams, _set_controls and _set_volume_params keep their behaviour and their
+ * waits on every bridge; mi_bridge_add_member on an open bridge re-seats the seat's current kind, and a later
+ * mi_bridge_set_controls(h_flags) overrides every pin's flags as ever.  One of those calls made between a change and the
+ * submit that carries it has the last word on the pin's flags -- the change writes the flags the roster holds when the tick
+ * is submitted --, so device and roster agree after that tick: a LEAVE followed by mi_bridge_add_member leaves the seat
+ * plumbed (its row still cleared once), a JOIN followed by mi_bridge_remove_member leaves it unplumbed with the new kind.
+ * Out of scope: mi_volume_params and input gain per change (the waiting setters'); growing nstreams; kinds outside
+ * mi_bridge_create_ratios' rules; mi_session; the plugin's server legs. */
+#define MI_BRIDGE_JOIN 1  /* a NEW endpoint of kind `leg` takes the seat; a seat that is taken is replaced (leave + join) */
+#define MI_BRIDGE_LEAVE 2 /* the seat is unplumbed; `leg` is not read */
+typedef struct mi_bridge_change {
+	int32_t stream, op;
+	mi_bridge_leg leg;
+} mi_bridge_change;
+int mi_bridge_change_members(mi_bridge *b, const mi_bridge_change *h_changes, int count);
 int mi_bridge_member_count(const mi_bridge *b, int conference); /* plumbed pins, or MI_EINVAL */
 int mi_bridge_get_levels(mi_bridge *b, float *h_linear);        /* MS_VOLUME_GET_LINEAR of every stream */
 /* the election of audioconference.c:436-452, as mi_session_active_speakers (now_ms ignored: the ticks are the clock) */

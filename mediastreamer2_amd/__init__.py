@@ -820,6 +820,7 @@ class SessionConfig(C.Structure):
 
 
 MI_SESSION_PCM16, MI_SESSION_PCMA, MI_SESSION_PCMU = 0, 1, 2
+MI_BRIDGE_JOIN, MI_BRIDGE_LEAVE = 1, 2
 
 
 class Session(_ConferenceBatch):
@@ -886,7 +887,7 @@ class Bridge(_ConferenceBatch):
     _destroy, _prefix = "mi_bridge_destroy", "bridge"
 
     def __init__(self, ctx, nstreams, members=32, rate=8000, in_codec=MI_SESSION_PCMU, out_codec=MI_SESSION_PCMU, plc=False, device=0,
-                 leg_rates=None, legs=None, endpoints=None, concealed=None, rational=None, ratios=None):
+                 leg_rates=None, legs=None, endpoints=None, concealed=None, rational=None, ratios=None, open=None, admit=None):
         """leg_rates: the rate of every leg's code words or PCM [nstreams] (mi_bridge_create_rated: rate / leg rate in
         {1, 2, 3, 6}); None: every leg at `rate`.
         legs: every leg's (rate, in_codec, out_codec) [nstreams], a sequence of triples or a structured array with those
@@ -900,7 +901,10 @@ class Bridge(_ConferenceBatch):
         (a 32 kHz member of a 48 kHz conference, a 24 kHz member of a 16 kHz one); geometry and views are endpoints='.
         ratios: the same triples for mi_bridge_create_ratios: rational= where a leg may also be at 4 or 1/4 of `rate`, or
         stand a : b to it with a, b <= 8 and a ratio of at most 8/3 (a 32 kHz member of an 8, 12 or 24 kHz conference, a
-        12 kHz member of a 16 kHz one); geometry and views are endpoints='."""
+        12 kHz member of a 16 kHz one); geometry and views are endpoints='.
+        open: the same triples for mi_bridge_create_open: ratios= whose seats may change hands (change()); admit: the kinds
+        (rate, in_codec, out_codec) that may ever take a seat besides those of open= themselves.  The bridge is planned for
+        the union, so the byte rows' pitch is the widest admitted kind's; admit=None or empty is ratios= exactly."""
         self._own_ctx = ctx is None
         self.ctx = ctx = Context(device) if ctx is None else ctx
         cfg = BridgeConfig()
@@ -911,12 +915,14 @@ class Bridge(_ConferenceBatch):
         by_leg = {"mi_bridge_create_legs": legs, "mi_bridge_create_endpoints": endpoints, "mi_bridge_create_concealed": concealed,
                   "mi_bridge_create_rational": rational, "mi_bridge_create_ratios": ratios}
         given = [(getattr(ctx.L, entry), v) for entry, v in by_leg.items() if v is not None]
+        assert admit is None or open is not None, "admit= goes with open="
+        if open is not None:
+            assert not given, "one of legs=, endpoints=, concealed=, rational=, ratios= and open="
+            kinds = np.zeros((0, 3), np.int32) if admit is None or len(admit) == 0 else self._triples(admit)
+            given = [(lambda c, cf, lg, out: ctx.L.mi_bridge_create_open(c, cf, lg, kinds.ctypes.data, len(kinds), out), open)]
         if given:
-            assert len(given) == 1, "one of legs=, endpoints=, concealed=, rational= and ratios="
-            create, lg = given[0][0], np.asarray(given[0][1])
-            if lg.dtype.names:
-                lg = np.stack([lg[k] for k in ("rate", "in_codec", "out_codec")], axis=-1)
-            lg = np.ascontiguousarray(lg, np.int32)
+            assert len(given) == 1, "one of legs=, endpoints=, concealed=, rational=, ratios= and open="
+            create, lg = given[0][0], self._triples(given[0][1])
             assert lg.shape == (nstreams, 3), "one (rate, in_codec, out_codec) per leg"
             check(create(ctx.h, C.byref(cfg), lg.ctypes.data, C.byref(h)))
         elif leg_rates is None:
@@ -934,6 +940,27 @@ class Bridge(_ConferenceBatch):
         if given:  # byte rows at mi_bridge_tick_bytes' pitch
             self.in_dtype = self.out_dtype = C.c_uint8
             self.in_len, self.out_len = self.tick_bytes()
+
+    @staticmethod
+    def _triples(v):
+        """(rate, in_codec, out_codec) rows as mi_bridge_leg [k]: a sequence of triples or a structured array with those fields"""
+        v = np.asarray(v)
+        if v.dtype.names:
+            v = np.stack([v[k] for k in ("rate", "in_codec", "out_codec")], axis=-1)
+        v = np.ascontiguousarray(v, np.int32)
+        assert v.ndim == 2 and v.shape[1] == 3, "(rate, in_codec, out_codec) triples"
+        return v
+
+    def change(self, joins=(), leaves=()):
+        """mi_bridge_change_members: joins [(stream, (rate, in_codec, out_codec)), ...] -- a NEW endpoint of that kind takes the
+        seat, replacing whoever holds it --, leaves [stream, ...].  In effect for the next tick submitted, the one being filled
+        if one is acquired; never waits for the device.  leg_rate / leg_codec / leg_bytes / member_count answer at once."""
+        ch = np.zeros((len(joins) + len(leaves), 5), np.int32)  # mi_bridge_change: stream, op, leg
+        for i, (stream, kind) in enumerate(joins):
+            ch[i] = (int(stream), MI_BRIDGE_JOIN, *(int(v) for v in kind))
+        for i, stream in enumerate(leaves):
+            ch[len(joins) + i] = (int(stream), MI_BRIDGE_LEAVE, 0, 0, 0)
+        check(self.ctx.L.mi_bridge_change_members(self.h, ch.ctypes.data, len(ch)))
 
     def close(self):
         super().close()

@@ -68,6 +68,7 @@ BRIDGE_EXPORTS = [
     "mi_bridge_create_concealed",
     "mi_bridge_create_rational",
     "mi_bridge_create_ratios",
+    "mi_bridge_create_open", "mi_bridge_change_members",
 ]
 
 
@@ -280,6 +281,8 @@ def load():
     L.mi_bridge_create_concealed.argtypes = [vp, vp, vp, pp]
     L.mi_bridge_create_rational.argtypes = [vp, vp, vp, pp]
     L.mi_bridge_create_ratios.argtypes = [vp, vp, vp, pp]
+    L.mi_bridge_create_open.argtypes = [vp, vp, vp, vp, i32, pp]
+    L.mi_bridge_change_members.argtypes = [vp, vp, i32]
     L.mi_bridge_leg_codec.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.mi_bridge_leg_bytes.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.mi_bridge_set_volume_params.argtypes = [vp, i32, i32, C.POINTER(VolumeParams)]

@@ -42,8 +42,11 @@
 #include "tick_pipe.hpp"
 
 #include "bridge_phases.hpp"
+#include "bridge_roster.hpp"
 
 #pragma clang fp contract(off)
+
+static_assert(PLAN_MAX_RATE_CLASSES == PLC_MAX_CLASSES, "the plan refuses what the concealer cannot hold");
 
 // bridge_ratios.hip: bridge_ratios_kernel on `nconf` workgroups; args: a RatiosArgs, as bytes
 int mi_bridge_ratios_launch(const void *args, size_t bytes, int nconf, size_t lds, hipStream_t stream);
@@ -308,6 +311,16 @@ struct mi_bridge {
 	float *d_tab = nullptr;
 	int2 *d_gen = nullptr; // plan.generic: RatiosArgs::gen_tab
 	uint8_t *d_codec = nullptr; // the codecs as data ([n]; [2][n] with plc: the second row names PCM in, behind the concealer)
+	// membership changes (mi_bridge_change_members): what the calls since the last submit left per seat, merged -- op 0: nothing
+	// --, the seats whose output row is still to be cleared in slots to come, and per slot the pinned command row the tick
+	// carries, its device copy and its length
+	struct Pending { uint8_t op = 0, ratio = 0, codec = 0, cls = 0; bool clear = false; int32_t len = 0; };
+	std::vector<Pending> pending;      // [n]
+	std::vector<int32_t> changed;      // the seats with pending[s].op != 0
+	std::vector<uint8_t> clear_left;   // [n] submits in which the seat's row is still to be cleared
+	std::vector<int32_t> clearing;     // the seats with clear_left[s] != 0
+	mi_seat_cmd *h_cmd[SLOTS] = {}, *d_cmd[SLOTS] = {};
+	int ncmd[SLOTS] = {};
 };
 
 namespace {
@@ -343,10 +356,30 @@ void fill_args(mi_bridge *b) {
 	b->args.gen_tab = b->d_gen;
 }
 
+// a tick that carries membership changes: the bridge's own state in one launch, the concealer's in one of plc.hip's.  Called
+// inside the pipe's kernels(slot), behind the wait for the download that last read this slot's output rows: only there is
+// zeroing a row free of a race with it
+int apply_changes(mi_bridge *b, int slot) {
+	const Plan &pl = b->plan;
+	RosterArgs ra = {};
+	ra.cmd = b->d_cmd[slot], ra.count = b->ncmd[slot], ra.nstreams = pl.n;
+	ra.ratio = b->d_ratio, ra.codec = b->d_codec, ra.codec_pcm = b->d_codec && b->plc ? b->d_codec + pl.n : nullptr;
+	MixerEdit me;
+	mi_volume_edit(b->vol, &ra.vol);
+	mi_mixer_edit(b->mix, &me);
+	ra.flags = me.flags;
+	ra.hist_in = b->d_hist_in, ra.hist_out = b->d_hist_out, ra.hin_stride = pl.hin_stride, ra.hout_stride = pl.hout_stride;
+	ra.out = b->d_out[slot], ra.out_bytes = (int)pl.out_bytes;
+	const int rc = mi_bridge_roster_launch(ra, b->ctx->stream);
+	if (rc != MI_OK || !b->plc) return rc;
+	return mi_plc_apply_seats(b->plc, b->d_cmd[slot], b->ncmd[slot]);
+}
+
 int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's stream
 	const Plan &pl = b->plan;
 	const mi_bridge_config &cf = pl.cfg;
 	int rc, in_kind = cf.in_codec;
+	if (b->ncmd[slot] && (rc = apply_changes(b, slot)) != MI_OK) return rc;
 	RatiosArgs ga = b->args; // each kernel is passed the part that is its own
 	RationalArgs &qa = ga.q;
 	BridgeArgs &a = qa.u.l.r.b;
@@ -477,6 +510,39 @@ int build_tables(mi_bridge *b) {
 	return MI_OK;
 }
 
+// ---- membership changes on their way to the device.  stage_changes writes the command row of the tick about to be submitted
+// into the slot's pinned staging (acquire has waited for the slot's last use): the merged changes, each with MI_SEAT_CLEAR
+// where the seat's row is to be zeroed, then a bare MI_SEAT_CLEAR for every seat that left within the last SLOTS - 1 submits --
+// a slot's device row is cleared only by the tick that runs in that slot, so the clear repeats until every slot has had it.
+// changes_submitted: the tick is on its way
+void stage_changes(mi_bridge *b, int slot) {
+	int k = 0;
+	mi_seat_cmd *row = b->h_cmd[slot];
+	for (const int32_t s : b->changed) {
+		const mi_bridge::Pending &p = b->pending[(size_t)s];
+		const bool clear = p.clear || b->clear_left[(size_t)s];
+		// the pin's flags as the roster has them NOW: a waiting call since the change (mi_bridge_set_controls, _add_member,
+		// _remove_member) has had the last word on them
+		row[k++] = {s, (uint8_t)(p.op | (clear ? MI_SEAT_CLEAR : 0)), p.ratio, p.codec, p.cls, p.len, b->roster.flags[(size_t)s], {0, 0, 0}};
+	}
+	for (const int32_t s : b->clearing)
+		if (!b->pending[(size_t)s].op) row[k++] = {s, MI_SEAT_CLEAR, 0, 0, 0, 0, 0, {0, 0, 0}};
+	b->ncmd[slot] = k;
+}
+
+void changes_submitted(mi_bridge *b) {
+	for (const int32_t s : b->clearing) b->clear_left[(size_t)s]--;
+	b->clearing.erase(std::remove_if(b->clearing.begin(), b->clearing.end(), [&](int32_t s) { return !b->clear_left[(size_t)s]; }), b->clearing.end());
+	for (const int32_t s : b->changed) {
+		if (b->pending[(size_t)s].clear) {
+			if (!b->clear_left[(size_t)s]) b->clearing.push_back(s);
+			b->clear_left[(size_t)s] = SLOTS - 1;
+		}
+		b->pending[(size_t)s] = mi_bridge::Pending();
+	}
+	b->changed.clear();
+}
+
 } // namespace
 
 extern "C" {
@@ -500,6 +566,8 @@ void mi_bridge_destroy(mi_bridge *b) {
 			if (p) mi_host_free(c, p);
 		for (uint8_t *p : {b->d_in[i], b->d_present[i], b->d_ev[i], b->d_out[i]})
 			if (p) mi_dev_free(c, p);
+		if (b->h_cmd[i]) mi_host_free(c, b->h_cmd[i]);
+		if (b->d_cmd[i]) mi_dev_free(c, b->d_cmd[i]);
 	}
 	void *const rest[] = {b->d_ratio, b->d_hist_in, b->d_hist_out, b->d_tab, b->d_gen, b->d_codec, b->d_pcm, b->d_evlen};
 	for (void *p : rest)
@@ -520,6 +588,7 @@ static int build_bridge(mi_ctx *ctx, Plan &plan, mi_bridge **out) {
 	const Plan &pl = b->plan;
 	const size_t n = (size_t)pl.n;
 	b->roster.init(pl.n, pl.mm);
+	b->pending.resize(n), b->clear_left.resize(n);
 	int rc = MI_OK;
 	auto fail = [&](int code) { return mi_bridge_destroy(b), code; };
 	if ((rc = mi_volume_create(ctx, pl.n, pl.cfg.rate, &b->vol)) != MI_OK) return fail(rc);
@@ -535,6 +604,9 @@ static int build_bridge(mi_ctx *ctx, Plan &plan, mi_bridge **out) {
 		if (!b->h_in[i] || !b->h_present[i] || !b->h_out[i] || !b->d_in[i] || !b->d_present[i] || !b->d_out[i]) return fail(MI_ENOMEM);
 		if (pl.cfg.plc) b->h_ev[i] = (uint8_t *)mi_host_alloc(ctx, n), b->d_ev[i] = (uint8_t *)mi_dev_alloc(ctx, n);
 		if (pl.cfg.plc && (!b->h_ev[i] || !b->d_ev[i])) return fail(MI_ENOMEM);
+		// every seat may change in one tick
+		b->h_cmd[i] = (mi_seat_cmd *)mi_host_alloc(ctx, n * sizeof(mi_seat_cmd)), b->d_cmd[i] = (mi_seat_cmd *)mi_dev_alloc(ctx, n * sizeof(mi_seat_cmd));
+		if (!b->h_cmd[i] || !b->d_cmd[i]) return fail(MI_ENOMEM);
 		// rows of pins whose output is off are never written: they read as zeros
 		MI_HIP(hipMemsetAsync(b->d_out[i], 0, n * pl.out_bytes, ctx->stream));
 		memset(b->h_out[i], 0, n * pl.out_bytes);
@@ -548,7 +620,7 @@ static int build_bridge(mi_ctx *ctx, Plan &plan, mi_bridge **out) {
 		if ((rc = reset_resamplers(b, 0, pl.n)) != MI_OK) return fail(rc);
 		if ((rc = build_tables(b)) != MI_OK) return fail(rc);
 	}
-	if (!pl.leg_codec.empty()) {
+	if (pl.data) {
 		std::vector<uint8_t> rows = pl.leg_codec;
 		if (pl.cfg.plc) // (one pair on every leg) a second row for the kernel behind the concealer, whose input is PCM
 			for (size_t s = 0; s < n; ++s) rows.push_back((uint8_t)(pl.leg_codec[s] & ~3u));
@@ -559,7 +631,11 @@ static int build_bridge(mi_ctx *ctx, Plan &plan, mi_bridge **out) {
 		if (pl.leg_plc) { // at every leg's own rate behind its own decoder, into PCM rows of `pitch` samples
 			std::vector<uint8_t> kind(n);
 			for (size_t s = 0; s < n; ++s) kind[s] = pl.leg_codec[s] & 3;
-			if ((rc = mi_plc_create_legs(ctx, pl.n, pl.leg_rate.data(), kind.data(), pl.pitch, &b->plc)) != MI_OK) return fail(rc);
+			std::vector<int32_t> open; // an open bridge: a rate class for every kind that may come
+			for (const mi_bridge_leg &k : pl.kinds)
+				if (std::find(open.begin(), open.end(), k.rate) == open.end()) open.push_back(k.rate);
+			if ((rc = mi_plc_create_legs(ctx, pl.n, pl.leg_rate.data(), kind.data(), pl.pitch, &b->plc, open.data(), (int)open.size())) != MI_OK)
+				return fail(rc);
 			if (!(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * pl.pitch * 2))) return fail(MI_ENOMEM);
 			if (hipMemsetAsync(b->d_pcm, 0, n * pl.pitch * 2, ctx->stream) != hipSuccess) return fail(MI_ENODEV);
 		} else { // at the legs' one rate, on rows of the host buffers' pitch
@@ -604,6 +680,14 @@ int mi_bridge_create_rational(mi_ctx *ctx, const mi_bridge_config *cfg, const mi
 }
 int mi_bridge_create_ratios(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, mi_bridge **out) {
 	return create(RULES_RATIOS, ctx, cfg, nullptr, h_legs, out);
+}
+int mi_bridge_create_open(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, const mi_bridge_leg *h_admit, int nadmit,
+                          mi_bridge **out) {
+	MI_CHECK_ARG(ctx && cfg && h_legs && out && nadmit >= 0 && (h_admit || nadmit == 0));
+	*out = nullptr;
+	Plan plan;
+	const int rc = plan_open(RULES_RATIOS, cfg, h_legs, h_admit, nadmit, &plan);
+	return rc != MI_OK ? rc : build_bridge(ctx, plan, out);
 }
 
 int mi_bridge_leg_codec(const mi_bridge *b, int stream, int *in_codec, int *out_codec) {
@@ -655,8 +739,11 @@ int mi_bridge_submit(mi_bridge *b) {
 		return MI_EINVAL;
 	}
 	const size_t n = (size_t)b->plan.n;
-	return b->pipe.submit(
+	stage_changes(b, b->pipe.next_slot());
+	const int rc = b->pipe.submit(
 	    [&](int slot) {
+		    if (b->ncmd[slot])
+			    MI_HIP(hipMemcpyAsync(b->d_cmd[slot], b->h_cmd[slot], (size_t)b->ncmd[slot] * sizeof(mi_seat_cmd), hipMemcpyHostToDevice, b->pipe.s_up));
 		    MI_HIP(hipMemcpyAsync(b->d_in[slot], b->h_in[slot], n * b->plan.in_bytes, hipMemcpyHostToDevice, b->pipe.s_up));
 		    if (b->plc) { // an absent leg is the concealer's to fill
 			    for (size_t i = 0; i < n; ++i) b->h_ev[slot][i] = b->h_present[slot][i] ? MI_PLC_RECEIVED : MI_PLC_CONCEAL;
@@ -671,6 +758,8 @@ int mi_bridge_submit(mi_bridge *b) {
 		    MI_HIP(hipMemcpyAsync(b->h_out[slot], b->d_out[slot], n * b->plan.out_bytes, hipMemcpyDeviceToHost, b->pipe.s_down));
 		    return MI_OK;
 	    });
+	if (rc == MI_OK) changes_submitted(b);
+	return rc;
 }
 
 int mi_bridge_collect(mi_bridge *b, const void **h_out) {
@@ -739,6 +828,42 @@ int mi_bridge_remove_member(mi_bridge *b, int stream) {
 	for (int i = 0; i < SLOTS; ++i) {
 		MI_HIP(hipMemsetAsync(b->d_out[i] + (size_t)stream * b->plan.out_bytes, 0, b->plan.out_bytes, b->ctx->stream));
 		memset(b->h_out[i] + (size_t)stream * b->plan.out_bytes, 0, b->plan.out_bytes);
+	}
+	return MI_OK;
+}
+
+// no stream, event or device synchronise and no blocking copy on this path: the roster and the plan's per-seat vectors answer
+// at once, the device follows with the next tick submitted (stage_changes, apply_changes)
+int mi_bridge_change_members(mi_bridge *b, const mi_bridge_change *h_changes, int count) {
+	MI_CHECK_ARG(b && count >= 0 && (h_changes || count == 0));
+	Plan &pl = b->plan;
+	std::vector<uint8_t> ratio;
+	int rc = check_changes(pl, b->roster.flags.data(), h_changes, count, &ratio);
+	if (rc != MI_OK) return rc;
+	std::vector<uint8_t> cls((size_t)count, 0); // every JOIN's rate class in the concealer, before anything is applied
+	for (int i = 0; b->plc && i < count; ++i) {
+		if (h_changes[i].op != MI_BRIDGE_JOIN) continue;
+		if ((rc = mi_plc_class_of(b->plc, h_changes[i].stream, h_changes[i].leg.rate)) < 0) return rc;
+		cls[(size_t)i] = (uint8_t)rc;
+	}
+	for (int i = 0; i < count; ++i) {
+		const mi_bridge_change &c = h_changes[i];
+		const size_t s = (size_t)c.stream;
+		mi_bridge::Pending &p = b->pending[s];
+		if (!p.op) b->changed.push_back(c.stream);
+		const bool was = b->roster.leave(c.stream); // a seat that is taken is replaced: leave + join
+		p.clear |= was;
+		if (c.op == MI_BRIDGE_LEAVE) {
+			p.op = MI_SEAT_LEAVE;
+			continue;
+		}
+		b->roster.join(c.stream); // a NEW endpoint: the last of its conference's list
+		p.op = MI_SEAT_JOIN, p.ratio = ratio[(size_t)i], p.codec = (uint8_t)(c.leg.in_codec | c.leg.out_codec << 2), p.len = c.leg.rate / 100;
+		p.cls = cls[(size_t)i];
+		if (b->plc) mi_plc_seat(b->plc, c.stream, p.cls, c.leg.in_codec);
+		if (!pl.leg_rate.empty()) pl.leg_rate[s] = c.leg.rate;
+		if (!pl.leg_codec.empty()) pl.leg_codec[s] = p.codec;
+		if (!pl.ratio.empty()) pl.ratio[s] = p.ratio;
 	}
 	return MI_OK;
 }

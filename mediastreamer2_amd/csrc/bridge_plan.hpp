@@ -129,6 +129,13 @@ struct Plan {
 	std::vector<int32_t> leg_rate;  // [n], empty: every leg at cfg.rate
 	std::vector<uint8_t> leg_codec; // [n] in_codec | out_codec << 2 where the codecs are the kernel's data; empty: cfg's pair
 	std::vector<uint8_t> ratio;     // [n] ratio bytes, empty unless `rated`
+	// the codecs are the kernel's data (a row on the device) and the host rows byte rows.  On a closed bridge: leg_codec is there
+	bool data = false;
+	// plan_open with admitted kinds: the seats may change hands.  Everything above that is not per seat was planned for `kinds`,
+	// the distinct (rate, in_codec, out_codec) of the initial legs and the admitted ones; the three per-seat vectors always exist
+	bool open = false;
+	std::vector<mi_bridge_leg> kinds;
+	std::vector<uint8_t> kind_ratio; // [kinds.size()] the ratio byte of each (1 without resamplers)
 };
 
 #define MI_PLAN_ARG(cond) if (!(cond)) return mi::set_error("%s:%d invalid argument: %s", __FILE__, __LINE__, #cond), (int)MI_EINVAL
@@ -137,8 +144,10 @@ struct Plan {
 inline size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 
 // rates [nstreams] or null: every leg at cfg->rate.  codec [nstreams] in_codec | out_codec << 2 (plan_legs has checked them)
-// or null: cfg's pair on every leg.  MI_OK, or the refusal with its text set; *p is whole only with MI_OK.
-inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const int32_t *rates, const uint8_t *codec, Plan *p) {
+// or null: cfg's pair on every leg.  MI_OK, or the refusal with its text set; *p is whole only with MI_OK.  own: the legs from
+// `own` on are no seats but stand for admitted kinds, a conference of members_per_conference each (plan_open), and a refusal
+// names them so; < 0: every leg is a seat.
+inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const int32_t *rates, const uint8_t *codec, Plan *p, int own = -1) {
 	MI_PLAN_ARG(cfg && p);
 	MI_PLAN_ARG(cfg->nstreams > 0 && cfg->members_per_conference > 0 && cfg->members_per_conference <= MI_MIXER_MAX_CHANNELS &&
 	            cfg->nstreams % cfg->members_per_conference == 0);
@@ -150,6 +159,8 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 	*p = Plan(), p->cfg = *cfg;
 	const int n = p->n = cfg->nstreams, mm = p->mm = cfg->members_per_conference, len = p->len = cfg->rate / 100;
 	p->nconf = n / mm;
+	const auto who = [&](int s) { return own >= 0 && s >= own ? "admitted kind" : "leg"; };
+	const auto idx = [&](int s) { return own >= 0 && s >= own ? (s - own) / mm : s; };
 	bool mixed = false, differ = false; // the legs' pairs differ: the codecs are the kernel's data; they or the rates do
 	for (int s = 1; codec && s < n; ++s) mixed |= codec[s] != codec[0], differ |= codec[s] != codec[0] || (rates && rates[s] != rates[0]);
 	p->leg_plc = rules.leg_plc && cfg->plc && differ;
@@ -172,27 +183,27 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 			const int la = lr / g, cb = cfg->rate / g; // a : b
 			const FilterRule in = filter_rule(la, cb), out = filter_rule(cb, la);
 			if (la > GENERIC_MAX_TERM || cb > GENERIC_MAX_TERM || !in.direct || !out.direct || in.filt_len > GENERIC_MAX_FILT || out.filt_len > GENERIC_MAX_FILT)
-				MI_REFUSE("%s: leg %d at %d Hz in a %d Hz conference is %d : %d (%.3f), a ratio whose resamplers have no direct table "
+				MI_REFUSE("%s: %s %d at %d Hz in a %d Hz conference is %d : %d (%.3f), a ratio whose resamplers have no direct table "
 				          "of at most %d taps (%d taps%s one way, %d%s the other); supported: whole ratios 1, 2, 3, 4, 6 either way, and a : b "
 				          "with a, b <= %d and a ratio of at most 8/3",
-				          fn, s, lr, cfg->rate, la, cb, (double)std::max(la, cb) / std::min(la, cb), GENERIC_MAX_FILT, in.filt_len,
+				          fn, who(s), idx(s), lr, cfg->rate, la, cb, (double)std::max(la, cb) / std::min(la, cb), GENERIC_MAX_FILT, in.filt_len,
 				          in.direct ? "" : ", interpolated,", out.filt_len, out.direct ? "" : ", interpolated,", GENERIC_MAX_TERM);
 			rb = gen_byte(la, cb), added = true;
 		}
 		if (up && !rules.above)
-			MI_REFUSE("mi_bridge_create_rated: leg %d at %d Hz is above its conference's %d Hz (only legs at or below the mix are resampled)",
-			          s, lr, cfg->rate);
+			MI_REFUSE("mi_bridge_create_rated: %s %d at %d Hz is above its conference's %d Hz (only legs at or below the mix are resampled)",
+			          who(s), idx(s), lr, cfg->rate);
 		const int hi = up ? lr : cfg->rate, lo = up ? cfg->rate : lr;
 		if (rb == NO_WHOLE_RATIO)
-			MI_REFUSE("%s: leg %d at %d Hz in a %d Hz conference is no whole ratio (%.3f); supported: 1, 2, 3, 6%s", fn, s, lr, cfg->rate,
+			MI_REFUSE("%s: %s %d at %d Hz in a %d Hz conference is no whole ratio (%.3f); supported: 1, 2, 3, 6%s", fn, who(s), idx(s), lr, cfg->rate,
 			          (double)hi / lo, rules.rational ? ", and 3/2 either way" : "");
 		if (rb == RATIO_NOT_SERVED)
-			MI_REFUSE("%s: leg %d at %d Hz in a %d Hz conference is ratio %d; supported: 1, 2, 3, %s6%s", fn, s, lr, cfg->rate, hi / lo,
+			MI_REFUSE("%s: %s %d at %d Hz in a %d Hz conference is ratio %d; supported: 1, 2, 3, %s6%s", fn, who(s), idx(s), lr, cfg->rate, hi / lo,
 			          rules.ratios ? "4, " : "", rules.ratios ? ", and a : b with a, b <= 8 up to 8/3 either way" : rules.rational ? ", and 3/2 either way" : "");
 		// what holds for a leg of any ratio, checked once that ratio is known to be served: a tick of whole groups, and one rate
 		// for the one concealer batch
 		if (lr % 800 != 0)
-			MI_REFUSE("%s: leg %d's rate %d is no multiple of 800 (a 10 ms tick must be whole groups of 8 samples)", fn, s, lr);
+			MI_REFUSE("%s: %s %d's rate %d is no multiple of 800 (a 10 ms tick must be whole groups of 8 samples)", fn, who(s), idx(s), lr);
 		if (cfg->plc && !p->leg_plc && p->common && lr != p->common)
 			MI_REFUSE("%s: plc with legs at %d Hz and %d Hz: the concealer batch has one rate", fn, p->common, lr);
 		if (!p->common) p->common = lr;
@@ -266,6 +277,7 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 	// ---- the host rows
 	p->pitch = p->rated ? widest / 100 : len;
 	p->in_bytes = (size_t)p->pitch * (cfg->in_codec ? 1 : 2), p->out_bytes = (size_t)p->pitch * (cfg->out_codec ? 1 : 2);
+	p->data = data;
 	if (data) { // byte rows: the widest leg's tick in bytes, rounded up to the 16 bytes a lane loads
 		p->in_bytes = p->out_bytes = 0;
 		for (int s = 0; s < n; ++s) {
@@ -286,10 +298,13 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 // mi_bridge_create_legs and its successors: the legs' codecs checked, the concealer asked about every rate where it will be
 // the per-leg one, then plan_bridge under the same rules with the first leg's pair as the bridge's.  A uniform bridge is
 // mi_bridge_create_rated's, its one pair compile-time in the kernels.
-inline int plan_legs(const Rules &rules, const mi_bridge_config *cfg, const mi_bridge_leg *legs, Plan *p) {
+inline int plan_legs(const Rules &rules, const mi_bridge_config *cfg, const mi_bridge_leg *legs, Plan *p, int own = -1) {
 	MI_PLAN_ARG(cfg && legs && p);
 	MI_PLAN_ARG(cfg->nstreams > 0);
 	const size_t n = (size_t)cfg->nstreams;
+	const int per = std::max(1, cfg->members_per_conference);
+	const auto who = [&](size_t s) { return own >= 0 && (int)s >= own ? "admitted kind" : "leg"; };
+	const auto idx = [&](size_t s) { return own >= 0 && (int)s >= own ? ((int)s - own) / per : (int)s; };
 	std::vector<int32_t> rate(n);
 	std::vector<uint8_t> codec(n);
 	int differs = -1; // the first leg whose pair is not leg 0's
@@ -297,20 +312,114 @@ inline int plan_legs(const Rules &rules, const mi_bridge_config *cfg, const mi_b
 		const mi_bridge_leg &l = legs[s];
 		for (int v : {l.in_codec, l.out_codec})
 			if (v < MI_SESSION_PCM16 || v > MI_SESSION_PCMU)
-				MI_REFUSE("%s: leg %zu names codec %d; supported: MI_SESSION_PCM16 (0), MI_SESSION_PCMA (1), MI_SESSION_PCMU (2)", rules.fn, s, v);
+				MI_REFUSE("%s: %s %d names codec %d; supported: MI_SESSION_PCM16 (0), MI_SESSION_PCMA (1), MI_SESSION_PCMU (2)", rules.fn, who(s), idx(s), v);
 		rate[s] = l.rate;
 		codec[s] = (uint8_t)(l.in_codec | l.out_codec << 2);
 		if (differs < 0 && codec[s] != codec[0]) differs = (int)s;
 	}
 	if (rules.leg_plc && cfg->plc) {
 		for (size_t s = 0; s < n; ++s) // what the concealer cannot serve
-			if (const int rc = mi_plc_check_rate(rules.fn, "leg", (int)s, rate[s])) return rc;
+			if (const int rc = mi_plc_check_rate(rules.fn, who(s), idx(s), rate[s])) return rc;
 	} else if (differs >= 0 && cfg->plc)
 		MI_REFUSE("%s: plc with leg %d's codecs (in %d, out %d) unlike leg 0's (in %d, out %d): the concealer batch "
 		          "sits behind one decoder", rules.fn, differs, legs[differs].in_codec, legs[differs].out_codec, legs[0].in_codec, legs[0].out_codec);
 	mi_bridge_config c = *cfg;
 	c.in_codec = legs[0].in_codec, c.out_codec = legs[0].out_codec;
-	return plan_bridge(rules, &c, rate.data(), codec.data(), p);
+	return plan_bridge(rules, &c, rate.data(), codec.data(), p, own);
+}
+
+// ---- seats that change hands (mi_bridge_create_open, mi_bridge_change_members)
+
+constexpr int PLAN_MAX_RATE_CLASSES = 7; // the concealer's PLC_MAX_CLASSES (common.hpp; bridge.hip holds the two equal)
+
+inline bool same_kind(const mi_bridge_leg &a, const mi_bridge_leg &b) {
+	return a.rate == b.rate && a.in_codec == b.in_codec && a.out_codec == b.out_codec;
+}
+
+// mi_bridge_create_open: ONE plan for the union -- the kinds of `legs` and the admitted ones.  It is the plan of the closed
+// bridge that holds the legs followed by one whole conference of each admitted kind (so every refusal, the LDS one included,
+// can come from an admitted kind alone, and names it so), cut back to the seats there are: the per-seat vectors are the
+// union's first nstreams entries, and a kind's ratio byte is the one plan_bridge wrote for it.  nadmit == 0: plan_legs exactly.
+inline int plan_open(const Rules &rules, const mi_bridge_config *cfg, const mi_bridge_leg *legs, const mi_bridge_leg *admit, int nadmit, Plan *p) {
+	MI_PLAN_ARG(cfg && legs && p && nadmit >= 0 && (admit || nadmit == 0));
+	if (nadmit == 0) return plan_legs(rules, cfg, legs, p);
+	MI_PLAN_ARG(cfg->nstreams > 0 && cfg->members_per_conference > 0 && cfg->members_per_conference <= MI_MIXER_MAX_CHANNELS &&
+	            cfg->nstreams % cfg->members_per_conference == 0);
+	const int n = cfg->nstreams, mm = cfg->members_per_conference;
+	MI_PLAN_ARG(nadmit <= (INT32_MAX - n) / mm);
+	std::vector<mi_bridge_leg> all(legs, legs + n);
+	for (int k = 0; k < nadmit; ++k) all.insert(all.end(), (size_t)mm, admit[k]);
+	mi_bridge_config c = *cfg;
+	c.nstreams = (int32_t)all.size();
+	const int rc = plan_legs(rules, &c, all.data(), p, n);
+	if (rc != MI_OK) return rc;
+	std::vector<int32_t> rates;
+	for (size_t i = 0; i < all.size(); ++i) {
+		const mi_bridge_leg &l = all[i];
+		if (std::find(rates.begin(), rates.end(), l.rate) == rates.end()) rates.push_back(l.rate);
+		if (std::find_if(p->kinds.begin(), p->kinds.end(), [&](const mi_bridge_leg &k) { return same_kind(k, l); }) == p->kinds.end())
+			p->kinds.push_back(l), p->kind_ratio.push_back(p->ratio.empty() ? 1 : p->ratio[i]);
+	}
+	if (cfg->plc && (int)rates.size() > PLAN_MAX_RATE_CLASSES)
+		MI_REFUSE("mi_bridge_create_open: plc with %zu distinct rates among the legs and the admitted kinds: the concealer holds %d rate classes",
+		          rates.size(), PLAN_MAX_RATE_CLASSES);
+	p->open = true;
+	p->cfg.nstreams = p->n = n, p->nconf = n / mm;
+	p->leg_rate.resize((size_t)n); // (plan_bridge keeps the rates it was given)
+	if (p->ratio.empty()) p->ratio.assign(all.size(), 1); // no resamplers: every kind at the mix
+	p->ratio.resize((size_t)n);
+	p->leg_codec.resize((size_t)n);
+	for (int s = 0; s < n; ++s) p->leg_codec[(size_t)s] = (uint8_t)(legs[s].in_codec | legs[s].out_codec << 2);
+	return MI_OK;
+}
+
+inline mi_bridge_leg seat_kind(const Plan &p, int s) {
+	const int pair = p.leg_codec.empty() ? p.cfg.in_codec | p.cfg.out_codec << 2 : p.leg_codec[(size_t)s];
+	return {p.leg_rate.empty() ? p.cfg.rate : p.leg_rate[(size_t)s], pair & 3, pair >> 2};
+}
+
+// mi_bridge_change_members' rules, without a device.  flags [p.n]: the pins' MI_MIX_* as the roster has them.  MI_OK with
+// ratio [count] -- the ratio byte of every JOIN's kind, 0 for a LEAVE --, or the refusal naming the entry; nothing is applied
+// here.  An open plan admits its `kinds` on every seat; any other plan admits on a seat that seat's own kind only.
+inline int check_changes(const Plan &p, const uint8_t *flags, const mi_bridge_change *ch, int count, std::vector<uint8_t> *ratio) {
+	MI_PLAN_ARG(flags && ratio && count >= 0 && (ch || count == 0));
+	const char *fn = "mi_bridge_change_members";
+	std::vector<int32_t> seen;
+	for (int i = 0; i < count; ++i) {
+		const mi_bridge_change &c = ch[i];
+		if (c.stream < 0 || c.stream >= p.n) return mi::set_error("%s: entry %d names stream %d of %d", fn, i, c.stream, p.n), (int)MI_EINVAL;
+		if (c.op != MI_BRIDGE_JOIN && c.op != MI_BRIDGE_LEAVE)
+			return mi::set_error("%s: entry %d (stream %d) has op %d; MI_BRIDGE_JOIN (1) or MI_BRIDGE_LEAVE (2)", fn, i, c.stream, c.op), (int)MI_EINVAL;
+		seen.push_back(c.stream);
+	}
+	std::sort(seen.begin(), seen.end());
+	const auto twice = std::adjacent_find(seen.begin(), seen.end());
+	if (twice != seen.end()) {
+		int at = count - 1;
+		while (at > 0 && ch[at].stream != *twice) --at;
+		return mi::set_error("%s: entry %d names stream %d a second time in one call", fn, at, *twice), (int)MI_EINVAL;
+	}
+	ratio->assign((size_t)count, 0);
+	for (int i = 0; i < count; ++i) {
+		const mi_bridge_change &c = ch[i];
+		if (c.op == MI_BRIDGE_LEAVE) {
+			if (!(flags[c.stream] & MI_MIX_LINKED)) return mi::set_error("%s: entry %d: stream %d is no member", fn, i, c.stream), (int)MI_EINVAL;
+			continue;
+		}
+		const mi_bridge_leg own = seat_kind(p, c.stream);
+		const size_t kind = (size_t)(std::find_if(p.kinds.begin(), p.kinds.end(), [&](const mi_bridge_leg &k) { return same_kind(k, c.leg); }) - p.kinds.begin());
+		const bool ok = p.open ? kind < p.kinds.size() : same_kind(own, c.leg);
+		if (!ok && p.open)
+			MI_REFUSE("%s: entry %d: seat %d cannot take an endpoint at %d Hz with codecs in %d, out %d: the bridge admits %zu kinds, "
+			          "those of its initial legs and of mi_bridge_create_open's h_admit", fn, i, c.stream, c.leg.rate, c.leg.in_codec, c.leg.out_codec,
+			          p.kinds.size());
+		if (!ok)
+			MI_REFUSE("%s: entry %d: seat %d cannot take an endpoint at %d Hz with codecs in %d, out %d: 1 kind is admitted there, the "
+			          "seat's own (%d Hz, in %d, out %d); mi_bridge_create_open plans a bridge for more", fn, i, c.stream, c.leg.rate,
+			          c.leg.in_codec, c.leg.out_codec, own.rate, own.in_codec, own.out_codec);
+		(*ratio)[(size_t)i] = p.open ? p.kind_ratio[kind] : p.ratio.empty() ? 1 : p.ratio[(size_t)c.stream];
+	}
+	return MI_OK;
 }
 
 } // namespace

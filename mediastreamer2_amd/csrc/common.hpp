@@ -125,6 +125,35 @@ struct VolumeView {
 };
 void mi_volume_view(const mi_volume *v, VolumeView *out);
 
+// What the bridge's roster kernel (bridge_roster.hip) WRITES of an mi_volume and an mi_mixer when a new endpoint takes a seat,
+// in stream order ahead of a tick: the meter as conference.hpp's reset_meters leaves it -- the state record, both halves of the
+// energy mirror, the one-second window -- and the pin's flags.  The arrays are those of mi_volume_view / mi_mixer_view.
+struct VolumeEdit {
+	mi_volume_state *state = nullptr;
+	float2 *win = nullptr;
+	float *energy[2] = {nullptr, nullptr};
+};
+void mi_volume_edit(mi_volume *v, VolumeEdit *out);
+struct MixerEdit {
+	uint8_t *flags = nullptr; // [nconf][mm] MI_MIX_*
+};
+void mi_mixer_edit(mi_mixer *m, MixerEdit *out);
+
+// One membership change as the device applies it (mi_bridge_change_members, bridge.hip): a pinned row of these per pipe slot,
+// uploaded with the tick they take effect in.  bridge_roster.hip applies the bridge's part, plc.hip the concealer's.
+enum : uint8_t { MI_SEAT_JOIN = 1, MI_SEAT_LEAVE = 2, MI_SEAT_CLEAR = 4 }; // CLEAR: zero the seat's output row in this tick's slot
+struct mi_seat_cmd {
+	int32_t stream;
+	uint8_t op;    // MI_SEAT_*
+	uint8_t ratio; // JOIN: the kind's ratio byte (bridge_plan.hpp)
+	uint8_t codec; // JOIN: in_codec | out_codec << 2
+	uint8_t cls;   // JOIN: the kind's rate class in the concealer
+	int32_t len;   // JOIN: the kind's rate / 100
+	uint8_t flags; // JOIN, LEAVE: the pin's MI_MIX_* as the roster has them when the tick is submitted
+	uint8_t pad[3];
+};
+static_assert(sizeof(mi_seat_cmd) == 16, "a command is one 16-byte load");
+
 // The concealer batch whose streams each have a rate and a decoder of their own (plc.hip), for the bridge's legs:
 // h_rate [nstreams] in Hz (multiples of 800), h_kind [nstreams] MI_SESSION_PCM16 | PCMA | PCMU: what the stream's byte row
 // holds, pitch: samples per PCM row.  MI_ENOTSUP, stream and rate in the message: a rate outside 8 - 48 kHz, or one whose
@@ -133,9 +162,24 @@ void mi_volume_view(const mi_volume *v, VolumeView *out);
 // mi_plc_process_legs: a tick of rate / 100 samples for every stream -- d_in byte rows at in_pitch (a multiple of 16; a
 // stream fills the first rate / 100 x 1 or 2 bytes), d_pcm the int16 rows out at `pitch` samples, d_mode the MI_PLC_*
 // event bytes -- in three launches, the decoders inside the RECEIVED pass.
+// Seats that change hands (mi_bridge_create_open): h_open_rate [nopen] are the rates of EVERY kind that may come, the
+// streams' own among them.  Each is a class from the start, built with room for every stream at rank = stream -- any class
+// may come to hold all of them, so a change never allocates.  nopen == 0: classes for the rates present, sized by their
+// streams, as ever.
+// mi_plc_class_of: the class a NEW endpoint at `rate` on `stream` would sit in, nothing changed; MI_ENOTSUP for a rate that
+// has none (a batch that is not open serves the stream's own rate only); mi_plc_create's batch: class 0 for every rate.
+// mi_plc_seat: that endpoint, whose row holds `kind`, takes the stream in class `cls`, on the host's mirrors at once.  mi_plc_apply_seats: the device's part, one launch on the context's stream over d_cmd
+// [count] -- for every JOIN the stream's tag and length rewritten and its class state at its rank zeroed (class_reset's four
+// arrays).
+constexpr int PLC_MAX_CLASSES = 7;
 int mi_plc_check_rate(const char *fn, const char *what, int index, int rate);
-int mi_plc_create_legs(mi_ctx *c, int nstreams, const int32_t *h_rate, const uint8_t *h_kind, int pitch, mi_plc **out);
+int mi_plc_create_legs(mi_ctx *c, int nstreams, const int32_t *h_rate, const uint8_t *h_kind, int pitch, mi_plc **out,
+                       const int32_t *h_open_rate = nullptr, int nopen = 0);
 int mi_plc_process_legs(mi_plc *p, const uint8_t *d_in, size_t in_pitch, int16_t *d_pcm, size_t pitch, const uint8_t *d_mode);
+struct mi_seat_cmd;
+int mi_plc_class_of(const mi_plc *p, int stream, int rate);
+void mi_plc_seat(mi_plc *p, int stream, int cls, int kind);
+int mi_plc_apply_seats(mi_plc *p, const mi_seat_cmd *d_cmd, int count);
 
 struct mi_ctx {
 	int device = 0;

@@ -366,6 +366,11 @@ void mi_mixer_view(const mi_mixer *m, MixerView *v) {
 	v->device = m->ctx->device;
 }
 
+void mi_mixer_edit(mi_mixer *m, MixerEdit *out) {
+	*out = MixerEdit();
+	if (m) out->flags = m->d_flags;
+}
+
 extern "C" {
 
 int mi_mixer_create(mi_ctx *ctx, int nconf, int max_members, int nsamples, mi_mixer **out) {

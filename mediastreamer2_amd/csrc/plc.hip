@@ -412,8 +412,7 @@ __global__ __launch_bounds__(64) void plc_conceal_kernel(PlcArgs a) {
 // rate, a whole PlcArgs record with its own state arrays; a stream's tag byte names its class (bits 0-2) and what its
 // row holds (MI_SESSION_* << 4), its rank is its index among the class's streams.  The tick is three launches as above:
 // plc_list_kernel as it is (the first record's nstreams, mode, len, count and list), then the two kernels below, which
-// pick the stream's record and run plc_stream on it.
-constexpr int PLC_MAX_CLASSES = 7;
+// pick the stream's record and run plc_stream on it.  (PLC_MAX_CLASSES: common.hpp)
 
 struct PlcLegsArgs {
 	PlcArgs cls[PLC_MAX_CLASSES]; // blocks / stride: the PCM rows out; nstreams, cap, len, mode, count, list: the same in each
@@ -458,6 +457,46 @@ __global__ __launch_bounds__(64) void plc_legs_conceal_kernel(PlcLegsArgs la) {
 		plc_stream<true, true>(a, lds_all, rank, s, MI_PLC_CONCEAL, a.len[s], reinterpret_cast<const uint4 *>(a.meta)[rank], lane);
 		wave_sync(); // the next stream reuses the LDS
 	}
+}
+
+// ---- seats that change hands (mi_plc_apply_seats): a NEW endpoint's concealer is a fresh plc_context_t at the seat's rank in
+// the class of ITS rate -- the four arrays class_reset clears --, and on the per-leg form the seat's tag (class, what its row
+// holds) and tick length are the new kind's.  One wavefront per command of the tick's row, in stream order ahead of the tick.
+struct PlcSeatClass {
+	int16_t *cont, *hist, *gen;
+	uint32_t *meta;
+	int T, nb;
+};
+struct PlcSeatArgs {
+	PlcSeatClass cls[PLC_MAX_CLASSES];
+	const mi_seat_cmd *cmd;
+	int count, nstreams, nclass;
+	uint8_t *tag;        // null: mi_plc_create's batch -- class 0, rank = stream, nothing per stream to rewrite
+	const int32_t *rank;
+	int32_t *len;
+};
+
+__global__ __launch_bounds__(64) void plc_seats_kernel(PlcSeatArgs a) {
+	const int i = blockIdx.x, lane = threadIdx.x;
+	if (i >= a.count) return;
+	const uint4 c = reinterpret_cast<const uint4 *>(a.cmd)[i]; // stream | op, ratio, codec, cls | len | flags
+	const int s = (int)c.x;
+	if (!(c.y & MI_SEAT_JOIN) || s < 0 || s >= a.nstreams) return;
+	int k = 0, r = s;
+	if (a.tag) {
+		k = (int)(c.y >> 24);
+		if (k >= a.nclass) return; // (the host names classes it has built)
+		r = a.rank[s];
+		if (lane == 0) a.tag[s] = (uint8_t)((unsigned)k | ((c.y >> 16) & 3u) << 4), a.len[s] = (int32_t)c.z;
+	}
+	const PlcSeatClass &q = a.cls[__builtin_amdgcn_readfirstlane(k)];
+	const size_t at = (size_t)r;
+	uint32_t *cont = reinterpret_cast<uint32_t *>(q.cont + at * 2 * q.T), *hist = reinterpret_cast<uint32_t *>(q.hist + at * q.nb);
+	uint32_t *gen = reinterpret_cast<uint32_t *>(q.gen + at * 2 * q.nb);
+	for (int j = lane; j < q.T; j += 64) cont[j] = 0u;       // [2 T] int16
+	for (int j = lane; j < q.nb / 2; j += 64) hist[j] = 0u;  // [nb] int16, nb even
+	for (int j = lane; j < q.nb; j += 64) gen[j] = 0u;       // [2 nb] int16
+	if (lane < 4) q.meta[at * 4 + lane] = 0u;
 }
 
 // kf_factor kiss_fft.c:412-435: 4s first, then 2, 3, 5, ...
@@ -523,6 +562,7 @@ struct mi_plc {
 	std::vector<int32_t> rank; // [nstreams] index among the class's streams
 	uint8_t *d_tag = nullptr;
 	int32_t *d_rank = nullptr, *d_len = nullptr; // d_len: rate / 100
+	bool open = false; // every class has room for every stream at rank = stream (mi_plc_create_legs' h_open_rate)
 	size_t in_bytes = 0;                         // the widest leg's tick in bytes, rounded up to the 16 a lane loads
 };
 
@@ -714,10 +754,16 @@ int mi_plc_check_rate(const char *fn, const char *what, int index, int rate) {
 	return MI_OK;
 }
 
-int mi_plc_create_legs(mi_ctx *c, int nstreams, const int32_t *h_rate, const uint8_t *h_kind, int pitch, mi_plc **out) {
+int mi_plc_create_legs(mi_ctx *c, int nstreams, const int32_t *h_rate, const uint8_t *h_kind, int pitch, mi_plc **out,
+                       const int32_t *h_open_rate, int nopen) {
 	MI_CHECK_ARG(c && out && nstreams > 0 && h_rate && h_kind && pitch > 0 && pitch <= 4096 && pitch % 8 == 0);
+	MI_CHECK_ARG(nopen >= 0 && (h_open_rate || nopen == 0));
 	*out = nullptr;
 	int rc;
+	for (int k = 0; k < nopen; ++k) {
+		if ((rc = mi_plc_check_rate("mi_plc_create", "admitted rate", k, h_open_rate[k])) != MI_OK) return rc;
+		MI_CHECK_ARG(h_open_rate[k] % 800 == 0 && h_open_rate[k] / 100 <= pitch);
+	}
 	for (int s = 0; s < nstreams; ++s) {
 		if ((rc = mi_plc_check_rate("mi_plc_create", "stream", s, h_rate[s])) != MI_OK) return rc;
 		// a tick is whole 16-byte groups of PCM inside the row, and the row holds one of the three kinds
@@ -728,10 +774,31 @@ int mi_plc_create_legs(mi_ctx *c, int nstreams, const int32_t *h_rate, const uin
 	p->ctx = c, p->nstreams = nstreams, p->cap = pitch, p->legs = true;
 	p->tag.resize((size_t)nstreams), p->rank.resize((size_t)nstreams);
 	std::vector<int32_t> len((size_t)nstreams);
+	p->open = nopen > 0;
+	for (int k = 0; k < nopen; ++k) { // the classes of every kind that may come, the streams' own among them
+		size_t at = 0;
+		while (at < p->cls.size() && p->cls[at].rate != h_open_rate[k]) ++at;
+		if (at < p->cls.size()) continue;
+		if (at == PLC_MAX_CLASSES) {
+			mi::set_error("mi_plc_create: admitted rate %d (%d Hz) brings an eighth rate (a bridge's ratios allow seven)", k, h_open_rate[k]);
+			delete p;
+			return MI_ENOTSUP;
+		}
+		p->cls.emplace_back();
+		class_sizes(h_open_rate[k], &p->cls[at]); // (mi_plc_check_rate above has held the rate to it)
+		p->cls[at].count = nstreams;
+		// any stream may come to sit at this rate with PCM in its row: the widest tick a row must hold
+		p->in_bytes = std::max(p->in_bytes, mi::round_up((size_t)h_open_rate[k] / 100 * 2, 16));
+	}
 	for (int s = 0; s < nstreams; ++s) {
 		size_t k = 0;
 		while (k < p->cls.size() && p->cls[k].rate != h_rate[s]) ++k;
 		if (k == p->cls.size()) {
+			if (p->open) {
+				mi::set_error("mi_plc_create: stream %d at %d Hz is at none of the %d admitted rates", s, h_rate[s], nopen);
+				delete p;
+				return MI_EINVAL;
+			}
 			if (k == PLC_MAX_CLASSES) {
 				mi::set_error("mi_plc_create: stream %d at %d Hz brings an eighth rate (a bridge's ratios allow seven)", s, h_rate[s]);
 				delete p;
@@ -741,7 +808,7 @@ int mi_plc_create_legs(mi_ctx *c, int nstreams, const int32_t *h_rate, const uin
 			class_sizes(h_rate[s], &p->cls[k]);
 		}
 		p->tag[(size_t)s] = (uint8_t)(k | (size_t)h_kind[s] << 4);
-		p->rank[(size_t)s] = p->cls[k].count++;
+		p->rank[(size_t)s] = p->open ? s : p->cls[k].count++;
 		len[(size_t)s] = h_rate[s] / 100;
 		p->in_bytes = std::max(p->in_bytes, mi::round_up((size_t)len[(size_t)s] * (h_kind[s] ? 1 : 2), 16));
 	}
@@ -794,6 +861,41 @@ int mi_plc_process_legs(mi_plc *p, const uint8_t *d_in, size_t in_pitch, int16_t
 	MI_LAUNCH_CHECK();
 	const int grid = std::min(p->nstreams, (p->ctx->cu_count > 0 ? p->ctx->cu_count : 256) * 16);
 	hipLaunchKernelGGL(plc_legs_conceal_kernel, dim3(grid), dim3(64), p->lds, p->ctx->stream, la);
+	MI_LAUNCH_CHECK();
+	return MI_OK;
+}
+
+int mi_plc_class_of(const mi_plc *p, int stream, int rate) {
+	MI_CHECK_ARG(p && stream >= 0 && stream < p->nstreams);
+	if (!p->legs) return 0;
+	int k = p->tag[(size_t)stream] & 7;
+	if (p->open) {
+		k = 0;
+		while (k < (int)p->cls.size() && p->cls[(size_t)k].rate != rate) ++k;
+	}
+	if (k >= (int)p->cls.size() || p->cls[(size_t)k].rate != rate) {
+		mi::set_error("mi_plc: stream %d cannot take a concealer at %d Hz: no such rate class", stream, rate);
+		return MI_ENOTSUP;
+	}
+	return k;
+}
+
+void mi_plc_seat(mi_plc *p, int stream, int cls, int kind) {
+	if (p->legs) p->tag[(size_t)stream] = (uint8_t)(cls | kind << 4);
+}
+
+int mi_plc_apply_seats(mi_plc *p, const mi_seat_cmd *d_cmd, int count) {
+	MI_CHECK_ARG(p && d_cmd && count > 0 && count <= p->nstreams && p->cls.size() <= (size_t)PLC_MAX_CLASSES);
+	int rc;
+	if ((rc = p->ctx->activate()) != MI_OK) return rc;
+	PlcSeatArgs a{};
+	for (size_t k = 0; k < p->cls.size(); ++k) {
+		const PlcClass &q = p->cls[k];
+		a.cls[k] = {q.d_cont, q.d_hist, q.d_gen, q.d_meta, q.T, q.nb};
+	}
+	a.cmd = d_cmd, a.count = count, a.nstreams = p->nstreams, a.nclass = (int)p->cls.size();
+	if (p->legs) a.tag = p->d_tag, a.rank = p->d_rank, a.len = p->d_len;
+	hipLaunchKernelGGL(plc_seats_kernel, dim3((unsigned)count), dim3(64), 0, p->ctx->stream, a);
 	MI_LAUNCH_CHECK();
 	return MI_OK;
 }

@@ -542,6 +542,13 @@ void mi_volume_view(const mi_volume *v, VolumeView *out) {
 	out->device = v->ctx->device;
 }
 
+void mi_volume_edit(mi_volume *v, VolumeEdit *out) {
+	*out = VolumeEdit();
+	if (!v) return;
+	out->state = v->d_state, out->win = v->d_win;
+	out->energy[0] = v->d_energy[0], out->energy[1] = v->d_energy[1];
+}
+
 extern "C" {
 
 void mi_volume_default_params(mi_volume_params *p) {
