@@ -15,13 +15,11 @@
 #include "g711.hpp"
 #include "volume_ctl.hpp"
 
-#include "bridge_plan.hpp" // BT, the resamplers' constants and lengths, the ratio byte's bits: what the host's plan shares
+#include "bridge_plan.hpp" // BT, the resamplers' constants, lengths and steps, the ratio byte's bits: what the host's plan shares
 
 #pragma clang fp contract(off)
 
 namespace {
-
-#include "resample_tile.hpp"
 
 // ---- the kernels' arguments.  Each kernel's struct holds the one before it, so the host fills a RationalArgs once per bridge
 // (mi_bridge::args, bridge.hip) and every kernel is passed its own part of it.
@@ -104,7 +102,6 @@ __device__ __forceinline__ int leg_span(int r, int conf) {
 
 __device__ __forceinline__ int lo16(unsigned w) { return (int)(short)(w & 0xffffu); }
 __device__ __forceinline__ int hi16(unsigned w) { return (int)(short)(w >> 16); }
-__device__ __forceinline__ unsigned pack16(int lo, int hi) { return (unsigned)(lo & 0xffff) | ((unsigned)hi << 16); }
 
 // ---- a kernel's view of its conference, built once at its head: the dynamic LDS, the kernel's static arrays (null where it
 // has none) and the locals every phase reads
@@ -380,30 +377,20 @@ __device__ __forceinline__ void mix_minus(const Conf &k, uint8_t *out, int pitch
 	}
 }
 
-// ---- the resamplers, one wavefront running one member's (their lengths: rated_plen and its kin, bridge_plan.hpp)
-__device__ __forceinline__ void load_taps(const float *row, f2 (&t2)[RS_FILT / 2]) {
-	const float4 *tp = reinterpret_cast<const float4 *>(row);
-#pragma unroll
-	for (int j = 0; j < RS_FILT / 4; ++j) {
-		const float4 v = tp[j];
-		t2[2 * j] = (f2){v.x, v.y}, t2[2 * j + 1] = (f2){v.z, v.w};
-	}
-}
+// ---- the resamplers, one wavefront running one member's: the steps of resample_steps.hpp, which mi_resampler's batch
+// kernels (resample.hip) are composed of as well -- the same shares from zero accumulators, added in the same order.  Here a
+// member's tick is read from the head of its row in LDS and its history from HBM, a loop of quads over the 64 lanes, and the
+// tables arrive as the lanes read them (build_tables, bridge.hip).
 
-// An up-sampler by `den`: resample_up_kernel's arithmetic in its order (resample.hip) --
-// out[m * den + p] = sum_j table[p][j] * x[m + j] through fir_tile from a zero accumulator, then rs_word2int --, the
-// tick read from the head of the member's row, the result written over the row.  x: [47 + in_len + slack] floats.
+// An up-sampler by `den`: out[m * den + p] = sum_j table[p][j] * x[m + j], one share per output, the result written over the
+// row.  x: [rs_flat_len(in_len)] floats.
 __device__ __forceinline__ void rated_up(float *x, int16_t *row, int16_t *hist, const float *tab, int den, int in_len, int lane) {
 	constexpr int HIST = RS_FILT - 1, HQ = RS_FILT / 4;
-	const int xn = (HIST + in_len + RS_R + 1 + 3) & ~3;
 	for (int q = lane; q < HQ + (in_len >> 2); q += 64) {
-		const bool h = q < HQ;
-		const short4 v = h ? *reinterpret_cast<const short4 *>(hist + 4 * q) : *reinterpret_cast<const short4 *>(row + 4 * (q - HQ));
-		const int b = h ? 4 * q : HIST + 4 * (q - HQ);
-		x[b] = (float)v.x, x[b + 1] = (float)v.y, x[b + 2] = (float)v.z;
-		if (!h || b + 3 < HIST) x[b + 3] = (float)v.w; // the history row's pad slot is not a sample
+		const short4 v = q < HQ ? *reinterpret_cast<const short4 *>(hist + 4 * q) : *reinterpret_cast<const short4 *>(row + 4 * (q - HQ));
+		scatter_quad<1>(x, v, q, HQ, HIST, 1, 0);
 	}
-	for (int i = HIST + in_len + lane; i < xn; i += 64) x[i] = 0.f;
+	for (int i = HIST + in_len + lane; i < rs_flat_len(in_len); i += 64) x[i] = 0.f;
 	wave_sync(); // the whole tick is staged before the first output lands on the row
 	const int nlanes = den * (in_len >> 3);
 	for (int base = 0; base < nlanes; base += 64) {
@@ -411,10 +398,8 @@ __device__ __forceinline__ void rated_up(float *x, int16_t *row, int16_t *hist, 
 		const bool on = l < nlanes;
 		const int tile = on ? l / den : 0, p = on ? l - tile * den : 0;
 		f2 t2[RS_FILT / 2], acc2[RS_R / 2];
-		load_taps(tab + p * RS_FILT, t2);
-#pragma unroll
-		for (int q = 0; q < RS_R / 2; ++q) acc2[q] = (f2){0.f, 0.f};
-		fir_tile<RS_FILT, RS_R>(x + tile * RS_R, t2, acc2);
+		load_taps<RS_FILT>(tab + p * RS_FILT, t2);
+		fir_share<RS_FILT>(x + tile * RS_R, t2, acc2);
 		if (on) {
 #pragma unroll
 			for (int q = 0; q < RS_R / 2; ++q) {
@@ -423,7 +408,8 @@ __device__ __forceinline__ void rated_up(float *x, int16_t *row, int16_t *hist, 
 			}
 		}
 	}
-	// new history = the last 47 samples of history ++ tick; the pad slot takes the zero slack
+	// history_quad(x, lane, HIST, in_len, 1, 0) written out, the pad slot taking the zero slack instead of a test: with the
+	// step's select bridge_ratios_kernel, which sits at its 128 VGPRs, spills one (profiles/resample_steps.md)
 	if (lane < HQ) {
 		const float *hx = x + in_len + 4 * lane;
 		short4 h;
@@ -433,11 +419,10 @@ __device__ __forceinline__ void rated_up(float *x, int16_t *row, int16_t *hist, 
 	wave_sync(); // x is read out before the wave's next member stages over it
 }
 
-// A down-sampler by `num`: resample_down_kernel's arithmetic in its order -- history ++ the row's in_len samples split by
-// input phase into arrays of `plen` floats, each phase's share of eight outputs through fir_tile, the shares added phase
-// upward, rs_word2int --; the in_len / num outputs leave through store_group<OUT> at `at` of `sink`, eight per lane: a leg's row
-// behind a pin, the head of the row itself (ON_ROW) in front of one.  xp: [num][plen] ++ [in_len] floats.  `kind` is the same
-// in every lane of the wave.
+// A down-sampler by `num` (a run-time count): lane (tile, phase) computes its phase's share of eight outputs, the shares meet
+// in LDS; the in_len / num outputs leave through store_group<OUT> at `at` of `sink`, eight per lane: a leg's row behind a pin,
+// the head of the row itself (ON_ROW) in front of one.  tab: phase-major [num][48].  xp: [num][plen] ++ [in_len] floats.
+// `kind` is the same in every lane of the wave.
 template <int OUT>
 __device__ __forceinline__ void resample_down(float *xp, const int16_t *row, int16_t *hist, const float *tab, int num, int in_len, int plen,
                                               int lane, uint8_t *sink, size_t at, int kind = OUT) {
@@ -447,15 +432,8 @@ __device__ __forceinline__ void resample_down(float *xp, const int16_t *row, int
 	for (int i = lane; i < num * plen; i += 64) xp[i] = 0.f;
 	wave_sync();
 	for (int q = lane; q < nq; q += 64) { // (a 287-sample history is more than one pass of the 64 lanes)
-		const bool h = q < hq;
-		const short4 v = h ? *reinterpret_cast<const short4 *>(hist + 4 * q) : *reinterpret_cast<const short4 *>(row + 4 * (q - hq));
-		const int b = h ? 4 * q : HIST + 4 * (q - hq); // index in history ++ row
-		const short e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-		for (int j = 0; j < 4; ++j) {
-			const int i = b + j;
-			if (!h || i < HIST) xp[(i % num) * plen + i / num] = (float)e[j];
-		}
+		const short4 v = q < hq ? *reinterpret_cast<const short4 *>(hist + 4 * q) : *reinterpret_cast<const short4 *>(row + 4 * (q - hq));
+		scatter_quad<1>(xp, v, q, hq, HIST, num, plen);
 	}
 	wave_sync(); // the whole tick is staged before the first output lands on the row
 	const int nlanes = num * (out_len >> 3);
@@ -464,10 +442,8 @@ __device__ __forceinline__ void resample_down(float *xp, const int16_t *row, int
 		const bool on = l < nlanes;
 		const int tile = on ? l / num : 0, p = on ? l - tile * num : 0;
 		f2 t2[RS_FILT / 2], acc2[RS_R / 2];
-		load_taps(tab + p * RS_FILT, t2);
-#pragma unroll
-		for (int q = 0; q < RS_R / 2; ++q) acc2[q] = (f2){0.f, 0.f};
-		fir_tile<RS_FILT, RS_R>(xp + p * plen + tile * RS_R, t2, acc2);
+		load_taps<RS_FILT>(tab + p * RS_FILT, t2);
+		fir_share<RS_FILT>(xp + p * plen + tile * RS_R, t2, acc2);
 		if (on) {
 			float *d = part + (tile * RS_R) * num + p;
 #pragma unroll
@@ -476,61 +452,30 @@ __device__ __forceinline__ void resample_down(float *xp, const int16_t *row, int
 	}
 	wave_sync();
 	for (int g = lane; g < (out_len >> 3); g += 64) {
-		const float *ps = part + g * 8 * num;
 		int o[8];
-#pragma unroll
-		for (int j = 0; j < 8; ++j) {
-			float sum = 0.f;
-			for (int p = 0; p < num; ++p) sum += ps[j * num + p];
-			o[j] = rs_word2int(sum);
-		}
+		gather_group(part + g * 8 * num, num, o);
 		store_group<OUT>(sink, at, g, o, kind);
 	}
-	// new history = the last HIST samples of history ++ row; the pad slot takes a zero
-	for (int q = lane; q < hq; q += 64) {
-		short4 h;
-		short *hp = &h.x;
-#pragma unroll
-		for (int j = 0; j < 4; ++j) {
-			const int i = in_len + 4 * q + j;
-			hp[j] = (4 * q + j < HIST) ? (short)xp[(i % num) * plen + i / num] : (short)0;
-		}
-		*reinterpret_cast<short4 *>(hist + 4 * q) = h;
-	}
+	for (int q = lane; q < hq; q += 64) *reinterpret_cast<short4 *>(hist + 4 * q) = history_quad(xp, q, HIST, in_len, num, plen);
 	wave_sync(); // xp is read out before the wave's next member stages over it
 }
 
-// One member's rational resampler, L / M = 3/2 or 2/3: resample_ratio_kernel's arithmetic in its order (resample.hip).
-// Output n = q * L + r is the sum of M shares p' = 0 .. M - 1 added upward from 0.f, each share fir_tile<24, 8> from a zero
-// accumulator over taps table[(r * M) % L][k * M + p'] -- rearranged on the host: tab [r * M + p'][24] -- and the window
-// X_{u % M}[q + k + u / M], u = (r * M) / L + p', of the input split into M phases and staged twice, the second copy one float
-// early (u / M is 0 or 1 and a window starts on 16 bytes); then rs_word2int.  Lane (tile, r) computes the M shares of its
-// eight outputs one after the other into accumulators of their own and adds them in that order: the bits of the batch
-// kernel's partial-sum array without the array.  The in_len samples at the head of `row` are the input, the in_len / M * L
-// outputs are written back over the row once the whole tick is staged -- the in_resampler in front of a pin as it stands, the
-// out_resampler behind it with store_row after it.  xp: [2][M][plen] floats.
+// One member's rational resampler, L / M = 3/2 or 2/3 (resample_split_kernel's head has the indices).  tab: rearranged on the
+// host per (r, p'), [r * M + p'][24].  Lane (tile, r) computes the M shares of its eight outputs one after the other into
+// accumulators of their own and adds them upward from 0.f: the bits of the batch kernel's partial-sum array without the
+// array.  The in_len samples at the head of `row` are the input, the in_len / M * L outputs are written back over the row
+// once the whole tick is staged -- the in_resampler in front of a pin as it stands, the out_resampler behind it with
+// store_row after it.  xp: [2][M][plen] floats.
 template <int L, int M>
 __device__ __forceinline__ void rational_run(float *xp, int16_t *row, int16_t *hist, const float *tab, int in_len, int lane) {
 	constexpr int NT = RQ_FT * M, HIST = NT - 1, HQ = NT / 4;
 	static_assert((L - 1) * M / L + M - 1 < 2 * M, "u / M is 0 or 1: two copies of the phase arrays");
-	const int plen = rational_plen(M, in_len), periods = in_len / M;
+	const int plen = rs_plen_odd(RQ_FT, M, in_len), periods = in_len / M;
 	for (int i = lane; i < 2 * M * plen; i += 64) xp[i] = 0.f;
 	wave_sync();
 	for (int q = lane; q < HQ + (in_len >> 2); q += 64) {
-		const bool h = q < HQ;
-		const short4 v = h ? *reinterpret_cast<const short4 *>(hist + 4 * q) : *reinterpret_cast<const short4 *>(row + 4 * (q - HQ));
-		const int b = h ? 4 * q : HIST + 4 * (q - HQ); // index in history ++ tick
-		const short e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-		for (int k = 0; k < 4; ++k) {
-			const int i = b + k;
-			if (!h || i < HIST) { // the history row's pad slot is not a sample
-				const int ph = i % M, m = i / M;
-				const float f = (float)e[k];
-				xp[ph * plen + m] = f;                       // copy 0
-				if (m >= 1) xp[(M + ph) * plen + m - 1] = f; // copy 1: X_p[m] at m - 1
-			}
-		}
+		const short4 v = q < HQ ? *reinterpret_cast<const short4 *>(hist + 4 * q) : *reinterpret_cast<const short4 *>(row + 4 * (q - HQ));
+		scatter_quad<2>(xp, v, q, HQ, HIST, M, plen);
 	}
 	wave_sync(); // the whole tick is staged before the first output lands on the row
 	const int nlanes = L * (periods >> 3);
@@ -543,15 +488,8 @@ __device__ __forceinline__ void rational_run(float *xp, int16_t *row, int16_t *h
 		for (int pp = 0; pp < M; ++pp) {
 			const int u = (r * M) / L + pp; // copy u / M, phase u % M: array u
 			f2 t2[RQ_FT / 2];
-			const float4 *tp = reinterpret_cast<const float4 *>(tab + (r * M + pp) * RQ_FT);
-#pragma unroll
-			for (int j = 0; j < RQ_FT / 4; ++j) {
-				const float4 w = tp[j];
-				t2[2 * j] = (f2){w.x, w.y}, t2[2 * j + 1] = (f2){w.z, w.w};
-			}
-#pragma unroll
-			for (int q = 0; q < RS_R / 2; ++q) acc2[pp][q] = (f2){0.f, 0.f};
-			fir_tile<RQ_FT, RS_R>(xp + u * plen + tile * RS_R, t2, acc2[pp]);
+			load_taps<RQ_FT>(tab + (r * M + pp) * RQ_FT, t2);
+			fir_share<RQ_FT>(xp + u * plen + tile * RS_R, t2, acc2[pp]);
 		}
 		if (on) {
 #pragma unroll
@@ -564,19 +502,10 @@ __device__ __forceinline__ void rational_run(float *xp, int16_t *row, int16_t *h
 			}
 		}
 	}
-	// new history = the last 24 * M - 1 samples of history ++ tick; the pad slot takes a zero
-	if (lane < HQ) {
-		short4 h;
-		short *hp = &h.x;
-#pragma unroll
-		for (int k = 0; k < 4; ++k) {
-			const int i = in_len + 4 * lane + k;
-			hp[k] = (4 * lane + k < HIST) ? (short)xp[(i % M) * plen + i / M] : (short)0;
-		}
-		*reinterpret_cast<short4 *>(hist + 4 * lane) = h;
-	}
+	if (lane < HQ) *reinterpret_cast<short4 *>(hist + 4 * lane) = history_quad(xp, lane, HIST, in_len, M, plen);
 	wave_sync(); // xp is read out before the wave's next member stages over it
 }
+
 
 // One member's resampler at num : den (in : out, lowest terms) in mi_resampler's GENERIC order: resample_generic_kernel's
 // arithmetic (resample.hip) with a direct table.  History ++ tick staged as floats; output k is ONE __builtin_fmaf chain from
@@ -651,7 +580,7 @@ __device__ __forceinline__ void resample_in(const Conf &k, const RatedArgs &ra, 
 			continue;
 		int16_t *row = reinterpret_cast<int16_t *>(k.rows + m * k.row_w), *hist = ra.hist_in + (size_t)(k.s0 + m) * hin;
 		if (FORMS >= F_ABOVE && (r & UD_ABOVE))
-			resample_down<ON_ROW>(scr, row, hist, ra.tab + ua->tab_down_in[n], n, ns * n, updown_plen(n, ns * n), lane, reinterpret_cast<uint8_t *>(row), 0);
+			resample_down<ON_ROW>(scr, row, hist, ra.tab + ua->tab_down_in[n], n, ns * n, rs_plen_odd(RS_FILT, n, ns * n), lane, reinterpret_cast<uint8_t *>(row), 0);
 		else rated_up(scr, row, hist, ra.tab + ra.tab_up[n], n, ns / n, lane);
 	}
 	if (FORMS < F_R32) return;
@@ -690,7 +619,7 @@ __device__ __forceinline__ void resample_out(const Conf &k, const RatedArgs &ra,
 			rated_up(scr, row, hist, ra.tab + ua->tab_up_out[n], n, ns, lane);
 			store_row(row, out + at, kind, ns * n, lane);
 		} else {
-			resample_down<OUT>(scr, row, hist, ra.tab + ra.tab_down[n], n, ns, rated_plen(n, ns), lane, out, at, kind);
+			resample_down<OUT>(scr, row, hist, ra.tab + ra.tab_down[n], n, ns, rs_plen(RS_FILT, n, ns), lane, out, at, kind);
 		}
 	}
 	if (FORMS < F_R32) return;

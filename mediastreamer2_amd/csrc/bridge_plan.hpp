@@ -22,24 +22,15 @@ int mi_plc_check_rate(const char *fn, const char *what, int index, int rate);
 namespace {
 
 constexpr int BT = 256, BMAX = MI_MIXER_MAX_CHANNELS;
-constexpr int RS_FILT = 48, RS_R = 8; // quality 3: 48 taps per polyphase row, fir_tile's eight positions
-constexpr int RQ_FT = 24;             // taps per lane of the rational resamplers: filt_len / M, 48 / 2 and 72 / 3
 constexpr size_t BRIDGE_LDS_MAX = 64 * 1024;
 constexpr size_t RATED_STATIC_LDS = 2048; // bound on a kernel's static LDS (tests/test_bridge_rates_cpu.py holds it)
 
-// ---- the resamplers' lengths, one wavefront running one member's.  floats per phase array of a down-sampler (history ++ tick
-// split by input phase, + the tile FIR's look-ahead): rated_plen behind a pin; updown_plen, the same with plen / 4 odd, in
-// FRONT of one.  Lane l of the tile FIR reads 16 bytes at phase (l % num) * plen + 8 * (l / num): the tiles fall on the even
-// 16-byte slots of the 256-byte bank row, an odd plen / 4 puts the neighbouring phase on the odd ones (an even one -- 144,
-// 224 -- stacks the phases on one slot).  The two stay apart: they decide the LDS bank placement of each form and the scratch
-// plan_bridge budgets for it.
-MI_PLAN_HD inline int rated_plen(int num, int in_len) { return ((num * RS_FILT - 1 + in_len + num - 1) / num + RS_R + 8 + 3) & ~3; }
-MI_PLAN_HD inline int updown_plen(int num, int in_len) { return rated_plen(num, in_len) | 4; }
-// of a rational resampler: resample_ratio_kernel's length with plen / 4 odd, as updown_plen and for its reason: lanes
-// (tile, r) and (tile, r + 1) read neighbouring arrays at one offset
-MI_PLAN_HD inline int rational_plen(int m, int in_len) { return (((RQ_FT * m - 1 + in_len + m - 1) / m + RS_R + 8 + 3) & ~3) | 4; }
-// bytes of a wavefront's scratch for it: two copies of M phase arrays
-MI_PLAN_HD inline size_t rational_scratch(int m, int in_len) { return (size_t)2 * m * rational_plen(m, in_len) * sizeof(float); }
+// ---- the resamplers' constants and lengths, one wavefront running one member's (under hipcc: their steps as well).  A
+// down-sampler's phase arrays are rs_plen(RS_FILT, num, ..) floats behind a pin and rs_plen_odd in FRONT of one; a rational
+// resampler's rs_plen_odd(RQ_FT, M, ..): lanes (tile, r) and (tile, r + 1) read neighbouring arrays at one offset.
+#include "resample_steps.hpp"
+// bytes of a wavefront's scratch for a rational resampler: two copies of M phase arrays
+MI_PLAN_HD inline size_t rational_scratch(int m, int in_len) { return (size_t)2 * m * rs_plen_odd(RQ_FT, m, in_len) * sizeof(float); }
 
 // of a resampler in mi_resampler's generic order (generic_run, bridge_phases.hpp): history ++ tick as floats, then the `den`
 // polyphase rows of `filt` taps at a pitch of filt + 1 floats -- the filters are 48 .. 128 taps, multiples of 8, and rows at
@@ -237,12 +228,12 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 			// mix (in front of the pin, behind it), down-sampler and up-sampler of a leg above it
 			size_t up = 0, down = 0;
 			if (p->used[r]) {
-				up = (size_t)((RS_FILT - 1 + len / r + RS_R + 1 + 3) & ~3) * 4;
-				down = ((size_t)r * rated_plen(r, len) + (size_t)len) * 4;
+				up = (size_t)rs_flat_len(len / r) * 4;
+				down = ((size_t)r * rs_plen(RS_FILT, r, len) + (size_t)len) * 4;
 			}
 			if (p->above[r]) {
-				up = std::max(up, (size_t)((RS_FILT - 1 + len + RS_R + 1 + 3) & ~3) * 4);
-				down = std::max(down, ((size_t)r * updown_plen(r, r * len) + (size_t)r * len) * 4);
+				up = std::max(up, (size_t)rs_flat_len(len) * 4);
+				down = std::max(down, ((size_t)r * rs_plen_odd(RS_FILT, r, r * len) + (size_t)r * len) * 4);
 			}
 			scratch = std::max(scratch, up16(std::max(up, down)));
 		}

@@ -14,14 +14,15 @@
 //       Each lane owns one polyphase row (FILT taps in VGPRs) and R consecutive
 //       input positions; the FILT-1+R sample window comes out of LDS with
 //       16-byte reads; outputs are staged in LDS and leave as 16-byte stores.
-//   resample_down_kernel<NUM,48,8>  integer down-sampling (den_rate == 1, e.g.
-//       48k->16k, 48k->8k, 16k->8k): the input is split by phase while it is
-//       staged and each lane (tile, phase) runs the same 48-tap tile FIR on its
-//       phase; the NUM shares of an output meet in LDS.
-//   resample_ratio_kernel<L,M,24,8> L/M = 3/2 or 2/3 (32k<->48k, 16k<->24k, ...):
-//       M input phases x L output residues, the same tile FIR with 24 taps.
+//   resample_split_kernel<L,M,FT,R> L outputs per M inputs.  <1,NUM,48,8>: integer
+//       down-sampling (den_rate == 1, e.g. 48k->16k, 48k->8k, 16k->8k); <3,2,24,8>
+//       and <2,3,24,8>: 32k<->48k, 16k<->24k, ...  The input is split into M phases
+//       while it is staged and each lane (tile, output residue, phase) runs the
+//       same tile FIR on its phase; the M shares of an output meet in LDS.
 //   resample_generic_kernel         any other ratio (direct table or the
 //       oversampled table + 4-point cubic interpolation), one block per stream.
+// The three tile kernels are compositions of the steps of resample_steps.hpp, as the
+// bridge's one-member-per-wave resamplers are (bridge_phases.hpp).
 //
 // HBM traffic per stream-tick (16k->48k): 320 B in + 960 B out (+ 96 B history
 // read + 96 B written).
@@ -144,18 +145,19 @@ bool design_filter(uint32_t in_rate, uint32_t out_rate, int quality, Design &d) 
 }
 
 // ------------------------------------------------------------------- kernels
-#include "resample_tile.hpp"
+#include "resample_steps.hpp"
 
-
-struct UpArgs {
+// what the persistent kernels take: one wavefront per stream, each with its own slice of the dynamic LDS
+struct RsArgs {
 	const int16_t *in;
 	int16_t *out;
 	int32_t *out_len;
 	int16_t *hist;
-	const float *table;
+	const float *table; // the resampler's own: polyphase rows [den][filt_len]
 	const uint8_t *run;
 	int in_len, in_stride, out_stride, hist_stride, nstreams;
-	int tiles; // ceil(in_len / R)
+	int tiles; // of R positions: ceil(in_len / R) going up, ceil(periods / R) in the split kernel
+	int plen;  // split kernel: floats per phase array (rs_plen)
 	int lds_per_wave;
 };
 
@@ -171,7 +173,8 @@ constexpr int UP_WAVES = 4; // most wavefronts per workgroup of the one-wave-per
 inline int waves_per_workgroup(int nstreams) { return nstreams <= 16384 ? UP_WAVES : 2; }
 
 template <int DEN, int FILT, int R, bool MULTI, bool TWO>
-__global__ __launch_bounds__(64 * UP_WAVES, 2) void resample_up_kernel(UpArgs a) {
+__global__ __launch_bounds__(64 * UP_WAVES, 2) void resample_up_kernel(RsArgs a) {
+	static_assert(FILT == RS_FILT && R == RS_R, "rs_flat_len is the window of these");
 	extern __shared__ __attribute__((aligned(16))) char smem_all[];
 	// Two or four independent wavefronts share a workgroup only to cut the number of workgroups the dispatcher has to
 	// place (0.4 us, then another 0.25 us, of a 6.6 us launch at 4096 streams); each has its own LDS slice and never
@@ -181,8 +184,8 @@ __global__ __launch_bounds__(64 * UP_WAVES, 2) void resample_up_kernel(UpArgs a)
 	constexpr int HIST = FILT - 1;
 	const int lane = threadIdx.x & 63;
 	const int out_per_stream = a.in_len * DEN;
-	const int xn = ((HIST + a.in_len + R + 1) + 3) & ~3;
-	float *x = reinterpret_cast<float *>(smem);                         // [xn] history ++ input ++ zero slack
+	const int xn = rs_flat_len(a.in_len);
+	float *x = reinterpret_cast<float *>(smem);                         // [xn] history ++ input ++ zero slack: one phase
 	int16_t *obuf = reinterpret_cast<int16_t *>(smem + (size_t)xn * 4); // [out_per_stream]
 
 	// ---- staging plan: quads [0, hq) are history, [hq, hq+iq) input; lane takes quads lane and lane+64
@@ -209,39 +212,19 @@ __global__ __launch_bounds__(64 * UP_WAVES, 2) void resample_up_kernel(UpArgs a)
 	const int nlanes = DEN * a.tiles;
 	float4 *tab4 = reinterpret_cast<float4 *>(smem + (size_t)xn * 4 + (size_t)((out_per_stream + 7) & ~7) * 2);
 	for (int i = lane; i < DEN * FILT / 4; i += 64) tab4[i] = reinterpret_cast<const float4 *>(a.table)[i];
-	f2 t2[FILT / 2]; // taps as register pairs: v_pk_fma_f32 broadcasts either half through op_sel
-	auto load_row = [&](int p) {
-		const float4 *tp = tab4 + p * (FILT / 4);
-#pragma unroll
-		for (int j = 0; j < FILT / 4; ++j) {
-			const float4 v = tp[j];
-			t2[2 * j] = (f2){v.x, v.y}, t2[2 * j + 1] = (f2){v.z, v.w};
-		}
-	};
+	const float *tab = reinterpret_cast<const float *>(tab4);
+	f2 t2[FILT / 2];
 	for (int i = HIST + a.in_len + lane; i < xn; i += 64) x[i] = 0.f; // slack stays zero for every stream
 	wave_sync(); // single wave: LDS fence, the table is in place
 	if (!MULTI) {
 		const int l0 = lane < nlanes ? lane : 0;
-		load_row(l0 - (l0 / DEN) * DEN);
+		load_taps<FILT>(tab + (l0 - (l0 / DEN) * DEN) * FILT, t2);
 	}
 
 	for (; s < a.nstreams; s += nwaves) {
 		// ---- the prefetched row goes to LDS as float
-		if (lane < nq) {
-			const int b = 4 * lane - (lane < hq ? 0 : 4 * hq - HIST);
-			if (lane < hq) {
-				if (b + 0 < HIST) x[b + 0] = (float)v0.x;
-				if (b + 1 < HIST) x[b + 1] = (float)v0.y;
-				if (b + 2 < HIST) x[b + 2] = (float)v0.z;
-				if (b + 3 < HIST) x[b + 3] = (float)v0.w;
-			} else {
-				x[b + 0] = (float)v0.x, x[b + 1] = (float)v0.y, x[b + 2] = (float)v0.z, x[b + 3] = (float)v0.w;
-			}
-		}
-		if (two && lane + 64 < nq) {
-			const int b = HIST + 4 * (lane + 64 - hq);
-			x[b + 0] = (float)v1.x, x[b + 1] = (float)v1.y, x[b + 2] = (float)v1.z, x[b + 3] = (float)v1.w;
-		}
+		if (lane < nq) scatter_quad<1>(x, v0, lane, hq, HIST, 1, 0);
+		if (two && lane + 64 < nq) scatter_quad<1>(x, v1, lane + 64, hq, HIST, 1, 0);
 		const int cur_run = runv;
 		// ---- next stream's row: in flight during this stream's arithmetic
 		const int sn = s + nwaves;
@@ -260,12 +243,10 @@ __global__ __launch_bounds__(64 * UP_WAVES, 2) void resample_up_kernel(UpArgs a)
 			const bool on = l < nlanes;
 			const int tile = on ? l / DEN : 0, p = on ? l - tile * DEN : 0;
 			const int m0 = tile * R;
-			if (MULTI) load_row(p); // several trips: the phase pattern shifts by 64 % DEN
+			if (MULTI) load_taps<FILT>(tab + p * FILT, t2); // several trips: the phase pattern shifts by 64 % DEN
 			wave_sync(); // single wave: LDS fence between staging and the window reads
 			f2 acc2[R / 2];
-#pragma unroll
-			for (int q = 0; q < R / 2; ++q) acc2[q] = (f2){0.f, 0.f};
-			fir_tile<FILT, R>(x + m0, t2, acc2);
+			fir_share<FILT>(x + m0, t2, acc2);
 			float acc[R];
 #pragma unroll
 			for (int q = 0; q < R / 2; ++q) acc[2 * q] = acc2[q].x, acc[2 * q + 1] = acc2[q].y;
@@ -280,7 +261,8 @@ __global__ __launch_bounds__(64 * UP_WAVES, 2) void resample_up_kernel(UpArgs a)
 		int16_t *o = a.out + (size_t)s * a.out_stride;
 		for (int q = lane; q < (out_per_stream >> 3); q += 64)
 			*reinterpret_cast<uint4 *>(o + 8 * q) = *reinterpret_cast<const uint4 *>(obuf + 8 * q);
-		// ---- new history = last FILT-1 samples of (history ++ input); the pad slot takes the zero slack
+		// ---- new history = last FILT-1 samples of (history ++ input); the pad slot takes the zero slack (history_quad's
+		// arithmetic without its select: profiles/resample_steps.md, exceptions)
 		if (lane < hq) {
 			const float *hx = x + a.in_len + 4 * lane;
 			short4 h;
@@ -292,57 +274,40 @@ __global__ __launch_bounds__(64 * UP_WAVES, 2) void resample_up_kernel(UpArgs a)
 	}
 }
 
-// Integer down-sampling (den == 1, e.g. 48k->16k, 48k->8k, 16k->8k): out[k] = sum_j T[j] * X[NUM*k + j] with
-// FILT*NUM taps, X = history ++ input.  Split by input phase, X_p[m] = X[NUM*m + p], it is NUM stride-1 FIRs of FILT
-// taps each, out[k] = sum_p sum_i T[NUM*i + p] * X_p[k + i] -- the up-sampler's tile FIR with the roles of the phases
-// turned around: lane (tile, phase) computes phase p's share of R = 8 consecutive outputs, the NUM shares meet in LDS.
-// One wavefront per stream (persistent, UP_WAVES per workgroup), input de-interleaved by phase while it is staged.
-// Accumulation is phase-major (the library runs j upward): within 1 LSB of it, like the FMA contraction already is.
-struct DownArgs {
-	const int16_t *in;
-	int16_t *out;
-	int32_t *out_len;
-	int16_t *hist;
-	const float *table; // natural order, FILT*NUM taps
-	const uint8_t *run;
-	int in_len, in_stride, out_stride, hist_stride, nstreams;
-	int tiles;  // ceil(out_len / R)
-	int plen;   // floats per phase array (multiple of 4)
-	int lds_per_wave;
-};
-
-template <int NUM, int FILT, int R>
-__global__ __launch_bounds__(64 * UP_WAVES, 2) void resample_down_kernel(DownArgs a) {
+// Every direct table that is no integer up-sampler: L outputs per M inputs, L / M = 1 / NUM (den == 1: 48k->16k, 48k->8k,
+// 16k->8k, FT = 48) or 3/2 and 2/3 (32k<->48k, 16k<->24k, 8k<->12k, FT = 24 = filt_len / M).  Output n = q*L + r reads table
+// row ph_r = (r*M) % L at input position q*M + off_r, off_r = (r*M) / L: for a fixed residue r consecutive q shift the window
+// by M samples, so the input is split into M phases X_p[m] = X[m*M + p] while it is staged, and tap j = i*M + p' of row ph_r
+// meets X_{u % M}[q + i + u / M], u = off_r + p' -- M stride-1 FIRs of FT taps, the up-sampler's tile FIR with the roles of
+// the phases turned around.  Lane (tile, r, p') computes that share of 8 consecutive q; the M shares of an output meet in
+// LDS.  u / M is 0 or 1 and a window must start on a 16-byte boundary, so with L > 1 every phase array is staged twice, the
+// second copy one float early; L = 1 has u = p' and the one copy.  One wavefront per stream (persistent, UP_WAVES per
+// workgroup).  Accumulation is phase-major (the library runs j upward): within 1 LSB of it, like the FMA contraction is.
+template <int L, int M, int FT, int R>
+__global__ __launch_bounds__(64 * UP_WAVES, 2) void resample_split_kernel(RsArgs a) {
+	static_assert(R == RS_R && (L - 1) * M / L + M - 1 < 2 * M, "u / M is 0 or 1: at most two copies of the phase arrays");
 	extern __shared__ __attribute__((aligned(16))) char smem_all[];
 	char *smem = smem_all + (size_t)(threadIdx.x >> 6) * a.lds_per_wave;
-	constexpr int NT = NUM * FILT, HIST = NT - 1;
+	constexpr int NT = FT * M, HIST = NT - 1, ROWS = L * M, COPIES = L > 1 ? 2 : 1;
 	const int lane = threadIdx.x & 63;
-	const int out_len = a.in_len / NUM;
-	float *xp = reinterpret_cast<float *>(smem);                       // [NUM][plen] phase arrays of history ++ input
-	float *part = xp + (size_t)NUM * a.plen;                           // [tiles*R][NUM] partial sums
-	float4 *tab4 = reinterpret_cast<float4 *>(part + (size_t)a.tiles * R * NUM); // [NUM][FILT] taps, phase-major
-	{
-		float *tab = reinterpret_cast<float *>(tab4);
-		for (int i = lane; i < NT; i += 64) tab[(i % NUM) * FILT + i / NUM] = a.table[i];
+	const int periods = a.in_len / M, out_len = periods * L;
+	float *xp = reinterpret_cast<float *>(smem);   // [COPIES][M][plen]: copy c holds X_p[m] at index m - c
+	float *part = xp + (size_t)COPIES * M * a.plen; // [tiles*R][L][M] partial sums
+	float *tab = part + (size_t)a.tiles * R * ROWS; // [L*M][FT] taps per (r, p')
+	for (int i = lane; i < ROWS * FT; i += 64) {
+		const int row = i / FT, k = i - row * FT, r = row / M, pp = row - r * M;
+		tab[i] = a.table[((r * M) % L) * NT + k * M + pp];
 	}
 	// zero the tails of the phase arrays once (slack the window reads may touch)
-	for (int i = lane; i < NUM * a.plen; i += 64) xp[i] = 0.f;
+	for (int i = lane; i < COPIES * M * a.plen; i += 64) xp[i] = 0.f;
 	wave_sync();
 	const int hq = a.hist_stride >> 2, nq = hq + (a.in_len >> 2);
-	const int nlanes = NUM * a.tiles;
+	const int nlanes = ROWS * a.tiles;
 	const int nwaves = gridDim.x * (blockDim.x >> 6);
-	f2 t2[FILT / 2];
-	auto load_row = [&](int p) {
-		const float4 *tp = tab4 + p * (FILT / 4);
-#pragma unroll
-		for (int j = 0; j < FILT / 4; ++j) {
-			const float4 v = tp[j];
-			t2[2 * j] = (f2){v.x, v.y}, t2[2 * j + 1] = (f2){v.z, v.w};
-		}
-	};
-	if (nlanes <= 64) {
+	f2 t2[FT / 2];
+	if (nlanes <= 64) { // one trip covers all lanes: the tap row is loaded once per wave
 		const int l0 = lane < nlanes ? lane : 0;
-		load_row(l0 - (l0 / NUM) * NUM);
+		load_taps<FT>(tab + (l0 - (l0 / ROWS) * ROWS) * FT, t2);
 	}
 	for (int s = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); s < a.nstreams; s += nwaves) {
 		if (a.run && !a.run[s]) {
@@ -359,162 +324,18 @@ __global__ __launch_bounds__(64 * UP_WAVES, 2) void resample_down_kernel(DownArg
 			if (q < nq) v[u] = *reinterpret_cast<const short4 *>(q < hq ? hs + 4 * q : xin + 4 * (q - hq));
 		}
 #pragma unroll
-		for (int u = 0; u < 3; ++u) {
-			const int q = lane + 64 * u;
-			if (q < nq) {
-				const int b = q < hq ? 4 * q : HIST + 4 * (q - hq); // index in history ++ input
-				const short e[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-				for (int k = 0; k < 4; ++k) {
-					const int i = b + k;
-					if (q >= hq || i < HIST) xp[(i % NUM) * a.plen + i / NUM] = (float)e[k];
-				}
-			}
-		}
-		for (int base = 0; base < nlanes; base += 64) {
-			const int l = base + lane;
-			const bool on = l < nlanes;
-			const int tile = on ? l / NUM : 0, p = on ? l - tile * NUM : 0;
-			if (nlanes > 64) load_row(p);
-			wave_sync();
-			f2 acc2[R / 2];
-#pragma unroll
-			for (int q = 0; q < R / 2; ++q) acc2[q] = (f2){0.f, 0.f};
-			fir_tile<FILT, R>(xp + (size_t)p * a.plen + tile * R, t2, acc2);
-			if (on) {
-				float *d = part + ((size_t)tile * R) * NUM + p;
-#pragma unroll
-				for (int q = 0; q < R / 2; ++q) d[(2 * q) * NUM] = acc2[q].x, d[(2 * q + 1) * NUM] = acc2[q].y;
-			}
-		}
-		wave_sync();
-		// ---- the NUM shares of each output meet, 8 outputs = one 16-byte store per lane
-		int16_t *o = a.out + (size_t)s * a.out_stride;
-		for (int g = lane; g < (out_len >> 3); g += 64) {
-			const float *ps = part + (size_t)g * 8 * NUM;
-			short r16[8];
-#pragma unroll
-			for (int k = 0; k < 8; ++k) {
-				float sum = 0.f;
-#pragma unroll
-				for (int p = 0; p < NUM; ++p) sum += ps[k * NUM + p];
-				r16[k] = rs_word2int(sum);
-			}
-			uint4 pk;
-			pk.x = (unsigned)(r16[0] & 0xffff) | ((unsigned)r16[1] << 16);
-			pk.y = (unsigned)(r16[2] & 0xffff) | ((unsigned)r16[3] << 16);
-			pk.z = (unsigned)(r16[4] & 0xffff) | ((unsigned)r16[5] << 16);
-			pk.w = (unsigned)(r16[6] & 0xffff) | ((unsigned)r16[7] << 16);
-			*reinterpret_cast<uint4 *>(o + 8 * g) = pk;
-		}
-		// ---- new history = last HIST samples of (history ++ input); the pad slot of the row takes a zero
-		for (int q = lane; q < hq; q += 64) {
-			short4 h;
-			short *hp = &h.x;
-#pragma unroll
-			for (int k = 0; k < 4; ++k) {
-				const int i = a.in_len + 4 * q + k;
-				hp[k] = (4 * q + k < HIST) ? (short)xp[(i % NUM) * a.plen + i / NUM] : (short)0;
-			}
-			*reinterpret_cast<short4 *>(a.hist + (size_t)s * a.hist_stride + 4 * q) = h;
-		}
-		if (lane == 0 && a.out_len) a.out_len[s] = out_len;
-		wave_sync(); // LDS reads above complete before the next stream is staged
-	}
-}
-
-// Rational ratios L/M with a direct table (32k<->48k, 16k<->24k, 8k<->12k: L/M = 3/2 or 2/3).  Output n = q*L + r reads
-// table row ph_r = (r*M) % L at input position q*M + off_r, off_r = (r*M) / L: for a fixed residue r consecutive q shift
-// the window by M samples, so -- as in the down-sampler -- the input is split into M phases X_p[m] = X[m*M + p] and tap
-// j = i*M + p' of row ph_r meets X_{u % M}[q + i + u / M], u = off_r + p'.  Lane (tile, r, p') runs the shared tile FIR
-// with FT = filt_len / M taps over 8 consecutive q; u / M is 0 or 1, and a window must start on a 16-byte boundary, so
-// every phase array is staged twice, the second copy one float early.  The M shares of an output meet in LDS.
-struct RatioArgs {
-	const int16_t *in;
-	int16_t *out;
-	int32_t *out_len;
-	int16_t *hist;
-	const float *table; // [L][filt_len]
-	const uint8_t *run;
-	int in_len, in_stride, out_stride, hist_stride, nstreams;
-	int tiles; // ceil(periods / R), periods = in_len / M
-	int plen;  // floats per phase array copy (multiple of 4)
-	int lds_per_wave;
-};
-
-template <int L, int M, int FT, int R>
-__global__ __launch_bounds__(64 * UP_WAVES, 2) void resample_ratio_kernel(RatioArgs a) {
-	extern __shared__ __attribute__((aligned(16))) char smem_all[];
-	char *smem = smem_all + (size_t)(threadIdx.x >> 6) * a.lds_per_wave;
-	constexpr int NT = FT * M, HIST = NT - 1, ROWS = L * M;
-	const int lane = threadIdx.x & 63;
-	const int periods = a.in_len / M, out_len = periods * L;
-	float *xp = reinterpret_cast<float *>(smem);                // [2][M][plen]: copy c holds X_p[m] at index m + c
-	float *part = xp + (size_t)2 * M * a.plen;                  // [tiles*R][L][M] partial sums
-	float4 *tab4 = reinterpret_cast<float4 *>(part + (size_t)a.tiles * R * ROWS); // [L*M][FT] taps per (r, p')
-	{
-		float *tab = reinterpret_cast<float *>(tab4);
-		for (int i = lane; i < ROWS * FT; i += 64) {
-			const int row = i / FT, k = i - row * FT, r = row / M, pp = row - r * M;
-			tab[i] = a.table[((r * M) % L) * NT + k * M + pp];
-		}
-	}
-	for (int i = lane; i < 2 * M * a.plen; i += 64) xp[i] = 0.f;
-	wave_sync();
-	const int hq = a.hist_stride >> 2, nq = hq + (a.in_len >> 2);
-	const int nlanes = ROWS * a.tiles;
-	const int nwaves = gridDim.x * (blockDim.x >> 6);
-	f2 t2[FT / 2];
-	for (int s = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); s < a.nstreams; s += nwaves) {
-		if (a.run && !a.run[s]) {
-			if (lane == 0 && a.out_len) a.out_len[s] = 0;
-			continue;
-		}
-		const int16_t *hs = a.hist + (size_t)s * a.hist_stride, *xin = a.in + (size_t)s * a.in_stride;
-		short4 v[3];
-#pragma unroll
-		for (int u = 0; u < 3; ++u) {
-			const int q = lane + 64 * u;
-			v[u] = make_short4(0, 0, 0, 0);
-			if (q < nq) v[u] = *reinterpret_cast<const short4 *>(q < hq ? hs + 4 * q : xin + 4 * (q - hq));
-		}
-#pragma unroll
-		for (int u = 0; u < 3; ++u) {
-			const int q = lane + 64 * u;
-			if (q < nq) {
-				const int b = q < hq ? 4 * q : HIST + 4 * (q - hq);
-				const short e[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-				for (int k = 0; k < 4; ++k) {
-					const int i = b + k;
-					if (q >= hq || i < HIST) {
-						const int ph = i % M, m = i / M;
-						const float f = (float)e[k];
-						xp[ph * a.plen + m] = f;                       // copy 0
-						if (m >= 1) xp[(M + ph) * a.plen + m - 1] = f; // copy 1: X_p[m] at m - 1, i.e. window start + 1
-					}
-				}
-			}
-		}
+		for (int u = 0; u < 3; ++u)
+			if (lane + 64 * u < nq) scatter_quad<COPIES>(xp, v[u], lane + 64 * u, hq, HIST, M, a.plen);
 		for (int base = 0; base < nlanes; base += 64) {
 			const int l = base + lane;
 			const bool on = l < nlanes;
 			const int tile = on ? l / ROWS : 0, row = on ? l - tile * ROWS : 0;
 			const int r = row / M, pp = row - r * M;
-			const int u = (r * M) / L + pp; // off_r + p'
-			{
-				const float4 *tp = tab4 + row * (FT / 4);
-#pragma unroll
-				for (int j = 0; j < FT / 4; ++j) {
-					const float4 w = tp[j];
-					t2[2 * j] = (f2){w.x, w.y}, t2[2 * j + 1] = (f2){w.z, w.w};
-				}
-			}
+			const int u = (r * M) / L + pp; // off_r + p': copy u / M, phase u % M -- array u
+			if (nlanes > 64) load_taps<FT>(tab + row * FT, t2);
 			wave_sync();
 			f2 acc2[R / 2];
-#pragma unroll
-			for (int q = 0; q < R / 2; ++q) acc2[q] = (f2){0.f, 0.f};
-			fir_tile<FT, R>(xp + (size_t)((u / M) * M + (u % M)) * a.plen + tile * R, t2, acc2);
+			fir_share<FT>(xp + (size_t)u * a.plen + tile * R, t2, acc2);
 			if (on) {
 				float *d = part + ((size_t)tile * R) * ROWS + row;
 #pragma unroll
@@ -522,39 +343,21 @@ __global__ __launch_bounds__(64 * UP_WAVES, 2) void resample_ratio_kernel(RatioA
 			}
 		}
 		wave_sync();
-		// ---- output n = q*L + r = the sum over p' of part[q][r][p']: consecutive n are consecutive (q, r) pairs
+		// ---- output n = q*L + r = the sum over p' of part[q][r][p'], consecutive n are consecutive (q, r) pairs: the M shares
+		// of each output meet, 8 outputs = one 16-byte store per lane
 		int16_t *o = a.out + (size_t)s * a.out_stride;
 		for (int g = lane; g < (out_len >> 3); g += 64) {
-			const float *ps = part + (size_t)g * 8 * M;
-			short r16[8];
-#pragma unroll
-			for (int k = 0; k < 8; ++k) {
-				float sum = 0.f;
-#pragma unroll
-				for (int pq = 0; pq < M; ++pq) sum += ps[k * M + pq];
-				r16[k] = rs_word2int(sum);
-			}
-			uint4 pk;
-			pk.x = (unsigned)(r16[0] & 0xffff) | ((unsigned)r16[1] << 16);
-			pk.y = (unsigned)(r16[2] & 0xffff) | ((unsigned)r16[3] << 16);
-			pk.z = (unsigned)(r16[4] & 0xffff) | ((unsigned)r16[5] << 16);
-			pk.w = (unsigned)(r16[6] & 0xffff) | ((unsigned)r16[7] << 16);
-			*reinterpret_cast<uint4 *>(o + 8 * g) = pk;
+			int r8[8];
+			gather_group(part + (size_t)g * 8 * M, M, r8);
+			*reinterpret_cast<uint4 *>(o + 8 * g) = make_uint4(pack16(r8[0], r8[1]), pack16(r8[2], r8[3]), pack16(r8[4], r8[5]), pack16(r8[6], r8[7]));
 		}
-		for (int q = lane; q < hq; q += 64) {
-			short4 h;
-			short *hp = &h.x;
-#pragma unroll
-			for (int k = 0; k < 4; ++k) {
-				const int i = a.in_len + 4 * q + k;
-				hp[k] = (4 * q + k < HIST) ? (short)xp[(i % M) * a.plen + i / M] : (short)0;
-			}
-			*reinterpret_cast<short4 *>(a.hist + (size_t)s * a.hist_stride + 4 * q) = h;
-		}
+		for (int q = lane; q < hq; q += 64)
+			*reinterpret_cast<short4 *>(a.hist + (size_t)s * a.hist_stride + 4 * q) = history_quad(xp, q, HIST, a.in_len, M, a.plen);
 		if (lane == 0 && a.out_len) a.out_len[s] = out_len;
-		wave_sync();
+		wave_sync(); // LDS reads above complete before the next stream is staged
 	}
 }
+
 
 struct GenArgs {
 	const int16_t *in;
@@ -680,130 +483,55 @@ void mi_resampler_view(mi_resampler *r, ResamplerView *v) {
 	v->ok = r->d.num == 1 && r->d.den > 1 && r->dev_direct() && r->d.phase_table.empty() && r->d.filt_len == 48 && r->phase_zero;
 }
 
+// 8-byte row loads, at most max_quads / 64 per lane, and 16-byte output stores; any other layout takes the generic kernel
+static bool tile_layout(const RsArgs &a, int out_len, int max_quads) {
+	const int nq = (a.hist_stride >> 2) + (a.in_len >> 2);
+	return ((a.in_len | a.in_stride) & 3) == 0 && nq <= max_quads && ((out_len | a.out_stride) & 7) == 0 &&
+	       (reinterpret_cast<uintptr_t>(a.in) & 7) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
+}
+
+// persistent waves: enough to fill every SIMD, each walking the same number of streams
+static int launch_waves(mi_resampler *r, void (*kernel)(RsArgs), RsArgs a, size_t lds, int waves_per_cu) {
+	const int max_waves = (r->ctx->cu_count > 0 ? r->ctx->cu_count : 256) * waves_per_cu;
+	const int per_wave = mi::ceil_div(r->nstreams, max_waves);
+	const int nwaves = mi::ceil_div(r->nstreams, per_wave);
+	const int wpw = waves_per_workgroup(r->nstreams);
+	a.lds_per_wave = (int)((lds + 15) & ~(size_t)15);
+	hipLaunchKernelGGL(kernel, dim3(mi::ceil_div(nwaves, wpw)), dim3(64 * wpw), (size_t)a.lds_per_wave * wpw, r->ctx->stream, a);
+	MI_LAUNCH_CHECK();
+	return MI_OK;
+}
+
+// a: the call's buffers and strides.  *done stays false where the layout is the generic kernel's
 template <int DEN, int FILT, int R>
-static int launch_up(mi_resampler *r, const int16_t *d_in, int in_len, int in_stride, int16_t *d_out,
-                     int out_stride, int32_t *d_out_len, const uint8_t *d_run, bool *done) {
-	*done = false;
-	const int tiles = mi::ceil_div(in_len, R);
-	const int xn = ((FILT - 1 + in_len + R + 1) + 3) & ~3;
-	const size_t lds = (size_t)xn * sizeof(float) + (size_t)((in_len * DEN + 7) & ~7) * sizeof(int16_t) +
+static int launch_up(mi_resampler *r, RsArgs a, bool *done) {
+	a.tiles = mi::ceil_div(a.in_len, R);
+	const size_t lds = (size_t)rs_flat_len(a.in_len) * sizeof(float) + (size_t)((a.in_len * DEN + 7) & ~7) * sizeof(int16_t) +
 	                   (size_t)DEN * FILT * sizeof(float); // window, output staging, polyphase table
-	const int nq = (r->hist_stride >> 2) + (in_len >> 2);
-	// 8-byte row loads (at most two per lane) and 16-byte output stores; any other layout takes the generic kernel
-	if (lds > 48 * 1024 || ((in_len | in_stride) & 3) != 0 || nq > 128 || (reinterpret_cast<uintptr_t>(d_in) & 7) != 0 ||
-	    (((in_len * DEN) | out_stride) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 15) != 0)
-		return MI_OK;
-	UpArgs a;
-	a.in = d_in;
-	a.out = d_out;
-	a.out_len = d_out_len;
-	a.hist = r->d_hist;
-	a.table = r->d_table;
-	a.run = d_run;
-	a.in_len = in_len;
-	a.in_stride = in_stride;
-	a.out_stride = out_stride;
-	a.hist_stride = r->hist_stride;
-	a.nstreams = r->nstreams;
-	a.tiles = tiles;
-	// persistent waves: enough to fill every SIMD, each walking the same number of streams
+	if (lds > 48 * 1024 || !tile_layout(a, a.in_len * DEN, 128)) return MI_OK;
 	static const int waves_per_cu = [] {
 		const char *e = getenv("MSMI355X_RESAMPLE_WAVES_PER_CU");
 		const int v = e ? atoi(e) : 0;
 		return v > 0 ? v : 16;
 	}();
-	const int max_waves = (r->ctx->cu_count > 0 ? r->ctx->cu_count : 256) * waves_per_cu;
-	const int per_wave = mi::ceil_div(r->nstreams, max_waves);
-	const int nwaves = mi::ceil_div(r->nstreams, per_wave);
-	const int wpw = waves_per_workgroup(r->nstreams);
-	const int grid = mi::ceil_div(nwaves, wpw);
-	a.lds_per_wave = (int)((lds + 15) & ~(size_t)15);
-	if (DEN * tiles <= 64 && nq <= 64)
-		hipLaunchKernelGGL((resample_up_kernel<DEN, FILT, R, false, false>), dim3(grid), dim3(64 * wpw),
-		                   (size_t)a.lds_per_wave * wpw, r->ctx->stream, a);
-	else
-		hipLaunchKernelGGL((resample_up_kernel<DEN, FILT, R, true, true>), dim3(grid), dim3(64 * wpw),
-		                   (size_t)a.lds_per_wave * wpw, r->ctx->stream, a);
-	MI_LAUNCH_CHECK();
+	const bool one_trip = DEN * a.tiles <= 64 && (a.hist_stride >> 2) + (a.in_len >> 2) <= 64;
 	*done = true;
-	return MI_OK;
+	return launch_waves(r, one_trip ? resample_up_kernel<DEN, FILT, R, false, false> : resample_up_kernel<DEN, FILT, R, true, true>, a, lds, waves_per_cu);
 }
 
-template <int NUM, int FILT, int R>
-static int launch_down(mi_resampler *r, const int16_t *d_in, int in_len, int in_stride, int16_t *d_out, int out_stride,
-                       int32_t *d_out_len, const uint8_t *d_run, bool *done) {
-	*done = false;
-	const int out_len = in_len / NUM;
-	const int nq = (r->hist_stride >> 2) + (in_len >> 2);
-	if ((in_len % NUM) != 0 || ((in_len | in_stride) & 3) != 0 || nq > 192 || ((out_len | out_stride) & 7) != 0 ||
-	    (reinterpret_cast<uintptr_t>(d_in) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 15) != 0 || !r->phase_zero)
-		return MI_OK; // the generic kernel takes every other layout (and any stream state off the phase grid)
-	DownArgs a;
-	a.in = d_in;
-	a.out = d_out;
-	a.out_len = d_out_len;
-	a.hist = r->d_hist;
-	a.table = r->d_table;
-	a.run = d_run;
-	a.in_len = in_len;
-	a.in_stride = in_stride;
-	a.out_stride = out_stride;
-	a.hist_stride = r->hist_stride;
-	a.nstreams = r->nstreams;
-	a.tiles = mi::ceil_div(out_len, R);
-	const int xlen = NUM * FILT - 1 + in_len;
-	a.plen = (mi::ceil_div(xlen, NUM) + R + 8 + 3) & ~3;
-	const size_t lds = ((size_t)NUM * a.plen + (size_t)a.tiles * R * NUM + (size_t)NUM * FILT) * sizeof(float);
-	if (lds > 30 * 1024) return MI_OK;
-	a.lds_per_wave = (int)((lds + 15) & ~(size_t)15);
-	const int max_waves = (r->ctx->cu_count > 0 ? r->ctx->cu_count : 256) * 16;
-	const int per_wave = mi::ceil_div(r->nstreams, max_waves);
-	const int nwaves = mi::ceil_div(r->nstreams, per_wave);
-	const int wpw = waves_per_workgroup(r->nstreams);
-	hipLaunchKernelGGL((resample_down_kernel<NUM, FILT, R>), dim3(mi::ceil_div(nwaves, wpw)), dim3(64 * wpw),
-	                   (size_t)a.lds_per_wave * wpw, r->ctx->stream, a);
-	MI_LAUNCH_CHECK();
-	*done = true;
-	return MI_OK;
-}
-
+// whole output periods only, and every stream's state on the phase grid: (last_sample, frac) == (0, 0)
 template <int L, int M, int FT, int R>
-static int launch_ratio(mi_resampler *r, const int16_t *d_in, int in_len, int in_stride, int16_t *d_out, int out_stride,
-                        int32_t *d_out_len, const uint8_t *d_run, bool *done) {
-	*done = false;
-	const int periods = in_len / M, out_len = periods * L;
-	const int nq = (r->hist_stride >> 2) + (in_len >> 2);
-	if ((in_len % M) != 0 || ((in_len | in_stride) & 3) != 0 || nq > 192 || ((out_len | out_stride) & 7) != 0 ||
-	    (reinterpret_cast<uintptr_t>(d_in) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 15) != 0 || !r->phase_zero)
-		return MI_OK;
-	RatioArgs a;
-	a.in = d_in;
-	a.out = d_out;
-	a.out_len = d_out_len;
-	a.hist = r->d_hist;
-	a.table = r->d_table;
-	a.run = d_run;
-	a.in_len = in_len;
-	a.in_stride = in_stride;
-	a.out_stride = out_stride;
-	a.hist_stride = r->hist_stride;
-	a.nstreams = r->nstreams;
+static int launch_split(mi_resampler *r, RsArgs a, bool *done) {
+	const int periods = a.in_len / M;
+	if ((a.in_len % M) != 0 || !tile_layout(a, periods * L, 192) || !r->phase_zero) return MI_OK;
 	a.tiles = mi::ceil_div(periods, R);
-	const int xlen = FT * M - 1 + in_len;
-	a.plen = (mi::ceil_div(xlen, M) + R + 8 + 3) & ~3;
-	const size_t lds = ((size_t)2 * M * a.plen + (size_t)a.tiles * R * L * M + (size_t)L * M * FT) * sizeof(float);
+	a.plen = rs_plen(FT, M, a.in_len);
+	const size_t lds = ((size_t)(L > 1 ? 2 : 1) * M * a.plen + (size_t)a.tiles * R * L * M + (size_t)L * M * FT) * sizeof(float);
 	if (lds > 30 * 1024) return MI_OK;
-	a.lds_per_wave = (int)((lds + 15) & ~(size_t)15);
-	const int max_waves = (r->ctx->cu_count > 0 ? r->ctx->cu_count : 256) * 16;
-	const int per_wave = mi::ceil_div(r->nstreams, max_waves);
-	const int nwaves = mi::ceil_div(r->nstreams, per_wave);
-	const int wpw = waves_per_workgroup(r->nstreams);
-	hipLaunchKernelGGL((resample_ratio_kernel<L, M, FT, R>), dim3(mi::ceil_div(nwaves, wpw)), dim3(64 * wpw),
-	                   (size_t)a.lds_per_wave * wpw, r->ctx->stream, a);
-	MI_LAUNCH_CHECK();
 	*done = true;
-	return MI_OK;
+	return launch_waves(r, resample_split_kernel<L, M, FT, R>, a, lds, 16);
 }
+
 
 extern "C" {
 
@@ -973,44 +701,32 @@ int mi_resampler_process_masked(mi_resampler *r, const int16_t *d_in, int in_len
 	MI_CHECK_ARG(out_stride >= need);
 	if (r->ctx->activate() != MI_OK) return MI_ENODEV;
 
-	if (r->d.num == 1 && r->d.direct && r->d.filt_len == 48) {
-		bool done = false;
-		int rc = MI_OK;
-		switch (r->d.den) {
-			case 2: rc = launch_up<2, 48, 8>(r, d_in, in_len, in_stride, d_out, out_stride, d_out_len, d_run, &done); break;
-			case 3: rc = launch_up<3, 48, 8>(r, d_in, in_len, in_stride, d_out, out_stride, d_out_len, d_run, &done); break;
-			case 4: rc = launch_up<4, 48, 8>(r, d_in, in_len, in_stride, d_out, out_stride, d_out_len, d_run, &done); break;
-			case 6: rc = launch_up<6, 48, 8>(r, d_in, in_len, in_stride, d_out, out_stride, d_out_len, d_run, &done); break;
+	const int num = (int)r->d.num, den = (int)r->d.den, filt = (int)r->d.filt_len;
+	RsArgs t = {d_in, d_out, d_out_len, r->d_hist, r->d_table, d_run, in_len, in_stride, out_stride, r->hist_stride, r->nstreams, 0, 0, 0};
+	bool done = false;
+	int rc = MI_OK;
+	if (r->d.direct && num == 1 && filt == 48) {
+		switch (den) {
+			case 2: rc = launch_up<2, 48, 8>(r, t, &done); break;
+			case 3: rc = launch_up<3, 48, 8>(r, t, &done); break;
+			case 4: rc = launch_up<4, 48, 8>(r, t, &done); break;
+			case 6: rc = launch_up<6, 48, 8>(r, t, &done); break;
 			default: break;
 		}
-		if (rc != MI_OK) return rc;
-		if (done) return MI_OK;
-	}
-
-	if (r->d.den == 1 && r->d.direct && r->d.filt_len == 48 * r->d.num) {
-		bool done = false;
-		int rc = MI_OK;
-		switch (r->d.num) {
-			case 2: rc = launch_down<2, 48, 8>(r, d_in, in_len, in_stride, d_out, out_stride, d_out_len, d_run, &done); break;
-			case 3: rc = launch_down<3, 48, 8>(r, d_in, in_len, in_stride, d_out, out_stride, d_out_len, d_run, &done); break;
-			case 4: rc = launch_down<4, 48, 8>(r, d_in, in_len, in_stride, d_out, out_stride, d_out_len, d_run, &done); break;
-			case 6: rc = launch_down<6, 48, 8>(r, d_in, in_len, in_stride, d_out, out_stride, d_out_len, d_run, &done); break;
+	} else if (r->d.direct && ((den == 1 && filt == 48 * num) || (den == 3 && num == 2 && filt == 48) || (den == 2 && num == 3 && filt == 72))) {
+		switch (10 * num + den) { // in : out
+			case 21: rc = launch_split<1, 2, 48, 8>(r, t, &done); break;
+			case 31: rc = launch_split<1, 3, 48, 8>(r, t, &done); break;
+			case 41: rc = launch_split<1, 4, 48, 8>(r, t, &done); break;
+			case 61: rc = launch_split<1, 6, 48, 8>(r, t, &done); break;
+			case 23: rc = launch_split<3, 2, 24, 8>(r, t, &done); break;
+			case 32: rc = launch_split<2, 3, 24, 8>(r, t, &done); break;
 			default: break;
 		}
-		if (rc != MI_OK) return rc;
-		if (done) return MI_OK;
 		// a block that is not a whole number of output periods leaves (last_sample, frac) off zero for good
-		if (in_len % (int)r->d.num) r->phase_zero = false;
+		if (rc == MI_OK && !done && in_len % num) r->phase_zero = false;
 	}
-
-	if (r->d.direct && ((r->d.den == 3 && r->d.num == 2 && r->d.filt_len == 48) || (r->d.den == 2 && r->d.num == 3 && r->d.filt_len == 72))) {
-		bool done = false;
-		const int rc = (r->d.den == 3) ? launch_ratio<3, 2, 24, 8>(r, d_in, in_len, in_stride, d_out, out_stride, d_out_len, d_run, &done)
-		                               : launch_ratio<2, 3, 24, 8>(r, d_in, in_len, in_stride, d_out, out_stride, d_out_len, d_run, &done);
-		if (rc != MI_OK) return rc;
-		if (done) return MI_OK;
-		if (in_len % (int)r->d.num) r->phase_zero = false;
-	}
+	if (rc != MI_OK || done) return rc;
 
 	GenArgs a;
 	a.in = d_in;

@@ -6,7 +6,7 @@ The yardstick is tests/bridge_parts.py's Parts on the C ABI -- mi_g711_decode on
 mi_volume_process (a batch per leg rate) -> mi_resampler_process_masked (leg -> conference) -> mi_mixer_process ->
 mi_resampler_process_masked (conference -> leg) -> mi_g711_encode once per law -- and every comparison with it is BIT-EXACT
 over all legs, samples and ticks: output bytes, mi_volume_state bytes, meter maxima.  Every shape here lies where
-mi_resampler runs its tile kernel for 3/2 and 2/3 (launch_ratio, csrc/resample.hip: input ticks of at most 696 samples and
+mi_resampler runs its tile kernel for 3/2 and 2/3 (launch_split, csrc/resample.hip: input ticks of at most 696 samples and
 at most 30 KB of LDS; the widest input here is 480 samples) -- past that it takes its generic kernel, whose sums run in
 another order.  Against the oracle chain the meters are bit-exact and the audio is held to the float resampler path's
 tolerance (tests/test_gpu_resample.py): 1e-4 RMS of full scale and at most 1 LSB."""
@@ -57,7 +57,7 @@ def test_equal_to_the_parts(ctx, mk, case, mm):
     with an input gain != 1, pin 3 with a gain; pin 0 (a 3/2 or 2/3 leg) without MI_MIX_OUTPUT for the first half and the
     same pin of the second conference for the second half, a seeded fifth of the legs absent per tick: the histories of
     absent and output-less pins must have stayed as they were for the later ticks to match.  All these shapes lie where
-    mi_resampler runs its tile kernel for 3/2 and 2/3 (launch_ratio: input ticks <= 696 samples, LDS <= 30 KB)."""
+    mi_resampler runs its tile kernel for 3/2 and 2/3 (launch_split: input ticks <= 696 samples, LDS <= 30 KB)."""
     n, nticks = 2 * mm, 12
     conf, legs = _legs(case, mm)
     br = mk(ms.Bridge, n, members=mm, rate=conf, rational=legs)

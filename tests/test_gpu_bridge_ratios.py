@@ -6,7 +6,7 @@ csrc/bridge_ratios.hip), next to legs at 1, 2, 3, 6 and 3/2 below and above.
 The yardstick is tests/bridge_parts.py's Parts on the C ABI -- mi_g711_decode once per law -> mi_volume_process (a batch per
 leg rate) -> mi_resampler_process_masked (leg -> conference) -> mi_mixer_process -> mi_resampler_process_masked (conference
 -> leg) -> mi_g711_encode once per law -- and every comparison with it is BIT-EXACT over all legs, samples and ticks: output
-bytes, mi_volume_state bytes, meter maxima.  The ratio-4 shapes lie where mi_resampler runs its tile kernel (launch_down,
+bytes, mi_volume_state bytes, meter maxima.  The ratio-4 shapes lie where mi_resampler runs its tile kernel (launch_split,
 csrc/resample.hip: nq <= 192, ticks of at most 576 samples on the wider side; the widest here is 480); for a : b
 mi_resampler has one form, resample_generic_kernel, at every shape.  Against the oracle chain the meters are bit-exact and
 the audio is held to the float resampler path's bar (tests/test_gpu_resample.py): 1e-4 RMS of full scale and at most 1 LSB."""
