@@ -269,7 +269,7 @@ int mi_bridge_remove_member(mi_bridge *b, int stream);
  * is submitted --, so device and roster agree after that tick: a LEAVE followed by mi_bridge_add_member leaves the seat
  * plumbed (its row still cleared once), a JOIN followed by mi_bridge_remove_member leaves it unplumbed with the new kind.
  * Out of scope: mi_volume_params and input gain per change (the waiting setters'); growing nstreams; kinds outside
- * mi_bridge_create_ratios' rules; mi_session; the plugin's server legs. */
+ * mi_bridge_create_ratios' rules; the plugin's server legs.  (mi_session has the call of its own: msmi355x_session.h.) */
 #define MI_BRIDGE_JOIN 1  /* a NEW endpoint of kind `leg` takes the seat; a seat that is taken is replaced (leave + join) */
 #define MI_BRIDGE_LEAVE 2 /* the seat is unplumbed; `leg` is not read */
 typedef struct mi_bridge_change {

@@ -821,6 +821,7 @@ class SessionConfig(C.Structure):
 
 MI_SESSION_PCM16, MI_SESSION_PCMA, MI_SESSION_PCMU = 0, 1, 2
 MI_BRIDGE_JOIN, MI_BRIDGE_LEAVE = 1, 2
+MI_SESSION_JOIN, MI_SESSION_LEAVE = 1, 2
 
 
 class Session(_ConferenceBatch):
@@ -873,6 +874,16 @@ class Session(_ConferenceBatch):
         po = C.c_void_p()
         check(self.ctx.L.mi_session_collect(self.h, C.byref(po)))
         return self._view(po, self.out_len, self.out_dtype)
+
+    def change_members(self, changes):
+        """mi_session_change_members (include/msmi355x_session.h): changes [(stream, MI_SESSION_JOIN | MI_SESSION_LEAVE), ...] -- a
+        JOIN seats a NEW endpoint (every filter of the stream fresh), replacing whoever holds the seat; a LEAVE unplumbs it.  In
+        effect for the next tick submitted, the one being filled if one is acquired; never waits for the device.  member_count
+        and active_speakers' joining order answer at once."""
+        ch = np.zeros((len(changes), 2), np.int32)  # mi_session_change: stream, op
+        for i, (stream, op) in enumerate(changes):
+            ch[i] = (int(stream), int(op))
+        check(self.ctx.L.mi_session_change_members(self.h, ch.ctypes.data if len(ch) else None, len(ch)))
 
 
 class BridgeConfig(C.Structure):

@@ -71,6 +71,11 @@ BRIDGE_EXPORTS = [
     "mi_bridge_create_open", "mi_bridge_change_members",
 ]
 
+# every symbol include/msmi355x_session.h declares: mi_session's membership without a drain, in the same library
+SESSION_EXPORTS = [
+    "mi_session_change_members",
+]
+
 
 class VolumeParams(C.Structure):
     _fields_ = [
@@ -288,6 +293,7 @@ def load():
     L.mi_bridge_set_volume_params.argtypes = [vp, i32, i32, C.POINTER(VolumeParams)]
     L.mi_bridge_get_volume_state.argtypes = [vp, i32, i32, C.POINTER(VolumeState)]
     L.mi_bridge_get_volume_max.argtypes = [vp, i32, i32, vp]
+    L.mi_session_change_members.argtypes = [vp, vp, i32]
     if hasattr(L, "mi_fifo_create"):
         L.mi_fifo_create.argtypes = [vp, i32, i32, pp]
         L.mi_fifo_destroy.argtypes = [vp]

@@ -332,6 +332,7 @@ struct mi_aec {
 	size_t wf_stride() const { return (size_t)2 * M * N; }
 	float *half(int s, int h) const { return d_WF + wf_stride() * s + (size_t)h * M * N; }
 	AecScalars *d_scal = nullptr;
+	uint8_t *d_fresh = nullptr; // a fresh stream's `small` row, then its AecScalars: what a seat that changes hands is given (mi_aec_edit)
 	void *d_tables = nullptr;
 	AecTables t;
 	FftPlan plan;
@@ -527,6 +528,19 @@ int init_state(mi_aec *a, int first, int count) {
 
 } // namespace
 
+// what mi_aec_reset writes for one stream, as byte ranges and templates (AecEdit, common.hpp): the layouts stay here
+void mi_aec_edit(mi_aec *a, AecEdit *out) {
+	*out = AecEdit();
+	if (!a) return;
+	static_assert(sizeof(AecScalars) % 16 == 0, "the scalar record is copied in 16-byte groups");
+	out->X = a->d_X, out->x_bytes = (size_t)(a->M + 1) * a->N * sizeof(float);
+	out->WF = a->d_WF, out->wf_bytes = a->wf_stride() * sizeof(float);
+	out->small = a->d_small, out->small_bytes = a->small_stride * (int)sizeof(float);
+	out->scal = a->d_scal, out->scal_bytes = (int)sizeof(AecScalars);
+	out->small_tpl = reinterpret_cast<const float *>(a->d_fresh);
+	out->scal_tpl = a->d_fresh + out->small_bytes;
+}
+
 extern "C" {
 
 int mi_aec_framesize(int framesize_at_8000, int sample_rate) { // speexec.c:171-180
@@ -595,6 +609,16 @@ int mi_aec_create(mi_ctx *ctx, int nstreams, int sample_rate, int frame_size, in
 		mi_aec_destroy(a);
 		return rc;
 	}
+	{ // the template of everything in a fresh stream that is not zero: stream 0's, as init_state has just written it
+		const size_t sb = (size_t)a->small_stride * sizeof(float);
+		if (hipMalloc((void **)&a->d_fresh, sb + sizeof(AecScalars)) != hipSuccess ||
+		    hipMemcpy(a->d_fresh, a->d_small, sb, hipMemcpyDeviceToDevice) != hipSuccess ||
+		    hipMemcpy(a->d_fresh + sb, a->d_scal, sizeof(AecScalars), hipMemcpyDeviceToDevice) != hipSuccess) {
+			mi::set_error("hipMalloc failed for the canceller's fresh-state template");
+			mi_aec_destroy(a);
+			return MI_ENOMEM;
+		}
+	}
 	{ // the FIFO entry's leg lists start as the identity: class c = legs c, c + 8, .. (all entered from the front)
 		a->cap8 = (nstreams + 7) / 8 + TickOrder::SLACK;
 		std::vector<int> ord((size_t)2 * 8 * a->cap8, 0), ctl(TickOrder::WORDS, 0);
@@ -619,6 +643,7 @@ void mi_aec_destroy(mi_aec *a) {
 	if (a->d_WF) (void)hipFree(a->d_WF);
 	if (a->d_small) (void)hipFree(a->d_small);
 	if (a->d_scal) (void)hipFree(a->d_scal);
+	if (a->d_fresh) (void)hipFree(a->d_fresh);
 	if (a->d_tables) (void)hipFree(a->d_tables);
 	if (a->d_order) (void)hipFree(a->d_order);
 	if (a->d_ctl) (void)hipFree(a->d_ctl);

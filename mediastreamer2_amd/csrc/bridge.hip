@@ -311,14 +311,10 @@ struct mi_bridge {
 	float *d_tab = nullptr;
 	int2 *d_gen = nullptr; // plan.generic: RatiosArgs::gen_tab
 	uint8_t *d_codec = nullptr; // the codecs as data ([n]; [2][n] with plc: the second row names PCM in, behind the concealer)
-	// membership changes (mi_bridge_change_members): what the calls since the last submit left per seat, merged -- op 0: nothing
-	// --, the seats whose output row is still to be cleared in slots to come, and per slot the pinned command row the tick
-	// carries, its device copy and its length
-	struct Pending { uint8_t op = 0, ratio = 0, codec = 0, cls = 0; bool clear = false; int32_t len = 0; };
-	std::vector<Pending> pending;      // [n]
-	std::vector<int32_t> changed;      // the seats with pending[s].op != 0
-	std::vector<uint8_t> clear_left;   // [n] submits in which the seat's row is still to be cleared
-	std::vector<int32_t> clearing;     // the seats with clear_left[s] != 0
+	// membership changes (mi_bridge_change_members): the calls' bookkeeping -- what they left per seat since the last submit,
+	// merged, and the seats whose output row is still to be cleared in slots to come (seat_changes.hpp) -- and per slot the
+	// pinned command row the tick carries, its device copy and its length
+	mi::SeatChanges changes;
 	mi_seat_cmd *h_cmd[SLOTS] = {}, *d_cmd[SLOTS] = {};
 	int ncmd[SLOTS] = {};
 };
@@ -510,39 +506,6 @@ int build_tables(mi_bridge *b) {
 	return MI_OK;
 }
 
-// ---- membership changes on their way to the device.  stage_changes writes the command row of the tick about to be submitted
-// into the slot's pinned staging (acquire has waited for the slot's last use): the merged changes, each with MI_SEAT_CLEAR
-// where the seat's row is to be zeroed, then a bare MI_SEAT_CLEAR for every seat that left within the last SLOTS - 1 submits --
-// a slot's device row is cleared only by the tick that runs in that slot, so the clear repeats until every slot has had it.
-// changes_submitted: the tick is on its way
-void stage_changes(mi_bridge *b, int slot) {
-	int k = 0;
-	mi_seat_cmd *row = b->h_cmd[slot];
-	for (const int32_t s : b->changed) {
-		const mi_bridge::Pending &p = b->pending[(size_t)s];
-		const bool clear = p.clear || b->clear_left[(size_t)s];
-		// the pin's flags as the roster has them NOW: a waiting call since the change (mi_bridge_set_controls, _add_member,
-		// _remove_member) has had the last word on them
-		row[k++] = {s, (uint8_t)(p.op | (clear ? MI_SEAT_CLEAR : 0)), p.ratio, p.codec, p.cls, p.len, b->roster.flags[(size_t)s], {0, 0, 0}};
-	}
-	for (const int32_t s : b->clearing)
-		if (!b->pending[(size_t)s].op) row[k++] = {s, MI_SEAT_CLEAR, 0, 0, 0, 0, 0, {0, 0, 0}};
-	b->ncmd[slot] = k;
-}
-
-void changes_submitted(mi_bridge *b) {
-	for (const int32_t s : b->clearing) b->clear_left[(size_t)s]--;
-	b->clearing.erase(std::remove_if(b->clearing.begin(), b->clearing.end(), [&](int32_t s) { return !b->clear_left[(size_t)s]; }), b->clearing.end());
-	for (const int32_t s : b->changed) {
-		if (b->pending[(size_t)s].clear) {
-			if (!b->clear_left[(size_t)s]) b->clearing.push_back(s);
-			b->clear_left[(size_t)s] = SLOTS - 1;
-		}
-		b->pending[(size_t)s] = mi_bridge::Pending();
-	}
-	b->changed.clear();
-}
-
 } // namespace
 
 extern "C" {
@@ -588,7 +551,7 @@ static int build_bridge(mi_ctx *ctx, Plan &plan, mi_bridge **out) {
 	const Plan &pl = b->plan;
 	const size_t n = (size_t)pl.n;
 	b->roster.init(pl.n, pl.mm);
-	b->pending.resize(n), b->clear_left.resize(n);
+	b->changes.init(pl.n, SLOTS);
 	int rc = MI_OK;
 	auto fail = [&](int code) { return mi_bridge_destroy(b), code; };
 	if ((rc = mi_volume_create(ctx, pl.n, pl.cfg.rate, &b->vol)) != MI_OK) return fail(rc);
@@ -739,7 +702,8 @@ int mi_bridge_submit(mi_bridge *b) {
 		return MI_EINVAL;
 	}
 	const size_t n = (size_t)b->plan.n;
-	stage_changes(b, b->pipe.next_slot());
+	// (mi::SeatChanges::stage: acquire has waited for the slot's last use)
+	b->ncmd[b->pipe.next_slot()] = b->changes.stage(b->h_cmd[b->pipe.next_slot()], b->roster.flags.data());
 	const int rc = b->pipe.submit(
 	    [&](int slot) {
 		    if (b->ncmd[slot])
@@ -758,7 +722,7 @@ int mi_bridge_submit(mi_bridge *b) {
 		    MI_HIP(hipMemcpyAsync(b->h_out[slot], b->d_out[slot], n * b->plan.out_bytes, hipMemcpyDeviceToHost, b->pipe.s_down));
 		    return MI_OK;
 	    });
-	if (rc == MI_OK) changes_submitted(b);
+	if (rc == MI_OK) b->changes.submitted();
 	return rc;
 }
 
@@ -833,7 +797,7 @@ int mi_bridge_remove_member(mi_bridge *b, int stream) {
 }
 
 // no stream, event or device synchronise and no blocking copy on this path: the roster and the plan's per-seat vectors answer
-// at once, the device follows with the next tick submitted (stage_changes, apply_changes)
+// at once, the device follows with the next tick submitted (mi::SeatChanges::stage, apply_changes)
 int mi_bridge_change_members(mi_bridge *b, const mi_bridge_change *h_changes, int count) {
 	MI_CHECK_ARG(b && count >= 0 && (h_changes || count == 0));
 	Plan &pl = b->plan;
@@ -849,16 +813,11 @@ int mi_bridge_change_members(mi_bridge *b, const mi_bridge_change *h_changes, in
 	for (int i = 0; i < count; ++i) {
 		const mi_bridge_change &c = h_changes[i];
 		const size_t s = (size_t)c.stream;
-		mi_bridge::Pending &p = b->pending[s];
-		if (!p.op) b->changed.push_back(c.stream);
 		const bool was = b->roster.leave(c.stream); // a seat that is taken is replaced: leave + join
-		p.clear |= was;
-		if (c.op == MI_BRIDGE_LEAVE) {
-			p.op = MI_SEAT_LEAVE;
-			continue;
-		}
+		mi::SeatChanges::Pending &p = b->changes.note(c.stream, c.op == MI_BRIDGE_LEAVE ? MI_SEAT_LEAVE : MI_SEAT_JOIN, was);
+		if (c.op == MI_BRIDGE_LEAVE) continue;
 		b->roster.join(c.stream); // a NEW endpoint: the last of its conference's list
-		p.op = MI_SEAT_JOIN, p.ratio = ratio[(size_t)i], p.codec = (uint8_t)(c.leg.in_codec | c.leg.out_codec << 2), p.len = c.leg.rate / 100;
+		p.ratio = ratio[(size_t)i], p.codec = (uint8_t)(c.leg.in_codec | c.leg.out_codec << 2), p.len = c.leg.rate / 100;
 		p.cls = cls[(size_t)i];
 		if (b->plc) mi_plc_seat(b->plc, c.stream, p.cls, c.leg.in_codec);
 		if (!pl.leg_rate.empty()) pl.leg_rate[s] = c.leg.rate;

@@ -8,6 +8,7 @@
 
 #include "../../include/msmi355x.h"
 #include "../../include/msmi355x_bridge.h"
+#include "seat_changes.hpp"
 
 #ifdef __HIPCC__
 #define MI_PLAN_HD __host__ __device__
@@ -375,21 +376,9 @@ inline mi_bridge_leg seat_kind(const Plan &p, int s) {
 inline int check_changes(const Plan &p, const uint8_t *flags, const mi_bridge_change *ch, int count, std::vector<uint8_t> *ratio) {
 	MI_PLAN_ARG(flags && ratio && count >= 0 && (ch || count == 0));
 	const char *fn = "mi_bridge_change_members";
-	std::vector<int32_t> seen;
-	for (int i = 0; i < count; ++i) {
-		const mi_bridge_change &c = ch[i];
-		if (c.stream < 0 || c.stream >= p.n) return mi::set_error("%s: entry %d names stream %d of %d", fn, i, c.stream, p.n), (int)MI_EINVAL;
-		if (c.op != MI_BRIDGE_JOIN && c.op != MI_BRIDGE_LEAVE)
-			return mi::set_error("%s: entry %d (stream %d) has op %d; MI_BRIDGE_JOIN (1) or MI_BRIDGE_LEAVE (2)", fn, i, c.stream, c.op), (int)MI_EINVAL;
-		seen.push_back(c.stream);
-	}
-	std::sort(seen.begin(), seen.end());
-	const auto twice = std::adjacent_find(seen.begin(), seen.end());
-	if (twice != seen.end()) {
-		int at = count - 1;
-		while (at > 0 && ch[at].stream != *twice) --at;
-		return mi::set_error("%s: entry %d names stream %d a second time in one call", fn, at, *twice), (int)MI_EINVAL;
-	}
+	static_assert(MI_BRIDGE_JOIN == MI_SEAT_JOIN && MI_BRIDGE_LEAVE == MI_SEAT_LEAVE, "the public ops are the command's");
+	const int rc = mi::check_seat_list(fn, "MI_BRIDGE_JOIN (1) or MI_BRIDGE_LEAVE (2)", p.n, ch, count);
+	if (rc != MI_OK) return rc;
 	ratio->assign((size_t)count, 0);
 	for (int i = 0; i < count; ++i) {
 		const mi_bridge_change &c = ch[i];

@@ -93,6 +93,11 @@ inline FifoView fifo_view(const mi_fifo *f) {
 	return v;
 }
 
+// Stream s's share of `phases` re-framing phases (mi_fifo_push_lead, mi_aec_stagger_fifos): a multiplicative hash (a bijection
+// of the 32-bit slot index) decides, so that ANY regular arrangement of slots -- consecutive legs of a conference, every eighth
+// slot, one bank -- gets every phase equally often.  Host and device use the same function.
+__host__ __device__ inline unsigned fifo_phase_of(unsigned s, unsigned phases) { return ((s * 0x9E3779B1u) >> 16) % phases; }
+
 // What the canceller's tick kernel needs of an up-sampling mi_resampler to run it as its own first phase (MSResample folded
 // into MSSpeexEC's launch, mi_aec_process_fifos_resampled).  Filled by mi_resampler_view (resample.hip); ok = the resampler
 // is an integer up-sampler with the 48-tap direct table whose streams all sit on a whole output period.
@@ -139,20 +144,30 @@ struct MixerEdit {
 };
 void mi_mixer_edit(mi_mixer *m, MixerEdit *out);
 
-// One membership change as the device applies it (mi_bridge_change_members, bridge.hip): a pinned row of these per pipe slot,
-// uploaded with the tick they take effect in.  bridge_roster.hip applies the bridge's part, plc.hip the concealer's.
-enum : uint8_t { MI_SEAT_JOIN = 1, MI_SEAT_LEAVE = 2, MI_SEAT_CLEAR = 4 }; // CLEAR: zero the seat's output row in this tick's slot
-struct mi_seat_cmd {
-	int32_t stream;
-	uint8_t op;    // MI_SEAT_*
-	uint8_t ratio; // JOIN: the kind's ratio byte (bridge_plan.hpp)
-	uint8_t codec; // JOIN: in_codec | out_codec << 2
-	uint8_t cls;   // JOIN: the kind's rate class in the concealer
-	int32_t len;   // JOIN: the kind's rate / 100
-	uint8_t flags; // JOIN, LEAVE: the pin's MI_MIX_* as the roster has them when the tick is submitted
-	uint8_t pad[3];
+// One membership change as the device applies it (mi_bridge_change_members, mi_session_change_members): mi_seat_cmd, with the
+// host's bookkeeping around it
+#include "seat_changes.hpp"
+
+// What the session's roster kernel (session_roster.hip) WRITES when a new endpoint takes a seat, besides the meter and the pin
+// above: a fresh canceller, fresh resamplers.  The canceller's layout stays aec.hip's: the kernel is told which byte ranges of
+// a stream are zero in a fresh speex_echo_state (both filter halves, the X history) and handed a template of the rest -- the
+// `small` row and the scalar record as init_state writes them, built once on the device when the canceller is created.
+struct AecEdit {
+	float *X = nullptr, *WF = nullptr;   // [nstreams] x_bytes / wf_bytes each, multiples of 16
+	size_t x_bytes = 0, wf_bytes = 0;
+	float *small = nullptr;              // [nstreams] small_bytes each, a multiple of 16
+	void *scal = nullptr;                // [nstreams] scal_bytes each, a multiple of 16
+	const float *small_tpl = nullptr;    // small_bytes
+	const void *scal_tpl = nullptr;      // scal_bytes
+	int small_bytes = 0, scal_bytes = 0;
 };
-static_assert(sizeof(mi_seat_cmd) == 16, "a command is one 16-byte load");
+void mi_aec_edit(mi_aec *a, AecEdit *out);
+struct ResamplerEdit {
+	int16_t *hist = nullptr; // [nstreams][hist_stride], hist_stride a multiple of 8
+	int2 *pos = nullptr;     // [nstreams] (last_sample, frac)
+	int hist_stride = 0;
+};
+void mi_resampler_edit(mi_resampler *r, ResamplerEdit *out);
 
 // The concealer batch whose streams each have a rate and a decoder of their own (plc.hip), for the bridge's legs:
 // h_rate [nstreams] in Hz (multiples of 800), h_kind [nstreams] MI_SESSION_PCM16 | PCMA | PCMU: what the stream's byte row

@@ -89,21 +89,28 @@ inline int reset_meters(mi_volume *vol, int first, int count) {
 	return rc != MI_OK ? rc : mi_volume_reset_max(vol, first, count);
 }
 
-// the level meter read-out (MS_VOLUME_GET_LINEAR) an active-speaker detector polls
-inline int get_levels(mi_volume *vol, int n, float *h_linear) {
+// the level meter read-out (MS_VOLUME_GET_LINEAR) an active-speaker detector polls.  fresh: the seats a NEW endpoint has
+// taken whose meter the device has not been handed yet (mi_session_change_members: it travels with the next tick) -- a new
+// MSVolume has metered nothing
+inline int get_levels(mi_volume *vol, int n, float *h_linear, const std::vector<int32_t> *fresh = nullptr) {
 	std::vector<mi_volume_state> st((size_t)n);
 	const int rc = mi_volume_get_state(vol, 0, n, st.data());
 	if (rc != MI_OK) return rc;
 	for (int i = 0; i < n; ++i) h_linear[i] = st[(size_t)i].energy; // volume_get_linear msvolume.c:129-134
+	if (fresh)
+		for (const int32_t s : *fresh) h_linear[(size_t)s] = 0.f;
 	return MI_OK;
 }
 
 // ms_audio_conference_process_events' election in mixer mode (:436-452) on the meters' one-second maxima.  The windows run
 // on the device, one record per tick (msvolume.c:404): the caller's clock is not needed
-inline int active_speakers(mi_volume *vol, const Roster &r, int32_t *h_winner, float *h_max_db) {
+// (fresh: as get_levels' -- ortp_extremum_init: 0 before the first record)
+inline int active_speakers(mi_volume *vol, const Roster &r, int32_t *h_winner, float *h_max_db, const std::vector<int32_t> *fresh = nullptr) {
 	std::vector<float> mx(r.flags.size());
 	const int rc = mi_volume_get_max(vol, 0, (int)mx.size(), mx.data());
 	if (rc != MI_OK) return rc;
+	if (fresh)
+		for (const int32_t s : *fresh) mx[(size_t)s] = 0.f;
 	r.elect(mx.data(), h_winner, h_max_db);
 	return MI_OK;
 }

@@ -33,11 +33,7 @@ struct FifoArgs {
 	int32_t *overflow; // number of pushes refused because the ring was full
 };
 
-// Stream s's share of `phases` re-framing phases: a multiplicative hash (a bijection of the 32-bit slot index) decides,
-// so that ANY regular arrangement of slots -- consecutive legs of a conference, every eighth slot, one bank -- gets every
-// phase equally often.  Host and device use the same function.
-__host__ __device__ inline unsigned fifo_phase_of(unsigned s, unsigned phases) { return ((s * 0x9E3779B1u) >> 16) % phases; }
-
+// (fifo_phase_of, a stream's share of the re-framing phases: common.hpp)
 // `unit * phase(s)` samples of silence appended to streams [first, first + count): the lead a leg starts with
 __global__ void fifo_rewind_kernel(int2 *pos, int count, int head) { // mi_fifo_reset_range_at
 	const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);

@@ -483,6 +483,11 @@ void mi_resampler_view(mi_resampler *r, ResamplerView *v) {
 	v->ok = r->d.num == 1 && r->d.den > 1 && r->dev_direct() && r->d.phase_table.empty() && r->d.filt_len == 48 && r->phase_zero;
 }
 
+void mi_resampler_edit(mi_resampler *r, ResamplerEdit *out) {
+	*out = ResamplerEdit();
+	if (r) out->hist = r->d_hist, out->pos = r->d_pos, out->hist_stride = r->hist_stride;
+}
+
 // 8-byte row loads, at most max_quads / 64 per lane, and 16-byte output stores; any other layout takes the generic kernel
 static bool tile_layout(const RsArgs &a, int out_len, int max_quads) {
 	const int nq = (a.hist_stride >> 2) + (a.in_len >> 2);

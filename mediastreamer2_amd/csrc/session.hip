@@ -13,10 +13,14 @@
 #include "conference.hpp"
 #include "tick_pipe.hpp"
 
+#include "../../include/msmi355x_session.h"
+#include "session_roster.hpp"
+
 #include <cmath>
 
 namespace {
 constexpr int SLOTS = 3; // upload | compute | download can each hold a different tick
+static_assert(SLOTS == SESSION_ROSTER_SLOTS, "the roster kernel clears the kept mix of every slot");
 }
 
 struct mi_session {
@@ -45,6 +49,12 @@ struct mi_session {
 	uint8_t *d_reset_gate = nullptr; // [n] mi_session_reset_streams: 1 = the leg's reference FIFO gets its delay again
 	mi_graph *graph[SLOTS] = {};
 	mi::Roster roster; // conference membership / active-speaker election (MSAudioConference, src/voip/audioconference.c)
+	// membership changes (mi_session_change_members): the calls' bookkeeping (seat_changes.hpp) and per slot the pinned command
+	// row the tick carries, its device copy and its length
+	mi::SeatChanges changes;
+	mi_seat_cmd *h_cmd[SLOTS] = {}, *d_cmd[SLOTS] = {};
+	int ncmd[SLOTS] = {};
+	int lead_unit = 0, lead_phases = 0; // cfg.stagger: mi_aec_stagger_info's, what a fresh seat's queues lead with
 };
 
 namespace {
@@ -119,6 +129,30 @@ int run_tick_kernels(mi_session *s, int slot) { // everything on the context's s
 	return MI_OK;
 }
 
+// a tick that carries membership changes: the session's own state in one launch, the concealer's in one of plc.hip's.  Called
+// inside the pipe's kernels(slot), behind the wait for the download that last read this slot's output rows -- only there is
+// zeroing a row free of a race with it -- and in front of the slot's graph, never inside it
+int apply_changes(mi_session *s, int slot) {
+	SessionRosterArgs ra = {};
+	ra.cmd = s->d_cmd[slot], ra.count = s->ncmd[slot], ra.nstreams = s->n;
+	mi_aec_edit(s->aec, &ra.aec);
+	mi_resampler_edit(s->rs, &ra.rs_in);
+	mi_resampler_edit(s->rs_out, &ra.rs_out);
+	mi_volume_edit(s->vol, &ra.vol);
+	MixerEdit me;
+	mi_mixer_edit(s->mix, &me);
+	ra.flags = me.flags;
+	ra.f_mic = fifo_view(s->f_mic), ra.f_ref = fifo_view(s->f_ref), ra.f_out = fifo_view(s->f_out);
+	ra.ref_delay = s->cfg.ref_delay_ms * s->cfg.rate / 1000;
+	ra.lead_unit = s->lead_unit, ra.lead_phases = s->lead_phases;
+	for (int i = 0; i < SLOTS; ++i) ra.mix[i] = s->d_mix[i];
+	ra.mix_len = s->len;
+	ra.out = reinterpret_cast<uint8_t *>(s->d_out[slot]), ra.out_bytes = (int)s->out_bytes;
+	const int rc = mi_session_roster_launch(ra, s->ctx->stream);
+	if (rc != MI_OK || !s->plc) return rc;
+	return mi_plc_apply_seats(s->plc, s->d_cmd[slot], s->ncmd[slot]);
+}
+
 } // namespace
 
 extern "C" {
@@ -152,6 +186,8 @@ void mi_session_destroy(mi_session *s) {
 		if (s->d_mix[i]) mi_dev_free(c, s->d_mix[i]);
 		if (s->h_ev[i]) mi_host_free(c, s->h_ev[i]);
 		if (s->d_ev[i]) mi_dev_free(c, s->d_ev[i]);
+		if (s->h_cmd[i]) mi_host_free(c, s->h_cmd[i]);
+		if (s->d_cmd[i]) mi_dev_free(c, s->d_cmd[i]);
 	}
 	void *dv[] = {s->d_up, s->d_tick, s->d_pcm, s->d_down, s->d_zero, s->d_evlen, s->d_reset_gate};
 	for (void *p : dv)
@@ -183,6 +219,7 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 	s->cfg = *cfg;
 	s->n = cfg->nstreams;
 	s->roster.init(s->n, cfg->members_per_conference);
+	s->changes.init(s->n, SLOTS);
 	s->in_len = cfg->in_rate / 100;
 	s->len = cfg->rate / 100;
 	const bool down = cfg->out_rate != 0 && cfg->out_rate != cfg->rate;
@@ -230,6 +267,9 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 		s->d_mic[i] = (int16_t *)mi_dev_alloc(ctx, n * s->mic_bytes);
 		s->d_out[i] = (int16_t *)mi_dev_alloc(ctx, n * s->out_bytes);
 		if (!s->h_mic[i] || !s->h_out[i] || !s->d_mic[i] || !s->d_out[i]) return fail(MI_ENOMEM);
+		// every seat may change in one tick
+		s->h_cmd[i] = (mi_seat_cmd *)mi_host_alloc(ctx, n * sizeof(mi_seat_cmd)), s->d_cmd[i] = (mi_seat_cmd *)mi_dev_alloc(ctx, n * sizeof(mi_seat_cmd));
+		if (!s->h_cmd[i] || !s->d_cmd[i]) return fail(MI_ENOMEM);
 		if (!cfg->ref_loopback) {
 			s->h_ref[i] = (int16_t *)mi_host_alloc(ctx, n * s->ref_bytes);
 			s->d_ref[i] = (int16_t *)mi_dev_alloc(ctx, n * s->ref_bytes);
@@ -266,6 +306,7 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 		if ((rc = mi_fifo_push(s->f_ref, s->d_zero, delay, delay, nullptr)) != MI_OK) return fail(rc);
 	}
 	if (cfg->stagger && (rc = mi_aec_stagger_fifos(s->aec, s->f_mic, s->f_ref, s->len, 0, s->n)) != MI_OK) return fail(rc);
+	if (cfg->stagger && (rc = mi_aec_stagger_info(s->aec, s->len, &s->lead_unit, &s->lead_phases)) != MI_OK) return fail(rc);
 	MI_HIP(hipStreamSynchronize(ctx->stream));
 	*out = s;
 	return MI_OK;
@@ -317,16 +358,21 @@ int mi_session_submit(mi_session *s) {
 	}
 	mi_ctx *c = s->ctx;
 	const size_t n = (size_t)s->n;
-	return s->pipe.submit(
+	const int at = s->pipe.next_slot();
+	s->ncmd[at] = s->changes.stage(s->h_cmd[at], s->roster.flags.data());
+	const int rc = s->pipe.submit(
 	    [&](int slot) {
+		    if (s->ncmd[slot])
+			    MI_HIP(hipMemcpyAsync(s->d_cmd[slot], s->h_cmd[slot], (size_t)s->ncmd[slot] * sizeof(mi_seat_cmd), hipMemcpyHostToDevice, s->pipe.s_up));
 		    MI_HIP(hipMemcpyAsync(s->d_mic[slot], s->h_mic[slot], n * s->mic_bytes, hipMemcpyHostToDevice, s->pipe.s_up));
 		    if (s->ref_bytes) MI_HIP(hipMemcpyAsync(s->d_ref[slot], s->h_ref[slot], n * s->ref_bytes, hipMemcpyHostToDevice, s->pipe.s_up));
 		    if (s->plc) MI_HIP(hipMemcpyAsync(s->d_ev[slot], s->h_ev[slot], n, hipMemcpyHostToDevice, s->pipe.s_up));
 		    return MI_OK;
 	    },
 	    [&](int slot) {
-		    if (!s->cfg.use_graphs) return run_tick_kernels(s, slot);
 		    int rc;
+		    if (s->ncmd[slot] && (rc = apply_changes(s, slot)) != MI_OK) return rc;
+		    if (!s->cfg.use_graphs) return run_tick_kernels(s, slot);
 		    if (!s->graph[slot]) {
 			    // first use of the slot: run eagerly once is not an option (state would advance twice), so capture directly
 			    if ((rc = mi_ctx_capture_begin(c)) != MI_OK) return rc;
@@ -343,6 +389,8 @@ int mi_session_submit(mi_session *s) {
 		    MI_HIP(hipMemcpyAsync(s->h_out[slot], s->d_out[slot], n * s->out_bytes, hipMemcpyDeviceToHost, s->pipe.s_down));
 		    return MI_OK;
 	    });
+	if (rc == MI_OK) s->changes.submitted();
+	return rc;
 }
 
 int mi_session_collect(mi_session *s, const int16_t **h_out) {
@@ -404,6 +452,28 @@ int mi_session_remove_member(mi_session *s, int stream) {
 	return MI_OK;
 }
 
+// no stream, event or device synchronise, no blocking copy and no allocation on this path: the roster answers at once, the
+// device follows with the next tick submitted (mi::SeatChanges::stage, apply_changes)
+int mi_session_change_members(mi_session *s, const mi_session_change *h_changes, int count) {
+	static_assert(MI_SESSION_JOIN == MI_SEAT_JOIN && MI_SESSION_LEAVE == MI_SEAT_LEAVE, "the public ops are the command's");
+	const char *fn = "mi_session_change_members";
+	if (!s) {
+		mi::set_error("%s: a null session", fn);
+		return MI_EINVAL;
+	}
+	const int rc = mi::check_uniform_changes(fn, "MI_SESSION_JOIN (1) or MI_SESSION_LEAVE (2)", s->n, s->roster.flags.data(), h_changes, count);
+	if (rc != MI_OK) return rc;
+	for (int i = 0; i < count; ++i) {
+		const mi_session_change &c = h_changes[i];
+		const bool was = s->roster.leave(c.stream); // a seat that is taken is replaced: leave + join
+		mi::SeatChanges::Pending &p = s->changes.note(c.stream, (uint8_t)c.op, was);
+		if (c.op == MI_SESSION_LEAVE) continue;
+		s->roster.join(c.stream); // a NEW endpoint: the last of its conference's list
+		p.len = s->in_len;        // (the concealer's batch is uniform: class 0, its tick the session's)
+	}
+	return MI_OK;
+}
+
 int mi_session_member_count(const mi_session *s, int conference) {
 	if (!s || conference < 0 || conference >= s->roster.nconf) return MI_EINVAL;
 	return s->roster.count(conference);
@@ -414,7 +484,8 @@ int mi_session_member_count(const mi_session *s, int conference) {
 int mi_session_active_speakers(mi_session *s, uint64_t now_ms, int32_t *h_winner, float *h_max_db) {
 	MI_CHECK_ARG(s && h_winner);
 	(void)now_ms;
-	return mi::active_speakers(s->vol, s->roster, h_winner, h_max_db);
+	const std::vector<int32_t> fresh = s->changes.joining();
+	return mi::active_speakers(s->vol, s->roster, h_winner, h_max_db, &fresh);
 }
 
 // A call leg leaves and another takes its place: every per-stream state of the chain goes back to its initial value
@@ -449,7 +520,8 @@ int mi_session_reset_streams(mi_session *s, int first, int count) {
 
 int mi_session_get_levels(mi_session *s, float *h_linear) {
 	MI_CHECK_ARG(s && h_linear);
-	return mi::get_levels(s->vol, s->n, h_linear);
+	const std::vector<int32_t> fresh = s->changes.joining();
+	return mi::get_levels(s->vol, s->n, h_linear, &fresh);
 }
 
 } // extern "C"
