@@ -268,7 +268,8 @@ int mi_bridge_remove_member(mi_bridge *b, int stream);
  * submit that carries it has the last word on the pin's flags -- the change writes the flags the roster holds when the tick
  * is submitted --, so device and roster agree after that tick: a LEAVE followed by mi_bridge_add_member leaves the seat
  * plumbed (its row still cleared once), a JOIN followed by mi_bridge_remove_member leaves it unplumbed with the new kind.
- * Out of scope: mi_volume_params and input gain per change (the waiting setters'); growing nstreams; kinds outside
+ * Out of scope: mi_volume_params and input gain per membership change (mi_bridge_change_controls below sends them with the
+ * same tick, the waiting setters keep working); growing nstreams; kinds outside
  * mi_bridge_create_ratios' rules; the plugin's server legs.  (mi_session has the call of its own: msmi355x_session.h.) */
 #define MI_BRIDGE_JOIN 1  /* a NEW endpoint of kind `leg` takes the seat; a seat that is taken is replaced (leave + join) */
 #define MI_BRIDGE_LEAVE 2 /* the seat is unplumbed; `leg` is not read */
@@ -284,6 +285,83 @@ int mi_bridge_active_speakers(mi_bridge *b, uint64_t now_ms, int32_t *h_winner, 
 /* the meters' running state and MS_VOLUME_GET_MAX (linear), for tests and monitoring; both wait for the ticks submitted */
 int mi_bridge_get_volume_state(mi_bridge *b, int first, int count, mi_volume_state *h_state);
 int mi_bridge_get_volume_max(mi_bridge *b, int first, int count, float *h_max);
+
+/* ---- The rest of the conference control plane WITHOUT waiting for the device.
+ *
+ * mi_bridge_set_controls, mi_bridge_set_volume_params, mi_bridge_get_levels and mi_bridge_active_speakers above each wait for
+ * every tick submitted (and copy whole [nstreams] arrays): a mute toggle or a level poll empties the three-tick pipeline that
+ * mi_bridge_change_members leaves alone.  The calls below steer and observe a running bridge without that.  The waiting calls
+ * keep their semantics and their waits.
+ *
+ * mi_bridge_change_controls: ms_audio_conference_mute_member (audioconference.c:377-388), MS_AUDIO_MIXER_SET_ACTIVE /
+ * _ENABLE_OUTPUT / _SET_INPUT_GAIN (audiomixer.c:372-414) and MSVolume's setters, per seat.  The calling contract is
+ * mi_bridge_change_members': the changes travel with the NEXT tick submitted -- the tick being filled, if one is acquired --
+ * and the device applies them in stream order ahead of that tick's kernels (controls_kernel, csrc/controls.hip); ticks
+ * submitted earlier are untouched, collected or not.  The call contains no stream, event or device synchronise, no blocking
+ * copy and no allocation.  Several calls before one submit merge per seat AND per field, the last one wins.
+ *   MI_CTL_FLAGS:  the pin's MI_MIX_ACTIVE and MI_MIX_OUTPUT bits are taken from `flags` (mute: ACTIVE clear; listen-only off:
+ *     OUTPUT clear).  MI_MIX_LINKED is membership's: any bit outside ACTIVE | OUTPUT is MI_EINVAL.  The seat must be a member
+ *     when the call is made; earlier mi_bridge_change_members calls not yet submitted count.  Clearing MI_MIX_OUTPUT does not
+ *     clear what the seat last heard, as mi_bridge_set_controls does not.
+ *   MI_CTL_GAIN:   the pin's input gain, on any seat.
+ *   MI_CTL_VOLUME: the seat's whole mi_volume_params, on any seat; params.peer != -1 is MI_ENOTSUP, as in
+ *     mi_bridge_set_volume_params.  Gain and parameters survive joins.
+ * Inside a tick membership changes are applied first, then controls: MI_BRIDGE_JOIN plus MI_CTL_FLAGS with ACTIVE clear before
+ * one submit gives a member that arrives muted.  What a tick carries is staged at submit from the host's own mirrors of flags,
+ * gains and parameters, which the waiting setters (mi_bridge_set_controls, _set_volume_params, _add_member, _remove_member)
+ * update too: a waiting call made between a change and its submit has the last word on the fields it sets, and device and
+ * host agree after that tick.  A LEAVE after an MI_CTL_FLAGS on the same seat leaves the seat unplumbed.
+ * Nothing of a refused call is applied, and the message names the entry.  MI_EINVAL: a NULL bridge; count < 0, or count > 0
+ * with a NULL h_changes; a stream out of range; an empty or unknown `what`; one stream twice in one call; the two rules of
+ * MI_CTL_FLAGS.  count == 0 is MI_OK and does nothing.
+ * Measured at 1024 conferences x 32 mu-law legs, three ticks in flight (profiles/bridge_controls.md): 1.0 us per call for one
+ * seat, 1.4 us for 32, 29 us for 1024, against 48 us for one mi_bridge_set_controls; a poll of every level and speaker costs
+ * 4 us through mi_bridge_collected_report against 425 us through mi_bridge_active_speakers + mi_bridge_get_levels, and a
+ * server that polls after every tick sustains 9880 ticks a second instead of 1694; the report kernel adds about 4 us to a
+ * 96 us tick. */
+#define MI_CTL_FLAGS 1u
+#define MI_CTL_GAIN 2u
+#define MI_CTL_VOLUME 4u
+typedef struct mi_bridge_control {
+	int32_t stream;
+	uint32_t what;  /* MI_CTL_* */
+	uint32_t flags; /* MI_CTL_FLAGS: MI_MIX_ACTIVE | MI_MIX_OUTPUT */
+	float gain;     /* MI_CTL_GAIN */
+	mi_volume_params params; /* MI_CTL_VOLUME */
+} mi_bridge_control;
+int mi_bridge_change_controls(mi_bridge *b, const mi_bridge_control *h_changes, int count);
+
+/* Levels and the election come back WITH the tick.  mi_bridge_set_reports(b, MI_REPORT_SPEAKERS | MI_REPORT_LEVELS) -- 0: off,
+ * the default -- is a configuration call: it may wait once and allocate; nothing per tick does.  From the next submit on one
+ * kernel (report_kernel, csrc/controls.hip) runs behind the tick's kernels, reads what the tick left and writes a report block
+ * that is downloaded with the tick's output.  mi_bridge_collected_report hands out the block of the tick LAST COLLECTED:
+ * pointers into pinned memory, valid for as long as that tick's output is; it never waits.  MI_EINVAL: nothing collected yet,
+ * reports were off for that tick, or its slot has been submitted again.  At most 64 members per conference (MI_ENOTSUP).
+ *   MI_REPORT_LEVELS:   levels [nstreams], every stream's MS_VOLUME_GET_LINEAR: bit for bit what mi_bridge_get_levels returns
+ *     when that tick is the last one submitted (the raw meter, muted members included).
+ *   MI_REPORT_SPEAKERS: per conference ms_audio_conference_process_events' election (audioconference.c:436-452): winner
+ *     [nconf] (stream or -1), max_lin [nconf] (the winner's one-second maximum, linear, or 0) and max_db [nconf], worked out
+ *     on the host in this call from max_lin with the waiting call's own expression, so the float is the one
+ *     mi_bridge_active_speakers gives.  Eligible are the plumbed, unmuted members whose maximum is above -30 dBm0 -- exactly the
+ *     waiting call's set: the kernel compares with the smallest float whose dBm0 value is above -30.0f, derived once with the
+ *     host's libm.  Of the eligible the largest maximum wins, of equal maxima the member that joined first.
+ *   A VISIBLE, DELIBERATE DIFFERENCE (in the manner of SURVEY Appendix A): the kernel compares LINEAR maxima, the reference dBm0
+ *   floats.  Where two eligible members' maxima are different floats whose dBm0 values round to the same float -- a band of
+ *   about four ulp near -30 dBm0 -- the reference takes the earlier joiner and the report the louder.  mi_bridge_active_speakers
+ *   stays the reference-exact call. */
+#define MI_REPORT_SPEAKERS 1u
+#define MI_REPORT_LEVELS 2u
+typedef struct mi_bridge_report {
+	uint64_t seq;  /* the tick's sequence number: 0 for the first tick the bridge was submitted */
+	uint32_t what; /* MI_REPORT_* as they were set when the tick was submitted */
+	int32_t nstreams, nconf;
+	const float *levels;   /* [nstreams], NULL without MI_REPORT_LEVELS */
+	const int32_t *winner; /* [nconf], NULL without MI_REPORT_SPEAKERS, as are the next two */
+	const float *max_lin;  /* [nconf] */
+	const float *max_db;   /* [nconf]; -120 (MS_VOLUME_DB_LOWEST) where nobody was elected */
+} mi_bridge_report;
+int mi_bridge_set_reports(mi_bridge *b, uint32_t what);
+int mi_bridge_collected_report(mi_bridge *b, mi_bridge_report *out);
 
 #ifdef __cplusplus
 }

@@ -811,6 +811,43 @@ class _ConferenceBatch(_Batch):
         check(self._call("active_speakers", C.c_uint64(int(now_ms)), _ptr(win), _ptr(db)))
         return win, db
 
+    def change_controls(self, changes):
+        """mi_<bridge|session>_change_controls: changes [(stream, {"flags": MI_MIX_ACTIVE | MI_MIX_OUTPUT bits, "gain": float,
+        "volume": VolumeParams}), ...], each dict naming at least one of the three ("volume": Bridge only).  In effect for the
+        next tick submitted, the one being filled if one is acquired, after that tick's membership changes; never waits for
+        the device."""
+        kind = _lib.Control if self._prefix == "bridge" else _lib.SessionControl
+        arr = (kind * max(len(changes), 1))()
+        for c, (stream, fields) in zip(arr, changes):
+            unknown = set(fields) - {"flags", "gain", "volume"}
+            assert not unknown and (self._prefix == "bridge" or "volume" not in fields), f"change_controls: {sorted(fields)}"
+            c.stream = int(stream)
+            if "flags" in fields:
+                c.what, c.flags = c.what | MI_CTL_FLAGS, int(fields["flags"])
+            if "gain" in fields:
+                c.what, c.gain = c.what | MI_CTL_GAIN, float(fields["gain"])
+            if "volume" in fields:
+                c.what, c.params = c.what | MI_CTL_VOLUME, fields["volume"]
+        check(self._call("change_controls", C.cast(arr, C.c_void_p) if len(changes) else None, len(changes)))
+
+    def set_reports(self, speakers=False, levels=False):
+        """mi_<bridge|session>_set_reports: from the next tick submitted on, every tick brings its election and / or its levels
+        back with its output (collected_report).  A configuration call: it may wait once."""
+        check(self._call("set_reports", (MI_REPORT_SPEAKERS if speakers else 0) | (MI_REPORT_LEVELS if levels else 0)))
+
+    def collected_report(self):
+        """mi_<bridge|session>_collected_report: the report of the tick last collected, as a dict of numpy views into the
+        pinned block (valid as long as that tick's output): seq, and with levels on "levels" [n], with speakers on "winner"
+        [nconf] (stream or -1), "max_lin" and "max_db" [nconf].  Never waits; MiError when reports were off for that tick."""
+        r = _lib.Report()
+        check(self._call("collected_report", C.byref(r)))
+        out = {"seq": int(r.seq), "what": int(r.what)}
+        for name, count in (("levels", r.nstreams), ("winner", r.nconf), ("max_lin", r.nconf), ("max_db", r.nconf)):
+            p = getattr(r, name)
+            if p:
+                out[name] = np.ctypeslib.as_array(p, shape=(count,))
+        return out
+
 
 class SessionConfig(C.Structure):
     _fields_ = [("nstreams", C.c_int32), ("members_per_conference", C.c_int32), ("in_rate", C.c_int32),
@@ -822,6 +859,8 @@ class SessionConfig(C.Structure):
 MI_SESSION_PCM16, MI_SESSION_PCMA, MI_SESSION_PCMU = 0, 1, 2
 MI_BRIDGE_JOIN, MI_BRIDGE_LEAVE = 1, 2
 MI_SESSION_JOIN, MI_SESSION_LEAVE = 1, 2
+MI_CTL_FLAGS, MI_CTL_GAIN, MI_CTL_VOLUME = 1, 2, 4
+MI_REPORT_SPEAKERS, MI_REPORT_LEVELS = 1, 2
 
 
 class Session(_ConferenceBatch):

@@ -69,11 +69,17 @@ BRIDGE_EXPORTS = [
     "mi_bridge_create_rational",
     "mi_bridge_create_ratios",
     "mi_bridge_create_open", "mi_bridge_change_members",
+    "mi_bridge_change_controls", "mi_bridge_set_reports", "mi_bridge_collected_report",
 ]
 
 # every symbol include/msmi355x_session.h declares: mi_session's membership without a drain, in the same library
 SESSION_EXPORTS = [
     "mi_session_change_members",
+]
+
+# every symbol include/msmi355x_session_controls.h declares: mi_session's mute, gain and reports without a drain
+SESSION_CONTROL_EXPORTS = [
+    "mi_session_change_controls", "mi_session_set_reports", "mi_session_collected_report",
 ]
 
 
@@ -96,6 +102,22 @@ class VolumeState(C.Structure):
         ("ng_gain", C.c_float), ("dc_offset", C.c_int32), ("sustain_dur", C.c_int32),
         ("ng_noise_dur", C.c_int32), ("fast_upramp", C.c_int32),
     ]
+
+
+class Control(C.Structure):
+    """mi_bridge_control; its first four fields are mi_session_control"""
+    _fields_ = [("stream", C.c_int32), ("what", C.c_uint32), ("flags", C.c_uint32), ("gain", C.c_float), ("params", VolumeParams)]
+
+
+class SessionControl(C.Structure):
+    _fields_ = Control._fields_[:4]
+
+
+class Report(C.Structure):
+    """mi_bridge_report and mi_session_report: one layout"""
+    _fields_ = [("seq", C.c_uint64), ("what", C.c_uint32), ("nstreams", C.c_int32), ("nconf", C.c_int32),
+                ("levels", C.POINTER(C.c_float)), ("winner", C.POINTER(C.c_int32)), ("max_lin", C.POINTER(C.c_float)),
+                ("max_db", C.POINTER(C.c_float))]
 
 
 _lib = None
@@ -294,6 +316,10 @@ def load():
     L.mi_bridge_get_volume_state.argtypes = [vp, i32, i32, C.POINTER(VolumeState)]
     L.mi_bridge_get_volume_max.argtypes = [vp, i32, i32, vp]
     L.mi_session_change_members.argtypes = [vp, vp, i32]
+    for p in ("session", "bridge"):
+        getattr(L, f"mi_{p}_change_controls").argtypes = [vp, vp, i32]
+        getattr(L, f"mi_{p}_set_reports").argtypes = [vp, u32]
+        getattr(L, f"mi_{p}_collected_report").argtypes = [vp, C.POINTER(Report)]
     if hasattr(L, "mi_fifo_create"):
         L.mi_fifo_create.argtypes = [vp, i32, i32, pp]
         L.mi_fifo_destroy.argtypes = [vp]

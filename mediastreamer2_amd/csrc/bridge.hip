@@ -43,6 +43,7 @@
 
 #include "bridge_phases.hpp"
 #include "bridge_roster.hpp"
+#include "controls.hpp"
 
 #pragma clang fp contract(off)
 
@@ -317,6 +318,8 @@ struct mi_bridge {
 	mi::SeatChanges changes;
 	mi_seat_cmd *h_cmd[SLOTS] = {}, *d_cmd[SLOTS] = {};
 	int ncmd[SLOTS] = {};
+	// mute, gain, parameters and the reports without a wait (mi_bridge_change_controls, mi_bridge_set_reports): controls.hpp
+	mi::ControlPlane ctl;
 };
 
 namespace {
@@ -376,6 +379,7 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 	const mi_bridge_config &cf = pl.cfg;
 	int rc, in_kind = cf.in_codec;
 	if (b->ncmd[slot] && (rc = apply_changes(b, slot)) != MI_OK) return rc;
+	if ((rc = b->ctl.apply(slot, b->mix, b->vol, true)) != MI_OK) return rc; // membership first, then controls
 	RatiosArgs ga = b->args; // each kernel is passed the part that is its own
 	RationalArgs &qa = ga.q;
 	BridgeArgs &a = qa.u.l.r.b;
@@ -532,6 +536,7 @@ void mi_bridge_destroy(mi_bridge *b) {
 		if (b->h_cmd[i]) mi_host_free(c, b->h_cmd[i]);
 		if (b->d_cmd[i]) mi_dev_free(c, b->d_cmd[i]);
 	}
+	b->ctl.destroy();
 	void *const rest[] = {b->d_ratio, b->d_hist_in, b->d_hist_out, b->d_tab, b->d_gen, b->d_codec, b->d_pcm, b->d_evlen};
 	for (void *p : rest)
 		if (p) mi_dev_free(c, p);
@@ -609,6 +614,9 @@ static int build_bridge(mi_ctx *ctx, Plan &plan, mi_bridge **out) {
 			if (pl.cfg.in_codec && !(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * pl.pitch * 2))) return fail(MI_ENOMEM);
 		}
 	}
+	mi_volume_params defaults;
+	mi_volume_default_params(&defaults); // mi_volume_create's
+	if ((rc = b->ctl.create(ctx, b->roster, SLOTS, &defaults)) != MI_OK) return fail(rc);
 	fill_args(b);
 	if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(MI_ENODEV);
 	*out = b;
@@ -704,10 +712,12 @@ int mi_bridge_submit(mi_bridge *b) {
 	const size_t n = (size_t)b->plan.n;
 	// (mi::SeatChanges::stage: acquire has waited for the slot's last use)
 	b->ncmd[b->pipe.next_slot()] = b->changes.stage(b->h_cmd[b->pipe.next_slot()], b->roster.flags.data());
+	b->ctl.stage(b->pipe.next_slot(), b->pipe.submitted, b->roster, b->changes);
 	const int rc = b->pipe.submit(
 	    [&](int slot) {
 		    if (b->ncmd[slot])
 			    MI_HIP(hipMemcpyAsync(b->d_cmd[slot], b->h_cmd[slot], (size_t)b->ncmd[slot] * sizeof(mi_seat_cmd), hipMemcpyHostToDevice, b->pipe.s_up));
+		    if (b->ctl.upload(slot, b->pipe.s_up) != MI_OK) return (int)MI_ENODEV;
 		    MI_HIP(hipMemcpyAsync(b->d_in[slot], b->h_in[slot], n * b->plan.in_bytes, hipMemcpyHostToDevice, b->pipe.s_up));
 		    if (b->plc) { // an absent leg is the concealer's to fill
 			    for (size_t i = 0; i < n; ++i) b->h_ev[slot][i] = b->h_present[slot][i] ? MI_PLC_RECEIVED : MI_PLC_CONCEAL;
@@ -717,12 +727,15 @@ int mi_bridge_submit(mi_bridge *b) {
 		    }
 		    return MI_OK;
 	    },
-	    [&](int slot) { return run_tick_kernels(b, slot); },
+	    [&](int slot) {
+		    const int rc = run_tick_kernels(b, slot);
+		    return rc != MI_OK ? rc : b->ctl.report(slot, b->mix, b->vol);
+	    },
 	    [&](int slot) {
 		    MI_HIP(hipMemcpyAsync(b->h_out[slot], b->d_out[slot], n * b->plan.out_bytes, hipMemcpyDeviceToHost, b->pipe.s_down));
-		    return MI_OK;
+		    return b->ctl.download(slot, b->pipe.s_down);
 	    });
-	if (rc == MI_OK) b->changes.submitted();
+	if (rc == MI_OK) b->changes.submitted(), b->ctl.submitted();
 	return rc;
 }
 
@@ -742,6 +755,7 @@ int mi_bridge_in_flight(const mi_bridge *b) { return b ? b->pipe.in_flight() : 0
 int mi_bridge_set_controls(mi_bridge *b, const uint8_t *h_flags, const float *h_gain) {
 	MI_CHECK_ARG(b && (h_flags || h_gain));
 	if (h_flags) b->roster.set_flags(h_flags);
+	if (h_gain) b->ctl.changes.set_gains(h_gain);
 	return mi_mixer_set_controls(b->mix, h_flags, h_gain); // [nconf][members] == [nstreams]
 }
 
@@ -753,6 +767,7 @@ int mi_bridge_set_volume_params(mi_bridge *b, int first, int count, const mi_vol
 			              first + i, h_params[i].peer);
 			return MI_ENOTSUP;
 		}
+	b->ctl.changes.set_params(first, count, h_params);
 	return mi_volume_set_params(b->vol, first, count, h_params);
 }
 
@@ -771,9 +786,10 @@ int mi_bridge_add_member(mi_bridge *b, int stream) {
 		mi::set_error("mi_bridge_add_member: stream %d is a member already", stream);
 		return MI_EINVAL;
 	}
-	const int rc = mi_bridge_reset_streams(b, stream, 1);
+	int rc = mi_bridge_reset_streams(b, stream, 1);
 	if (rc != MI_OK) return rc;
 	b->roster.join(stream);
+	if ((rc = b->ctl.joined_waiting(stream, b->roster)) != MI_OK) return rc;
 	return mi_mixer_set_controls(b->mix, b->roster.flags.data(), nullptr);
 }
 
@@ -825,6 +841,39 @@ int mi_bridge_change_members(mi_bridge *b, const mi_bridge_change *h_changes, in
 		if (!pl.ratio.empty()) pl.ratio[s] = p.ratio;
 	}
 	return MI_OK;
+}
+
+// no stream, event or device synchronise, no blocking copy and no allocation on this path: the mirrors answer at once, the
+// device follows with the next tick submitted (mi::ControlPlane::stage, ::apply)
+int mi_bridge_change_controls(mi_bridge *b, const mi_bridge_control *h_changes, int count) {
+	const char *fn = "mi_bridge_change_controls";
+	if (!b) {
+		mi::set_error("%s: a null bridge", fn);
+		return MI_EINVAL;
+	}
+	mi::ControlChanges &cc = b->ctl.changes;
+	int rc = mi::check_controls(fn, b->plan.n, b->roster.flags.data(), MI_CTL_FLAGS | MI_CTL_GAIN | MI_CTL_VOLUME, h_changes, count, cc.scratch);
+	if (rc != MI_OK || (rc = mi::check_control_params(fn, h_changes, count)) != MI_OK) return rc;
+	for (int i = 0; i < count; ++i) cc.apply(h_changes[i], b->roster.flags.data()), cc.apply_params(h_changes[i]);
+	return MI_OK;
+}
+
+int mi_bridge_set_reports(mi_bridge *b, uint32_t what) {
+	if (!b) {
+		mi::set_error("mi_bridge_set_reports: a null bridge");
+		return MI_EINVAL;
+	}
+	return b->ctl.set_reports("mi_bridge_set_reports", what, b->roster);
+}
+
+int mi_bridge_collected_report(mi_bridge *b, mi_bridge_report *out) {
+	if (!b || !out) {
+		mi::set_error("mi_bridge_collected_report: a null %s", b ? "report" : "bridge");
+		return MI_EINVAL;
+	}
+	out->nstreams = b->plan.n, out->nconf = b->plan.nconf;
+	return b->ctl.collected("mi_bridge_collected_report", b->pipe.collected, &out->seq, &out->what, &out->levels, &out->winner, &out->max_lin,
+	                        &out->max_db);
 }
 
 int mi_bridge_member_count(const mi_bridge *b, int conference) {

@@ -371,6 +371,8 @@ void mi_mixer_edit(mi_mixer *m, MixerEdit *out) {
 	if (m) out->flags = m->d_flags;
 }
 
+float *mi_mixer_gain_edit(mi_mixer *m) { return m ? m->d_gain : nullptr; } // (controls.hpp)
+
 extern "C" {
 
 int mi_mixer_create(mi_ctx *ctx, int nconf, int max_members, int nsamples, mi_mixer **out) {

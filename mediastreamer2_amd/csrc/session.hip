@@ -14,6 +14,8 @@
 #include "tick_pipe.hpp"
 
 #include "../../include/msmi355x_session.h"
+#include "../../include/msmi355x_session_controls.h"
+#include "controls.hpp"
 #include "session_roster.hpp"
 
 #include <cmath>
@@ -54,6 +56,8 @@ struct mi_session {
 	mi::SeatChanges changes;
 	mi_seat_cmd *h_cmd[SLOTS] = {}, *d_cmd[SLOTS] = {};
 	int ncmd[SLOTS] = {};
+	// mute, gain and the reports without a wait (mi_session_change_controls, mi_session_set_reports): controls.hpp
+	mi::ControlPlane ctl;
 	int lead_unit = 0, lead_phases = 0; // cfg.stagger: mi_aec_stagger_info's, what a fresh seat's queues lead with
 };
 
@@ -189,6 +193,7 @@ void mi_session_destroy(mi_session *s) {
 		if (s->h_cmd[i]) mi_host_free(c, s->h_cmd[i]);
 		if (s->d_cmd[i]) mi_dev_free(c, s->d_cmd[i]);
 	}
+	s->ctl.destroy();
 	void *dv[] = {s->d_up, s->d_tick, s->d_pcm, s->d_down, s->d_zero, s->d_evlen, s->d_reset_gate};
 	for (void *p : dv)
 		if (p) mi_dev_free(c, p);
@@ -307,6 +312,7 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 	}
 	if (cfg->stagger && (rc = mi_aec_stagger_fifos(s->aec, s->f_mic, s->f_ref, s->len, 0, s->n)) != MI_OK) return fail(rc);
 	if (cfg->stagger && (rc = mi_aec_stagger_info(s->aec, s->len, &s->lead_unit, &s->lead_phases)) != MI_OK) return fail(rc);
+	if ((rc = s->ctl.create(ctx, s->roster, SLOTS, nullptr)) != MI_OK) return fail(rc);
 	MI_HIP(hipStreamSynchronize(ctx->stream));
 	*out = s;
 	return MI_OK;
@@ -360,10 +366,12 @@ int mi_session_submit(mi_session *s) {
 	const size_t n = (size_t)s->n;
 	const int at = s->pipe.next_slot();
 	s->ncmd[at] = s->changes.stage(s->h_cmd[at], s->roster.flags.data());
+	s->ctl.stage(at, s->pipe.submitted, s->roster, s->changes);
 	const int rc = s->pipe.submit(
 	    [&](int slot) {
 		    if (s->ncmd[slot])
 			    MI_HIP(hipMemcpyAsync(s->d_cmd[slot], s->h_cmd[slot], (size_t)s->ncmd[slot] * sizeof(mi_seat_cmd), hipMemcpyHostToDevice, s->pipe.s_up));
+		    if (s->ctl.upload(slot, s->pipe.s_up) != MI_OK) return (int)MI_ENODEV;
 		    MI_HIP(hipMemcpyAsync(s->d_mic[slot], s->h_mic[slot], n * s->mic_bytes, hipMemcpyHostToDevice, s->pipe.s_up));
 		    if (s->ref_bytes) MI_HIP(hipMemcpyAsync(s->d_ref[slot], s->h_ref[slot], n * s->ref_bytes, hipMemcpyHostToDevice, s->pipe.s_up));
 		    if (s->plc) MI_HIP(hipMemcpyAsync(s->d_ev[slot], s->h_ev[slot], n, hipMemcpyHostToDevice, s->pipe.s_up));
@@ -372,7 +380,9 @@ int mi_session_submit(mi_session *s) {
 	    [&](int slot) {
 		    int rc;
 		    if (s->ncmd[slot] && (rc = apply_changes(s, slot)) != MI_OK) return rc;
-		    if (!s->cfg.use_graphs) return run_tick_kernels(s, slot);
+		    if ((rc = s->ctl.apply(slot, s->mix, s->vol, false)) != MI_OK) return rc; // membership first, then controls
+		    // the report's launch follows the tick's kernels -- behind the slot's graph, never inside it
+		    if (!s->cfg.use_graphs) return (rc = run_tick_kernels(s, slot)) != MI_OK ? rc : s->ctl.report(slot, s->mix, s->vol);
 		    if (!s->graph[slot]) {
 			    // first use of the slot: run eagerly once is not an option (state would advance twice), so capture directly
 			    if ((rc = mi_ctx_capture_begin(c)) != MI_OK) return rc;
@@ -383,13 +393,13 @@ int mi_session_submit(mi_session *s) {
 			    if (rc2 != MI_OK) return rc2;
 			    s->graph[slot] = g;
 		    }
-		    return mi_graph_launch(s->graph[slot]);
+		    return (rc = mi_graph_launch(s->graph[slot])) != MI_OK ? rc : s->ctl.report(slot, s->mix, s->vol);
 	    },
 	    [&](int slot) {
 		    MI_HIP(hipMemcpyAsync(s->h_out[slot], s->d_out[slot], n * s->out_bytes, hipMemcpyDeviceToHost, s->pipe.s_down));
-		    return MI_OK;
+		    return s->ctl.download(slot, s->pipe.s_down);
 	    });
-	if (rc == MI_OK) s->changes.submitted();
+	if (rc == MI_OK) s->changes.submitted(), s->ctl.submitted();
 	return rc;
 }
 
@@ -411,6 +421,7 @@ int mi_session_in_flight(const mi_session *s) { return s ? s->pipe.in_flight() :
 int mi_session_set_controls(mi_session *s, const uint8_t *h_flags, const float *h_gain) {
 	MI_CHECK_ARG(s && (h_flags || h_gain));
 	if (h_flags) s->roster.set_flags(h_flags);
+	if (h_gain) s->ctl.changes.set_gains(h_gain);
 	return mi_mixer_set_controls(s->mix, h_flags, h_gain); // [nconf][members] == [nstreams]
 }
 
@@ -424,9 +435,10 @@ int mi_session_add_member(mi_session *s, int stream) {
 		mi::set_error("mi_session_add_member: stream %d is a member already", stream);
 		return MI_EINVAL;
 	}
-	const int rc = mi_session_reset_streams(s, stream, 1);
+	int rc = mi_session_reset_streams(s, stream, 1);
 	if (rc != MI_OK) return rc;
 	s->roster.join(stream);
+	if ((rc = s->ctl.joined_waiting(stream, s->roster)) != MI_OK) return rc;
 	return mi_mixer_set_controls(s->mix, s->roster.flags.data(), nullptr);
 }
 
@@ -472,6 +484,39 @@ int mi_session_change_members(mi_session *s, const mi_session_change *h_changes,
 		p.len = s->in_len;        // (the concealer's batch is uniform: class 0, its tick the session's)
 	}
 	return MI_OK;
+}
+
+// no stream, event or device synchronise, no blocking copy and no allocation on this path: the mirrors answer at once, the
+// device follows with the next tick submitted (mi::ControlPlane::stage, ::apply)
+int mi_session_change_controls(mi_session *s, const mi_session_control *h_changes, int count) {
+	const char *fn = "mi_session_change_controls";
+	if (!s) {
+		mi::set_error("%s: a null session", fn);
+		return MI_EINVAL;
+	}
+	mi::ControlChanges &cc = s->ctl.changes;
+	const int rc = mi::check_controls(fn, s->n, s->roster.flags.data(), MI_CTL_FLAGS | MI_CTL_GAIN, h_changes, count, cc.scratch);
+	if (rc != MI_OK) return rc;
+	for (int i = 0; i < count; ++i) cc.apply(h_changes[i], s->roster.flags.data());
+	return MI_OK;
+}
+
+int mi_session_set_reports(mi_session *s, uint32_t what) {
+	if (!s) {
+		mi::set_error("mi_session_set_reports: a null session");
+		return MI_EINVAL;
+	}
+	return s->ctl.set_reports("mi_session_set_reports", what, s->roster);
+}
+
+int mi_session_collected_report(mi_session *s, mi_session_report *out) {
+	if (!s || !out) {
+		mi::set_error("mi_session_collected_report: a null %s", s ? "report" : "session");
+		return MI_EINVAL;
+	}
+	out->nstreams = s->n, out->nconf = s->roster.nconf;
+	return s->ctl.collected("mi_session_collected_report", s->pipe.collected, &out->seq, &out->what, &out->levels, &out->winner, &out->max_lin,
+	                        &out->max_db);
 }
 
 int mi_session_member_count(const mi_session *s, int conference) {

@@ -549,6 +549,8 @@ void mi_volume_edit(mi_volume *v, VolumeEdit *out) {
 	out->energy[0] = v->d_energy[0], out->energy[1] = v->d_energy[1];
 }
 
+mi_volume_params *mi_volume_params_edit(mi_volume *v) { return v ? v->d_params : nullptr; } // (controls.hpp)
+
 extern "C" {
 
 void mi_volume_default_params(mi_volume_params *p) {
