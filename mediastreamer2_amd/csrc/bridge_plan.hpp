@@ -372,12 +372,14 @@ inline mi_bridge_leg seat_kind(const Plan &p, int s) {
 
 // mi_bridge_change_members' rules, without a device.  flags [p.n]: the pins' MI_MIX_* as the roster has them.  MI_OK with
 // ratio [count] -- the ratio byte of every JOIN's kind, 0 for a LEAVE --, or the refusal naming the entry; nothing is applied
-// here.  An open plan admits its `kinds` on every seat; any other plan admits on a seat that seat's own kind only.
-inline int check_changes(const Plan &p, const uint8_t *flags, const mi_bridge_change *ch, int count, std::vector<uint8_t> *ratio) {
+// here.  An open plan admits its `kinds` on every seat; any other plan admits on a seat that seat's own kind only.  scratch:
+// mi::check_seat_list's
+inline int check_changes(const Plan &p, const uint8_t *flags, const mi_bridge_change *ch, int count, std::vector<uint8_t> *ratio,
+                         std::vector<int32_t> *scratch = nullptr) {
 	MI_PLAN_ARG(flags && ratio && count >= 0 && (ch || count == 0));
 	const char *fn = "mi_bridge_change_members";
 	static_assert(MI_BRIDGE_JOIN == MI_SEAT_JOIN && MI_BRIDGE_LEAVE == MI_SEAT_LEAVE, "the public ops are the command's");
-	const int rc = mi::check_seat_list(fn, "MI_BRIDGE_JOIN (1) or MI_BRIDGE_LEAVE (2)", p.n, ch, count);
+	const int rc = mi::check_seat_list(fn, "MI_BRIDGE_JOIN (1) or MI_BRIDGE_LEAVE (2)", p.n, ch, count, scratch);
 	if (rc != MI_OK) return rc;
 	ratio->assign((size_t)count, 0);
 	for (int i = 0; i < count; ++i) {

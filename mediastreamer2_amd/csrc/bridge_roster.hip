@@ -17,28 +17,23 @@ __device__ __forceinline__ void zero_words(void *p, int words, int lane) {
 __global__ __launch_bounds__(64) void bridge_roster_kernel(RosterArgs a) {
 	const int i = blockIdx.x, lane = threadIdx.x;
 	if (i >= a.count) return;
-	const uint4 c = reinterpret_cast<const uint4 *>(a.cmd)[i]; // stream | op, ratio, codec, cls | len | flags
-	const int s = (int)c.x;
-	const unsigned op = c.y & 0xffu, ratio = (c.y >> 8) & 0xffu, codec = (c.y >> 16) & 0xffu;
+	const SeatFields c = load_seat(a.cmd, i);
+	const int s = c.stream;
+	const unsigned op = c.op;
 	if (s < 0 || s >= a.nstreams) return; // (the host has checked every entry: no store without its seat)
 	if (op & MI_SEAT_JOIN) {
 		if (lane == 0) {
-			if (a.ratio) a.ratio[s] = (uint8_t)ratio;
-			if (a.codec) a.codec[s] = (uint8_t)codec;
-			if (a.codec_pcm) a.codec_pcm[s] = (uint8_t)(codec & ~3u);
-			mi_volume_state st = {};
-			st.gain = st.target_gain = 1; // volume_init msvolume.c:92
-			st.ng_gain = 1;               // :112
-			a.vol.state[s] = st;
-			a.vol.energy[0][s] = a.vol.energy[1][s] = 0.f;
-			a.vol.win[s] = make_float2(0.f, -1.f); // the one-second window not started
-			a.flags[s] = (uint8_t)(c.w & 0xffu); // linked, active, output on -- unless a later mi_bridge_set_controls said otherwise
+			if (a.ratio) a.ratio[s] = (uint8_t)c.ratio;
+			if (a.codec) a.codec[s] = (uint8_t)c.codec;
+			if (a.codec_pcm) a.codec_pcm[s] = (uint8_t)(c.codec & ~3u);
+			fresh_meter(a.vol, s);
+			a.flags[s] = (uint8_t)c.flags; // linked, active, output on -- unless a later mi_bridge_set_controls said otherwise
 		}
 		// speex_resampler_init: both histories zero, over the stride the plan keeps for the longest filter of any kind
 		if (a.hist_in) zero_words(a.hist_in + (size_t)s * a.hin_stride, a.hin_stride >> 1, lane);
 		if (a.hist_out) zero_words(a.hist_out + (size_t)s * a.hout_stride, a.hout_stride >> 1, lane);
 	}
-	if ((op & MI_SEAT_LEAVE) && lane == 0) a.flags[s] = (uint8_t)(c.w & 0xffu); // 0, with the same proviso
+	if ((op & MI_SEAT_LEAVE) && lane == 0) a.flags[s] = (uint8_t)c.flags; // 0, with the same proviso
 	// an unplumbed pin's row is left alone by the tick: what the departed leg last heard must not linger in this slot
 	if (op & MI_SEAT_CLEAR) zero_words(a.out + (size_t)s * a.out_bytes, a.out_bytes >> 2, lane);
 }

@@ -139,6 +139,15 @@ struct VolumeEdit {
 	float *energy[2] = {nullptr, nullptr};
 };
 void mi_volume_edit(mi_volume *v, VolumeEdit *out);
+// seat s's meter as a NEW MSVolume has it (one lane; both roster kernels)
+__device__ __forceinline__ void fresh_meter(const VolumeEdit &v, int s) {
+	mi_volume_state st = {};
+	st.gain = st.target_gain = 1; // volume_init msvolume.c:92
+	st.ng_gain = 1;               // :112
+	v.state[s] = st;
+	v.energy[0][s] = v.energy[1][s] = 0.f;
+	v.win[s] = make_float2(0.f, -1.f); // the one-second window not started
+}
 struct MixerEdit {
 	uint8_t *flags = nullptr; // [nconf][mm] MI_MIX_*
 };
@@ -191,7 +200,6 @@ int mi_plc_check_rate(const char *fn, const char *what, int index, int rate);
 int mi_plc_create_legs(mi_ctx *c, int nstreams, const int32_t *h_rate, const uint8_t *h_kind, int pitch, mi_plc **out,
                        const int32_t *h_open_rate = nullptr, int nopen = 0);
 int mi_plc_process_legs(mi_plc *p, const uint8_t *d_in, size_t in_pitch, int16_t *d_pcm, size_t pitch, const uint8_t *d_mode);
-struct mi_seat_cmd;
 int mi_plc_class_of(const mi_plc *p, int stream, int rate);
 void mi_plc_seat(mi_plc *p, int stream, int cls, int kind);
 int mi_plc_apply_seats(mi_plc *p, const mi_seat_cmd *d_cmd, int count);

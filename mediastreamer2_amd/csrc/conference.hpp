@@ -1,6 +1,7 @@
 // conference.hpp -- MSAudioConference's bookkeeping that mi_session (session.hip) and mi_bridge (bridge.hip) share: host
 // code only.  mi::Roster (who is a member, in which order they joined, who is elected) is plain C++ and calls nothing in
-// the library; the helpers below it are the halves of the two control planes that go through an mi_volume.
+// the library; the helpers below it are the halves of the owners' read-outs and resets that go through an mi_volume.
+// mi::ConferenceBook (conference_book.hpp) holds the roster next to the changes on their way to the device.
 #pragma once
 #include <cmath>
 #include <cstdint>

@@ -1,21 +1,19 @@
-// control_changes.hpp -- control changes on their way to the device, the part mi_bridge_change_controls (bridge.hip) and
-// mi_session_change_controls (session.hip) share, next to seat_changes.hpp: host code only, plain C++ with no HIP in it
-// (tests/host/controls_check.cpp runs it alone on the CPU).  A change -- mute, listen-only, input gain, a seat's
+// control_changes.hpp -- control changes on their way to the device, next to seat_changes.hpp: mi_ctl_cmd, the one place that
+// says how the device unpacks it (load_ctl), the list checks, and mi::ControlChanges, which mi::ConferenceBook
+// (conference_book.hpp) drives for mi_bridge_change_controls and mi_session_change_controls alike.  But for load_ctl, host code
+// only, plain C++ with no HIP in it (tests/host/controls_check.cpp runs it alone on the CPU).  A change -- mute, listen-only, input gain, a seat's
 // mi_volume_params -- is applied by the tick submitted next, so between the call and that submit it is bookkeeping: the host's
 // mirrors of what the device will hold (mi::Roster::flags, and the gains and parameters here), which every setter updates at
 // once, the waiting ones too; per seat the fields that a call has touched since the last submit, merged; and the command row
 // the tick carries, staged AT SUBMIT from the mirrors -- so whoever spoke last before the submit has the last word, field by
 // field.  Also here: the threshold the device's election compares with (report_threshold).
 #pragma once
-#include <algorithm>
 #include <cmath>
-#include <cstdint>
 #include <cstring>
-#include <vector>
+#include <type_traits>
+#include <utility>
 
-#include "../../include/msmi355x.h"
-
-namespace mi { void set_error(const char *fmt, ...); }
+#include "seat_changes.hpp"
 
 // One control change as the device applies it (controls.hip): a pinned row of these per pipe slot, uploaded with the tick they
 // take effect in.  MI_CTL_JOINED is the library's own: the seat's place in its conference's joining order, which the report
@@ -37,6 +35,19 @@ struct mi_ctl_cmd {
 };
 static_assert(sizeof(mi_volume_params) == 60, "fifteen words");
 static_assert(sizeof(mi_ctl_cmd) == 80, "a command is five 16-byte loads");
+// (load_ctl's shifts: the word at 4 is what | flags << 8; controls.hip copies the fifteen words from 16 on)
+static_assert(offsetof(mi_ctl_cmd, stream) == 0 && offsetof(mi_ctl_cmd, what) == 4 && offsetof(mi_ctl_cmd, flags) == 5 &&
+                  offsetof(mi_ctl_cmd, gain) == 8 && offsetof(mi_ctl_cmd, joined) == 12 && offsetof(mi_ctl_cmd, params) == 16,
+              "load_ctl unpacks these offsets");
+
+#ifdef __HIPCC__
+// the head of command i of a row as controls_kernel reads it: the first 16-byte load, named
+struct CtlFields { int stream; unsigned what, flags; float gain; unsigned joined; };
+__device__ __forceinline__ CtlFields load_ctl(const mi_ctl_cmd *row, int i) {
+	const uint4 c = reinterpret_cast<const uint4 *>(row + i)[0];
+	return {(int)c.x, c.y & 0xffu, (c.y >> 8) & 0xffu, __uint_as_float(c.z), c.w};
+}
+#endif
 
 namespace mi {
 
@@ -53,7 +64,7 @@ inline float report_threshold() {
 
 // what holds of every control list before anything is applied.  Control: { int32_t stream; uint32_t what, flags; ... };
 // allowed: the MI_CTL_* bits the object serves; flags [n]: the roster's MI_MIX_*, earlier membership changes included; seen:
-// scratch with room for n (ControlChanges::scratch), so that a call of up to n entries allocates nothing
+// check_named_once's
 template <class Control>
 inline int check_controls(const char *fn, int n, const uint8_t *flags, unsigned allowed, const Control *ch, int count, std::vector<int32_t> &seen) {
 	if (count < 0 || (count > 0 && !ch)) return set_error("%s: %d changes at %s", fn, count, ch ? "h_changes" : "a null h_changes"), (int)MI_EINVAL;
@@ -70,23 +81,23 @@ inline int check_controls(const char *fn, int n, const uint8_t *flags, unsigned 
 			return set_error("%s: entry %d: MI_CTL_FLAGS on stream %d, which is no member", fn, i, c.stream), (int)MI_EINVAL;
 		seen.push_back(c.stream);
 	}
-	std::sort(seen.begin(), seen.end());
-	const auto twice = std::adjacent_find(seen.begin(), seen.end());
-	if (twice != seen.end()) {
-		int at = count - 1;
-		while (at > 0 && ch[at].stream != *twice) --at;
-		return set_error("%s: entry %d names stream %d a second time in one call", fn, at, *twice), (int)MI_EINVAL;
-	}
-	return MI_OK;
+	return check_named_once(fn, ch, count, seen);
 }
+
+// a public control record with a `params` field (mi_bridge_control; not mi_session_control: the two readers below are empty)
+template <class Control, class = void>
+struct carries_params : std::false_type {};
+template <class Control>
+struct carries_params<Control, std::void_t<decltype(std::declval<Control>().params)>> : std::true_type {};
 
 // MI_CTL_VOLUME's own rule (mi_bridge_set_volume_params'): a bridge has no far end to limit against
 template <class Control>
 inline int check_control_params(const char *fn, const Control *ch, int count) {
-	for (int i = 0; i < count; ++i)
-		if ((ch[i].what & MI_CTL_VOLUME) && ch[i].params.peer != -1)
-			return set_error("%s: entry %d (stream %d) names an echo-limiter peer (%d); a bridge has no far end to limit against", fn, i,
-			                 ch[i].stream, ch[i].params.peer), (int)MI_ENOTSUP;
+	if constexpr (carries_params<Control>::value)
+		for (int i = 0; i < count; ++i)
+			if ((ch[i].what & MI_CTL_VOLUME) && ch[i].params.peer != -1)
+				return set_error("%s: entry %d (stream %d) names an echo-limiter peer (%d); a bridge has no far end to limit against", fn, i,
+				                 ch[i].stream, ch[i].params.peer), (int)MI_ENOTSUP;
 	return MI_OK;
 }
 
@@ -95,7 +106,7 @@ struct ControlChanges {
 	std::vector<mi_volume_params> params; // [n] the seats' MSVolume parameters likewise; empty: the object has no setter for them
 	std::vector<uint8_t> what;            // [n] the fields a call has touched since the last submit
 	std::vector<int32_t> changed;         // the seats with what[s] != 0
-	std::vector<int32_t> scratch;         // check_controls'
+	std::vector<int32_t> scratch;         // the list checks' (check_named_once), the membership lists' too
 
 	void init(int n, const mi_volume_params *initial) { // initial: every seat's parameters at creation, or null
 		gain.assign((size_t)n, 1.0f);                   // mi_mixer_create's
@@ -128,9 +139,8 @@ struct ControlChanges {
 	}
 	template <class Control>
 	void apply_params(const Control &c) {
-		if (!(c.what & MI_CTL_VOLUME)) return;
-		params[(size_t)c.stream] = c.params;
-		note(c.stream, MI_CTL_VOLUME);
+		if constexpr (carries_params<Control>::value)
+			if (c.what & MI_CTL_VOLUME) params[(size_t)c.stream] = c.params, note(c.stream, MI_CTL_VOLUME);
 	}
 
 	// the command row of the tick about to be submitted, into the slot's pinned staging: every touched field as the mirrors hold

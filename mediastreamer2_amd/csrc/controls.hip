@@ -19,15 +19,15 @@ namespace {
 __global__ __launch_bounds__(64) void controls_kernel(ControlArgs a) {
 	const int i = blockIdx.x * 64 + threadIdx.x;
 	if (i >= a.count) return;
-	const uint4 *src = reinterpret_cast<const uint4 *>(a.cmd + i);
-	const uint4 head = src[0]; // stream | what, flags | gain | joined
-	const int s = (int)head.x;
-	const unsigned what = head.y & 0xffu;
+	const CtlFields c = load_ctl(a.cmd, i);
+	const int s = c.stream;
+	const unsigned what = c.what;
 	if (s < 0 || s >= a.nstreams) return; // (the host has checked every entry: no store without its seat)
-	if (what & MI_CTL_FLAGS) a.flags[s] = (uint8_t)((head.y >> 8) & 0xffu);
-	if (what & MI_CTL_GAIN) a.gain[s] = __uint_as_float(head.z);
-	if (what & MI_CTL_JOINED) a.joined[s] = head.w;
+	if (what & MI_CTL_FLAGS) a.flags[s] = (uint8_t)c.flags;
+	if (what & MI_CTL_GAIN) a.gain[s] = c.gain;
+	if (what & MI_CTL_JOINED) a.joined[s] = c.joined;
 	if ((what & MI_CTL_VOLUME) && a.params) {
+		const uint4 *src = reinterpret_cast<const uint4 *>(a.cmd + i); // the parameters: the four loads behind the head
 		const uint4 p0 = src[1], p1 = src[2], p2 = src[3], p3 = src[4];
 		uint32_t *dst = reinterpret_cast<uint32_t *>(a.params + s); // 60 bytes at a 60-byte pitch: words
 		dst[0] = p0.x, dst[1] = p0.y, dst[2] = p0.z, dst[3] = p0.w;

@@ -479,15 +479,15 @@ struct PlcSeatArgs {
 __global__ __launch_bounds__(64) void plc_seats_kernel(PlcSeatArgs a) {
 	const int i = blockIdx.x, lane = threadIdx.x;
 	if (i >= a.count) return;
-	const uint4 c = reinterpret_cast<const uint4 *>(a.cmd)[i]; // stream | op, ratio, codec, cls | len | flags
-	const int s = (int)c.x;
-	if (!(c.y & MI_SEAT_JOIN) || s < 0 || s >= a.nstreams) return;
+	const SeatFields c = load_seat(a.cmd, i);
+	const int s = c.stream;
+	if (!(c.op & MI_SEAT_JOIN) || s < 0 || s >= a.nstreams) return;
 	int k = 0, r = s;
 	if (a.tag) {
-		k = (int)(c.y >> 24);
+		k = (int)c.cls;
 		if (k >= a.nclass) return; // (the host names classes it has built)
 		r = a.rank[s];
-		if (lane == 0) a.tag[s] = (uint8_t)((unsigned)k | ((c.y >> 16) & 3u) << 4), a.len[s] = (int32_t)c.z;
+		if (lane == 0) a.tag[s] = (uint8_t)((unsigned)k | (c.codec & 3u) << 4), a.len[s] = c.len;
 	}
 	const PlcSeatClass &q = a.cls[__builtin_amdgcn_readfirstlane(k)];
 	const size_t at = (size_t)r;

@@ -1,10 +1,12 @@
-// seat_changes.hpp -- membership changes on their way to the device, the part mi_bridge_change_members (bridge.hip) and
-// mi_session_change_members (session.hip) share: host code only, plain C++ with no HIP in it
+// seat_changes.hpp -- membership changes on their way to the device: mi_seat_cmd, the one place that says how the device
+// unpacks it (load_seat), the list checks, and mi::SeatChanges, which mi::ConferenceBook (conference_book.hpp) drives for
+// mi_bridge_change_members and mi_session_change_members alike.  But for load_seat, host code only, plain C++ with no HIP in it
 // (tests/host/session_open_check.cpp runs it alone on the CPU).  A change is applied by the tick submitted next, so between
 // the call and that submit it is bookkeeping: what the calls since the last submit left per seat, merged; the command row the
 // tick carries; and the seats whose output row is still to be cleared in slots to come.
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -26,15 +28,40 @@ struct mi_seat_cmd {
 	uint8_t pad[3];
 };
 static_assert(sizeof(mi_seat_cmd) == 16, "a command is one 16-byte load");
+// (load_seat's shifts: the word at 4 is op | ratio << 8 | codec << 16 | cls << 24, the one at 12 starts with flags)
+static_assert(offsetof(mi_seat_cmd, stream) == 0 && offsetof(mi_seat_cmd, op) == 4 && offsetof(mi_seat_cmd, ratio) == 5 && offsetof(mi_seat_cmd, codec) == 6 &&
+                  offsetof(mi_seat_cmd, cls) == 7 && offsetof(mi_seat_cmd, len) == 8 && offsetof(mi_seat_cmd, flags) == 12, "load_seat unpacks these offsets");
+
+#ifdef __HIPCC__
+// command i of a row as the kernels read it (bridge_roster.hip, session_roster.hip, plc.hip): the one 16-byte load, named
+struct SeatFields { int stream, len; unsigned op, ratio, codec, cls, flags; };
+__device__ __forceinline__ SeatFields load_seat(const mi_seat_cmd *row, int i) {
+	const uint4 c = reinterpret_cast<const uint4 *>(row)[i];
+	return {(int)c.x, (int)c.z, c.y & 0xffu, (c.y >> 8) & 0xffu, (c.y >> 16) & 0xffu, c.y >> 24, c.w & 0xffu};
+}
+#endif
 
 namespace mi {
 
+// no seat twice in one call, or the refusal naming the later entry.  seen: every entry's stream, gathered by the caller's own
+// pass into scratch with room for n (mi::ControlChanges::scratch), so that a call of up to n entries allocates nothing
+template <class Entry>
+inline int check_named_once(const char *fn, const Entry *ch, int count, std::vector<int32_t> &seen) {
+	std::sort(seen.begin(), seen.end());
+	const auto twice = std::adjacent_find(seen.begin(), seen.end());
+	if (twice == seen.end()) return MI_OK;
+	int at = count - 1;
+	while (at > 0 && ch[at].stream != *twice) --at;
+	return set_error("%s: entry %d names stream %d a second time in one call", fn, at, *twice), (int)MI_EINVAL;
+}
+
 // what holds of every change list before any entry is looked at for itself: each names a seat that exists and one of the two
 // ops (MI_SEAT_JOIN and MI_SEAT_LEAVE are the public values), and no seat twice.  Change: { int32_t stream, op; ... }.
-// names: the ops as the entry point's header spells them, for the message
+// names: the ops as the entry point's header spells them, for the message; scratch: check_named_once's, or null: the call's own
 template <class Change>
-inline int check_seat_list(const char *fn, const char *names, int n, const Change *ch, int count) {
-	std::vector<int32_t> seen;
+inline int check_seat_list(const char *fn, const char *names, int n, const Change *ch, int count, std::vector<int32_t> *scratch = nullptr) {
+	std::vector<int32_t> own, &seen = scratch ? *scratch : own;
+	seen.clear();
 	for (int i = 0; i < count; ++i) {
 		const Change &c = ch[i];
 		if (c.stream < 0 || c.stream >= n) return set_error("%s: entry %d names stream %d of %d", fn, i, c.stream, n), (int)MI_EINVAL;
@@ -42,21 +69,15 @@ inline int check_seat_list(const char *fn, const char *names, int n, const Chang
 			return set_error("%s: entry %d (stream %d) has op %d; %s", fn, i, c.stream, c.op, names), (int)MI_EINVAL;
 		seen.push_back(c.stream);
 	}
-	std::sort(seen.begin(), seen.end());
-	const auto twice = std::adjacent_find(seen.begin(), seen.end());
-	if (twice != seen.end()) {
-		int at = count - 1;
-		while (at > 0 && ch[at].stream != *twice) --at;
-		return set_error("%s: entry %d names stream %d a second time in one call", fn, at, *twice), (int)MI_EINVAL;
-	}
-	return MI_OK;
+	return check_named_once(fn, ch, count, seen);
 }
 
 // a list of uniform seats (mi_session_change_members): the above, and a LEAVE names a member.  flags [n]: the roster's MI_MIX_*
 template <class Change>
-inline int check_uniform_changes(const char *fn, const char *names, int n, const uint8_t *flags, const Change *ch, int count) {
+inline int check_uniform_changes(const char *fn, const char *names, int n, const uint8_t *flags, const Change *ch, int count,
+                                 std::vector<int32_t> *scratch = nullptr) {
 	if (count < 0 || (count > 0 && !ch)) return set_error("%s: %d changes at %s", fn, count, ch ? "h_changes" : "a null h_changes"), (int)MI_EINVAL;
-	const int rc = check_seat_list(fn, names, n, ch, count);
+	const int rc = check_seat_list(fn, names, n, ch, count, scratch);
 	if (rc != MI_OK) return rc;
 	for (int i = 0; i < count; ++i)
 		if (ch[i].op == MI_SEAT_LEAVE && !(flags[ch[i].stream] & MI_MIX_LINKED))

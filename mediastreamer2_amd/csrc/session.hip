@@ -9,9 +9,9 @@
 // Three HIP streams: uploads, kernels (the context's stream), downloads.  A tick's inputs go up while the previous
 // tick computes and the one before comes down; events order the three (mi::TickPipe, tick_pipe.hpp), hipGraphs (one per
 // buffer slot) replay the kernel sequence.  Pinned host buffers belong to the session: the caller fills / reads them in place.
+// Membership, controls and reports -- waiting or carried by the ticks -- are mi::ConferencePlane's (controls.hpp); here is what
+// is the session's own: launch_seats, mi_session_reset_streams, the rows a departed leg leaves behind, two meter read-outs.
 #include "common.hpp"
-#include "conference.hpp"
-#include "tick_pipe.hpp"
 
 #include "../../include/msmi355x_session.h"
 #include "../../include/msmi355x_session_controls.h"
@@ -50,14 +50,8 @@ struct mi_session {
 	int rounds = 0;                 // the canceller's frames of a tick, at most (max_frames of its call)
 	uint8_t *d_reset_gate = nullptr; // [n] mi_session_reset_streams: 1 = the leg's reference FIFO gets its delay again
 	mi_graph *graph[SLOTS] = {};
-	mi::Roster roster; // conference membership / active-speaker election (MSAudioConference, src/voip/audioconference.c)
-	// membership changes (mi_session_change_members): the calls' bookkeeping (seat_changes.hpp) and per slot the pinned command
-	// row the tick carries, its device copy and its length
-	mi::SeatChanges changes;
-	mi_seat_cmd *h_cmd[SLOTS] = {}, *d_cmd[SLOTS] = {};
-	int ncmd[SLOTS] = {};
-	// mute, gain and the reports without a wait (mi_session_change_controls, mi_session_set_reports): controls.hpp
-	mi::ControlPlane ctl;
+	// conference membership, controls and reports (MSAudioConference), the waiting calls' and what travels with the ticks: controls.hpp
+	mi::ConferencePlane conf;
 	int lead_unit = 0, lead_phases = 0; // cfg.stagger: mi_aec_stagger_info's, what a fresh seat's queues lead with
 };
 
@@ -133,12 +127,10 @@ int run_tick_kernels(mi_session *s, int slot) { // everything on the context's s
 	return MI_OK;
 }
 
-// a tick that carries membership changes: the session's own state in one launch, the concealer's in one of plc.hip's.  Called
-// inside the pipe's kernels(slot), behind the wait for the download that last read this slot's output rows -- only there is
-// zeroing a row free of a race with it -- and in front of the slot's graph, never inside it
-int apply_changes(mi_session *s, int slot) {
+// a tick that carries membership changes: the session's own state in one launch (mi::ConferencePlane::apply's seat_launch)
+int launch_seats(mi_session *s, int slot, const mi_seat_cmd *d_cmd, int count) {
 	SessionRosterArgs ra = {};
-	ra.cmd = s->d_cmd[slot], ra.count = s->ncmd[slot], ra.nstreams = s->n;
+	ra.cmd = d_cmd, ra.count = count, ra.nstreams = s->n;
 	mi_aec_edit(s->aec, &ra.aec);
 	mi_resampler_edit(s->rs, &ra.rs_in);
 	mi_resampler_edit(s->rs_out, &ra.rs_out);
@@ -152,9 +144,7 @@ int apply_changes(mi_session *s, int slot) {
 	for (int i = 0; i < SLOTS; ++i) ra.mix[i] = s->d_mix[i];
 	ra.mix_len = s->len;
 	ra.out = reinterpret_cast<uint8_t *>(s->d_out[slot]), ra.out_bytes = (int)s->out_bytes;
-	const int rc = mi_session_roster_launch(ra, s->ctx->stream);
-	if (rc != MI_OK || !s->plc) return rc;
-	return mi_plc_apply_seats(s->plc, s->d_cmd[slot], s->ncmd[slot]);
+	return mi_session_roster_launch(ra, s->ctx->stream);
 }
 
 } // namespace
@@ -190,10 +180,8 @@ void mi_session_destroy(mi_session *s) {
 		if (s->d_mix[i]) mi_dev_free(c, s->d_mix[i]);
 		if (s->h_ev[i]) mi_host_free(c, s->h_ev[i]);
 		if (s->d_ev[i]) mi_dev_free(c, s->d_ev[i]);
-		if (s->h_cmd[i]) mi_host_free(c, s->h_cmd[i]);
-		if (s->d_cmd[i]) mi_dev_free(c, s->d_cmd[i]);
 	}
-	s->ctl.destroy();
+	s->conf.destroy();
 	void *dv[] = {s->d_up, s->d_tick, s->d_pcm, s->d_down, s->d_zero, s->d_evlen, s->d_reset_gate};
 	for (void *p : dv)
 		if (p) mi_dev_free(c, p);
@@ -223,8 +211,6 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 	s->ctx = s->pipe.ctx = ctx;
 	s->cfg = *cfg;
 	s->n = cfg->nstreams;
-	s->roster.init(s->n, cfg->members_per_conference);
-	s->changes.init(s->n, SLOTS);
 	s->in_len = cfg->in_rate / 100;
 	s->len = cfg->rate / 100;
 	const bool down = cfg->out_rate != 0 && cfg->out_rate != cfg->rate;
@@ -255,7 +241,7 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 		std::vector<mi_volume_params> all((size_t)s->n, p);
 		if ((rc = mi_volume_set_params(s->vol, 0, s->n, all.data())) != MI_OK) return fail(rc);
 	}
-	if ((rc = mi_mixer_create(ctx, s->roster.nconf, cfg->members_per_conference, s->len, &s->mix)) != MI_OK) return fail(rc);
+	if ((rc = mi_mixer_create(ctx, s->n / cfg->members_per_conference, cfg->members_per_conference, s->len, &s->mix)) != MI_OK) return fail(rc);
 	// capacities: whole frames (the canceller reads / writes the rings frame-wise, mi_aec_process_fifos), two ticks + two
 	// frames, + one frame for the lead of a staggered leg (its output queue stands one frame fuller)
 	const int cap = (2 * s->len + (cfg->stagger ? 3 : 2) * s->frame + s->frame - 1) / s->frame * s->frame;
@@ -272,9 +258,6 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 		s->d_mic[i] = (int16_t *)mi_dev_alloc(ctx, n * s->mic_bytes);
 		s->d_out[i] = (int16_t *)mi_dev_alloc(ctx, n * s->out_bytes);
 		if (!s->h_mic[i] || !s->h_out[i] || !s->d_mic[i] || !s->d_out[i]) return fail(MI_ENOMEM);
-		// every seat may change in one tick
-		s->h_cmd[i] = (mi_seat_cmd *)mi_host_alloc(ctx, n * sizeof(mi_seat_cmd)), s->d_cmd[i] = (mi_seat_cmd *)mi_dev_alloc(ctx, n * sizeof(mi_seat_cmd));
-		if (!s->h_cmd[i] || !s->d_cmd[i]) return fail(MI_ENOMEM);
 		if (!cfg->ref_loopback) {
 			s->h_ref[i] = (int16_t *)mi_host_alloc(ctx, n * s->ref_bytes);
 			s->d_ref[i] = (int16_t *)mi_dev_alloc(ctx, n * s->ref_bytes);
@@ -312,7 +295,8 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 	}
 	if (cfg->stagger && (rc = mi_aec_stagger_fifos(s->aec, s->f_mic, s->f_ref, s->len, 0, s->n)) != MI_OK) return fail(rc);
 	if (cfg->stagger && (rc = mi_aec_stagger_info(s->aec, s->len, &s->lead_unit, &s->lead_phases)) != MI_OK) return fail(rc);
-	if ((rc = s->ctl.create(ctx, s->roster, SLOTS, nullptr)) != MI_OK) return fail(rc);
+	// (no initial parameters: the session's meters have no setter, so its controls carry no MI_CTL_VOLUME)
+	if ((rc = s->conf.create(ctx, s->n, cfg->members_per_conference, SLOTS, nullptr, s->vol, s->mix, s->plc)) != MI_OK) return fail(rc);
 	MI_HIP(hipStreamSynchronize(ctx->stream));
 	*out = s;
 	return MI_OK;
@@ -364,25 +348,20 @@ int mi_session_submit(mi_session *s) {
 	}
 	mi_ctx *c = s->ctx;
 	const size_t n = (size_t)s->n;
-	const int at = s->pipe.next_slot();
-	s->ncmd[at] = s->changes.stage(s->h_cmd[at], s->roster.flags.data());
-	s->ctl.stage(at, s->pipe.submitted, s->roster, s->changes);
+	s->conf.stage(s->pipe.next_slot(), s->pipe.submitted);
 	const int rc = s->pipe.submit(
 	    [&](int slot) {
-		    if (s->ncmd[slot])
-			    MI_HIP(hipMemcpyAsync(s->d_cmd[slot], s->h_cmd[slot], (size_t)s->ncmd[slot] * sizeof(mi_seat_cmd), hipMemcpyHostToDevice, s->pipe.s_up));
-		    if (s->ctl.upload(slot, s->pipe.s_up) != MI_OK) return (int)MI_ENODEV;
+		    if (s->conf.upload(slot, s->pipe.s_up) != MI_OK) return (int)MI_ENODEV;
 		    MI_HIP(hipMemcpyAsync(s->d_mic[slot], s->h_mic[slot], n * s->mic_bytes, hipMemcpyHostToDevice, s->pipe.s_up));
 		    if (s->ref_bytes) MI_HIP(hipMemcpyAsync(s->d_ref[slot], s->h_ref[slot], n * s->ref_bytes, hipMemcpyHostToDevice, s->pipe.s_up));
 		    if (s->plc) MI_HIP(hipMemcpyAsync(s->d_ev[slot], s->h_ev[slot], n, hipMemcpyHostToDevice, s->pipe.s_up));
 		    return MI_OK;
 	    },
 	    [&](int slot) {
-		    int rc;
-		    if (s->ncmd[slot] && (rc = apply_changes(s, slot)) != MI_OK) return rc;
-		    if ((rc = s->ctl.apply(slot, s->mix, s->vol, false)) != MI_OK) return rc; // membership first, then controls
+		    int rc = s->conf.apply(slot, [&](const mi_seat_cmd *d_cmd, int count) { return launch_seats(s, slot, d_cmd, count); });
+		    if (rc != MI_OK) return rc;
 		    // the report's launch follows the tick's kernels -- behind the slot's graph, never inside it
-		    if (!s->cfg.use_graphs) return (rc = run_tick_kernels(s, slot)) != MI_OK ? rc : s->ctl.report(slot, s->mix, s->vol);
+		    if (!s->cfg.use_graphs) return (rc = run_tick_kernels(s, slot)) != MI_OK ? rc : s->conf.report(slot);
 		    if (!s->graph[slot]) {
 			    // first use of the slot: run eagerly once is not an option (state would advance twice), so capture directly
 			    if ((rc = mi_ctx_capture_begin(c)) != MI_OK) return rc;
@@ -393,13 +372,13 @@ int mi_session_submit(mi_session *s) {
 			    if (rc2 != MI_OK) return rc2;
 			    s->graph[slot] = g;
 		    }
-		    return (rc = mi_graph_launch(s->graph[slot])) != MI_OK ? rc : s->ctl.report(slot, s->mix, s->vol);
+		    return (rc = mi_graph_launch(s->graph[slot])) != MI_OK ? rc : s->conf.report(slot);
 	    },
 	    [&](int slot) {
 		    MI_HIP(hipMemcpyAsync(s->h_out[slot], s->d_out[slot], n * s->out_bytes, hipMemcpyDeviceToHost, s->pipe.s_down));
-		    return s->ctl.download(slot, s->pipe.s_down);
+		    return s->conf.download(slot, s->pipe.s_down);
 	    });
-	if (rc == MI_OK) s->changes.submitted(), s->ctl.submitted();
+	if (rc == MI_OK) s->conf.submitted();
 	return rc;
 }
 
@@ -415,122 +394,64 @@ int mi_session_collect(mi_session *s, const int16_t **h_out) {
 
 int mi_session_in_flight(const mi_session *s) { return s ? s->pipe.in_flight() : 0; }
 
-// ---- conference control plane (what MSAudioConference drives through the mixer's methods, src/voip/audioconference.c:
-// mute = MS_AUDIO_MIXER_SET_ACTIVE 0, listen-only = MS_AUDIO_MIXER_ENABLE_OUTPUT ..., per-member input gain) and the level
-// meter read-out (MS_VOLUME_GET_LINEAR) an active-speaker detector polls.  Both wait for the ticks already submitted.
+// ---- conference control plane: every call's body is mi::ConferencePlane's (controls.hpp), the session brings what is its own
 int mi_session_set_controls(mi_session *s, const uint8_t *h_flags, const float *h_gain) {
 	MI_CHECK_ARG(s && (h_flags || h_gain));
-	if (h_flags) s->roster.set_flags(h_flags);
-	if (h_gain) s->ctl.changes.set_gains(h_gain);
-	return mi_mixer_set_controls(s->mix, h_flags, h_gain); // [nconf][members] == [nstreams]
+	return s->conf.set_controls(h_flags, h_gain);
 }
 
-// ms_audio_conference_add_member (src/voip/audioconference.c:322-345): a NEW endpoint joins -- its own filters are fresh
-// (resampler history, canceller, meter, FIFOs: mi_session_reset_streams), its mixer pin becomes linked / active / output
-// enabled.  The conference graph is detached and re-attached around this (:325-327): the other members' filters keep
-// their state (their MSFilter objects survive) and so do their streams here.
 int mi_session_add_member(mi_session *s, int stream) {
 	MI_CHECK_ARG(s && stream >= 0 && stream < s->n);
-	if (s->roster.is_member(stream)) {
-		mi::set_error("mi_session_add_member: stream %d is a member already", stream);
-		return MI_EINVAL;
-	}
-	int rc = mi_session_reset_streams(s, stream, 1);
-	if (rc != MI_OK) return rc;
-	s->roster.join(stream);
-	if ((rc = s->ctl.joined_waiting(stream, s->roster)) != MI_OK) return rc;
-	return mi_mixer_set_controls(s->mix, s->roster.flags.data(), nullptr);
+	return s->conf.add_member("mi_session_add_member", stream, [&](int seat) { return mi_session_reset_streams(s, seat, 1); });
 }
 
-// ms_audio_conference_remove_member (:366-374): the pin is unplumbed -- it neither contributes nor receives; the row of
-// its output is left alone from now on (zeros in a fresh download buffer).  The others carry on.
+// (what the departed leg last heard: its output rows and, where the mix at `rate` is kept, its rows there)
 int mi_session_remove_member(mi_session *s, int stream) {
 	MI_CHECK_ARG(s && stream >= 0 && stream < s->n);
-	if (!s->roster.leave(stream)) {
-		mi::set_error("mi_session_remove_member: stream %d is no member", stream);
-		return MI_EINVAL;
-	}
-	const int rc = mi_mixer_set_controls(s->mix, s->roster.flags.data(), nullptr);
-	if (rc != MI_OK) return rc;
-	if (s->ctx->activate() != MI_OK) return MI_ENODEV;
-	// the mixer leaves an unplumbed pin's row alone: what the departed leg last heard must not linger in the buffers
-	MI_HIP(hipStreamSynchronize(s->ctx->stream));
-	if (s->pipe.s_down) MI_HIP(hipStreamSynchronize(s->pipe.s_down));
-	for (int i = 0; i < SLOTS; ++i) {
-		if (s->d_out[i]) MI_HIP(hipMemsetAsync((uint8_t *)s->d_out[i] + (size_t)stream * s->out_bytes, 0, s->out_bytes, s->ctx->stream));
-		if (s->d_mix[i]) MI_HIP(hipMemsetAsync(s->d_mix[i] + (size_t)stream * s->len, 0, (size_t)s->len * 2, s->ctx->stream));
-		if (s->h_out[i]) memset((uint8_t *)s->h_out[i] + (size_t)stream * s->out_bytes, 0, s->out_bytes);
-	}
-	return MI_OK;
+	return s->conf.remove_member("mi_session_remove_member", stream, s->pipe, [&](int seat) -> int {
+		for (int i = 0; i < SLOTS; ++i) {
+			if (s->d_out[i]) MI_HIP(hipMemsetAsync((uint8_t *)s->d_out[i] + (size_t)seat * s->out_bytes, 0, s->out_bytes, s->ctx->stream));
+			if (s->d_mix[i]) MI_HIP(hipMemsetAsync(s->d_mix[i] + (size_t)seat * s->len, 0, (size_t)s->len * 2, s->ctx->stream));
+			if (s->h_out[i]) memset((uint8_t *)s->h_out[i] + (size_t)seat * s->out_bytes, 0, s->out_bytes);
+		}
+		return MI_OK;
+	});
 }
 
-// no stream, event or device synchronise, no blocking copy and no allocation on this path: the roster answers at once, the
-// device follows with the next tick submitted (mi::SeatChanges::stage, apply_changes)
+// no stream, event or device synchronise, no blocking copy and no allocation on these two paths: the book answers at once, the
+// device follows with the next tick submitted (mi::ConferenceBook; mi::ConferencePlane::stage, ::apply)
 int mi_session_change_members(mi_session *s, const mi_session_change *h_changes, int count) {
 	static_assert(MI_SESSION_JOIN == MI_SEAT_JOIN && MI_SESSION_LEAVE == MI_SEAT_LEAVE, "the public ops are the command's");
 	const char *fn = "mi_session_change_members";
-	if (!s) {
-		mi::set_error("%s: a null session", fn);
-		return MI_EINVAL;
-	}
-	const int rc = mi::check_uniform_changes(fn, "MI_SESSION_JOIN (1) or MI_SESSION_LEAVE (2)", s->n, s->roster.flags.data(), h_changes, count);
-	if (rc != MI_OK) return rc;
-	for (int i = 0; i < count; ++i) {
-		const mi_session_change &c = h_changes[i];
-		const bool was = s->roster.leave(c.stream); // a seat that is taken is replaced: leave + join
-		mi::SeatChanges::Pending &p = s->changes.note(c.stream, (uint8_t)c.op, was);
-		if (c.op == MI_SESSION_LEAVE) continue;
-		s->roster.join(c.stream); // a NEW endpoint: the last of its conference's list
-		p.len = s->in_len;        // (the concealer's batch is uniform: class 0, its tick the session's)
-	}
-	return MI_OK;
+	if (!s) return mi::set_error("%s: a null session", fn), (int)MI_EINVAL;
+	return s->conf.book.change_uniform_members(fn, "MI_SESSION_JOIN (1) or MI_SESSION_LEAVE (2)", h_changes, count, s->in_len);
 }
 
-// no stream, event or device synchronise, no blocking copy and no allocation on this path: the mirrors answer at once, the
-// device follows with the next tick submitted (mi::ControlPlane::stage, ::apply)
 int mi_session_change_controls(mi_session *s, const mi_session_control *h_changes, int count) {
 	const char *fn = "mi_session_change_controls";
-	if (!s) {
-		mi::set_error("%s: a null session", fn);
-		return MI_EINVAL;
-	}
-	mi::ControlChanges &cc = s->ctl.changes;
-	const int rc = mi::check_controls(fn, s->n, s->roster.flags.data(), MI_CTL_FLAGS | MI_CTL_GAIN, h_changes, count, cc.scratch);
-	if (rc != MI_OK) return rc;
-	for (int i = 0; i < count; ++i) cc.apply(h_changes[i], s->roster.flags.data());
-	return MI_OK;
+	if (!s) return mi::set_error("%s: a null session", fn), (int)MI_EINVAL;
+	return s->conf.book.change_controls(fn, h_changes, count);
 }
 
 int mi_session_set_reports(mi_session *s, uint32_t what) {
-	if (!s) {
-		mi::set_error("mi_session_set_reports: a null session");
-		return MI_EINVAL;
-	}
-	return s->ctl.set_reports("mi_session_set_reports", what, s->roster);
+	if (!s) return mi::set_error("mi_session_set_reports: a null session"), (int)MI_EINVAL;
+	return s->conf.set_reports("mi_session_set_reports", what);
 }
 
 int mi_session_collected_report(mi_session *s, mi_session_report *out) {
-	if (!s || !out) {
-		mi::set_error("mi_session_collected_report: a null %s", s ? "report" : "session");
-		return MI_EINVAL;
-	}
-	out->nstreams = s->n, out->nconf = s->roster.nconf;
-	return s->ctl.collected("mi_session_collected_report", s->pipe.collected, &out->seq, &out->what, &out->levels, &out->winner, &out->max_lin,
-	                        &out->max_db);
+	if (!s || !out) return mi::set_error("mi_session_collected_report: a null %s", s ? "report" : "session"), (int)MI_EINVAL;
+	return s->conf.collected("mi_session_collected_report", s->pipe.collected, out);
 }
 
-int mi_session_member_count(const mi_session *s, int conference) {
-	if (!s || conference < 0 || conference >= s->roster.nconf) return MI_EINVAL;
-	return s->roster.count(conference);
-}
+int mi_session_member_count(const mi_session *s, int conference) { return s ? s->conf.book.member_count(conference) : (int)MI_EINVAL; }
 
-// ms_audio_conference_process_events' election in mixer mode (:436-452, mi::Roster::elect).  now_ms: the caller's clock
-// (the ticker's time); not read (mi::active_speakers).
+// ms_audio_conference_process_events' election in mixer mode (:436-452, mi::Roster::elect).  now_ms: the caller's clock; not
+// read (mi::active_speakers).  A seat that has joined since the last submit reads as a fresh meter
 int mi_session_active_speakers(mi_session *s, uint64_t now_ms, int32_t *h_winner, float *h_max_db) {
 	MI_CHECK_ARG(s && h_winner);
 	(void)now_ms;
-	const std::vector<int32_t> fresh = s->changes.joining();
-	return mi::active_speakers(s->vol, s->roster, h_winner, h_max_db, &fresh);
+	const std::vector<int32_t> fresh = s->conf.book.joining();
+	return mi::active_speakers(s->vol, s->conf.book.roster, h_winner, h_max_db, &fresh);
 }
 
 // A call leg leaves and another takes its place: every per-stream state of the chain goes back to its initial value
@@ -565,7 +486,7 @@ int mi_session_reset_streams(mi_session *s, int first, int count) {
 
 int mi_session_get_levels(mi_session *s, float *h_linear) {
 	MI_CHECK_ARG(s && h_linear);
-	const std::vector<int32_t> fresh = s->changes.joining();
+	const std::vector<int32_t> fresh = s->conf.book.joining();
 	return mi::get_levels(s->vol, s->n, h_linear, &fresh);
 }
 

@@ -48,9 +48,9 @@ __device__ __forceinline__ void fresh_resampler(const ResamplerEdit &r, int s, i
 __global__ __launch_bounds__(RT) void session_roster_kernel(SessionRosterArgs a) {
 	const int i = blockIdx.x, t = threadIdx.x;
 	if (i >= a.count) return;
-	const uint4 c = reinterpret_cast<const uint4 *>(a.cmd)[i]; // stream | op, ratio, codec, cls | len | flags
-	const int s = (int)c.x;
-	const unsigned op = c.y & 0xffu;
+	const SeatFields c = load_seat(a.cmd, i);
+	const int s = c.stream;
+	const unsigned op = c.op;
 	if (s < 0 || s >= a.nstreams) return; // (the host has checked every entry: no store without its seat)
 	if (op & MI_SEAT_JOIN) {
 		// speex_echo_state_init: the filters and the far end's history zero, the rest from the template
@@ -66,18 +66,11 @@ __global__ __launch_bounds__(RT) void session_roster_kernel(SessionRosterArgs a)
 		fresh_fifo(a.f_mic, s, lead, t);
 		fresh_fifo(a.f_ref, s, a.ref_delay + lead, t);
 		fresh_fifo(a.f_out, s, 0, t);
-		if (t == 0) {
-			mi_volume_state st = {};
-			st.gain = st.target_gain = 1; // volume_init msvolume.c:92
-			st.ng_gain = 1;               // :112
-			a.vol.state[s] = st;
-			a.vol.energy[0][s] = a.vol.energy[1][s] = 0.f;
-			a.vol.win[s] = make_float2(0.f, -1.f); // the one-second window not started
-		}
+		if (t == 0) fresh_meter(a.vol, s);
 	}
 	if (op & (MI_SEAT_JOIN | MI_SEAT_LEAVE)) {
 		// linked, active, output on / unplumbed -- unless a later mi_session_set_controls said otherwise
-		if (t == 0) a.flags[s] = (uint8_t)(c.w & 0xffu);
+		if (t == 0) a.flags[s] = (uint8_t)c.flags;
 		// the kept mix is the next tick's far end (ref_loopback) and the encoder's input: nothing was sent to a new leg yet, and
 		// what a departed one last heard must not linger.  Only the context's stream touches these rows
 		for (int k = 0; k < SESSION_ROSTER_SLOTS; ++k)

@@ -2,7 +2,7 @@
 """What steering and observing a running bridge costs at a size a user runs: 1024 conferences x 32 legs of 8 kHz mu-law
 (mi_bridge_create), three ticks in flight.  Writes profiles/bridge_controls.md (or --out).
 
-    python scripts/bridge_controls_probe.py [--reps 200] [--ticks 600] [--out profiles/bridge_controls.md]
+    python scripts/bridge_controls_probe.py [--reps 200] [--ticks 600] [--out profiles/bridge_controls.md] [--tree DIR]
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python scripts/bridge_controls_probe.py --trace [--ticks 200]
     python scripts/bridge_controls_probe.py --summarise <dir> [--ticks 200]      (kernel names and counts of that trace)
 
@@ -14,7 +14,8 @@ Figures (the baselines are the waiting calls in the same process):
   3. the tick's device time by HIP events on the context's stream around the submit, pipe drained before: reports off, speakers,
      speakers + levels;
   4. ticks per second sustained with a poll after every tick, both ways.
---trace: `ticks` ticks without a control change and with reports off, for a kernel trace of this command."""
+--trace: `ticks` ticks without a control change and with reports off, for a kernel trace of this command.
+--tree: the checkout whose mediastreamer2_amd is loaded (default: this one), so that two builds can alternate in one job."""
 import argparse
 import csv
 import ctypes as C
@@ -27,7 +28,6 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 NCONF, MM = 1024, 32
@@ -49,11 +49,13 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--ticks", type=int, default=600)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bridge_controls.md"))
+    ap.add_argument("--tree", default=ROOT, help="the checkout whose mediastreamer2_amd is loaded")
     ap.add_argument("--trace", action="store_true", help="ticks without control changes, reports off, for a kernel trace")
     ap.add_argument("--summarise", metavar="DIR", help="kernel names and counts of the kernel trace under DIR; nothing runs")
     a = ap.parse_args()
     if a.summarise:
         return summarise(a.summarise, a.ticks)
+    sys.path.insert(0, os.path.abspath(a.tree))
 
     import torch
 

@@ -1,7 +1,7 @@
-// controls_check.cpp -- csrc/control_changes.hpp, the host's bookkeeping of control changes that mi_bridge_change_controls and
-// mi_session_change_controls share, run alone with mi::Roster (csrc/conference.hpp) and mi::SeatChanges (csrc/seat_changes.hpp),
-// without a GPU or the library (tests/test_controls_cpu.py builds this with the address and undefined-behaviour sanitizers and
-// reads its lines):
+// controls_check.cpp -- mi::ConferenceBook (csrc/conference_book.hpp), the host's bookkeeping under mi_bridge and mi_session,
+// driven through its controls half (csrc/control_changes.hpp) and what it shares with membership (mi::Roster of
+// csrc/conference.hpp, mi::SeatChanges of csrc/seat_changes.hpp) by the very calls the entry points make, without a GPU or the
+// library (tests/test_controls_cpu.py builds this with the address and undefined-behaviour sanitizers and reads its lines):
 //   controls_check bridge|session NSEATS MEMBERS STEP...
 //     c/STREAM:WHAT:FLAGS:GAIN[:STATIC[:PEER]],...  a call, as mi_*_change_controls makes it: checked, then applied to the
 //                                 mirrors (c/ alone: count 0); STATIC, PEER: the params' static_gain and peer (MI_CTL_VOLUME)
@@ -20,9 +20,7 @@
 #include <cstring>
 #include <string>
 
-#include "../../mediastreamer2_amd/csrc/conference.hpp"
-#include "../../mediastreamer2_amd/csrc/control_changes.hpp"
-#include "../../mediastreamer2_amd/csrc/seat_changes.hpp"
+#include "../../mediastreamer2_amd/csrc/conference_book.hpp"
 
 static char g_error[1024];
 void mi::set_error(const char *fmt, ...) {
@@ -55,13 +53,11 @@ int main(int argc, char **argv) {
 	if (n <= 0 || mm <= 0 || n % mm) return 2;
 	const char *fn = bridge ? "mi_bridge_change_controls" : "mi_session_change_controls";
 	const mi_volume_params dp = default_params();
-	mi::Roster roster;
-	roster.init(n, mm);
-	mi::SeatChanges seats;
-	seats.init(n, 3);
-	mi::ControlChanges ctl;
-	ctl.init(n, bridge ? &dp : nullptr);
-	unsigned reports = 0;
+	mi::ConferenceBook book; // a bridge's serves MI_CTL_VOLUME: it is given initial parameters
+	book.init(n, mm, 3, bridge ? &dp : nullptr);
+	const mi::Roster &roster = book.roster;
+	const mi::SeatChanges &seats = book.seats;
+	const mi::ControlChanges &ctl = book.controls;
 	std::vector<mi_seat_cmd> seat_row((size_t)n);
 	std::vector<mi_ctl_cmd> ctl_row((size_t)n);
 	for (int i = 4; i < argc; ++i) {
@@ -69,13 +65,10 @@ int main(int argc, char **argv) {
 		const char *arg = step.c_str() + (step.size() > 1 ? 2 : 0);
 		g_error[0] = 0;
 		if (step == "s") {
-			const int ks = seats.stage(seat_row.data(), roster.flags.data());
-			if (reports) // mi::ControlPlane::stage (controls.hpp)
-				for (const int32_t s : seats.changed)
-					if (seats.pending[(size_t)s].op & MI_SEAT_JOIN) ctl.note(s, MI_CTL_JOINED);
-			const int kc = ctl.stage(ctl_row.data(), roster.flags.data(), roster.joined.data());
+			int ks = -1, kc = -1;
+			book.stage(seat_row.data(), ctl_row.data(), &ks, &kc);
 			if (ks < 0 || ks > n || kc < 0 || kc > n) return 3;
-			seats.submitted(), ctl.submitted();
+			book.submitted();
 			printf("seat");
 			for (int j = 0; j < ks; ++j) printf(" %d:%d:%d", seat_row[(size_t)j].stream, seat_row[(size_t)j].op, seat_row[(size_t)j].flags);
 			printf("\nctl");
@@ -97,11 +90,11 @@ int main(int argc, char **argv) {
 			}
 			printf("thr %08x %s\n", bits, ok ? "ok" : "FAILED");
 		} else if (step.rfind("R/", 0) == 0) {
-			reports = (unsigned)atoi(arg);
+			book.reports = (unsigned)atoi(arg); // (mi::ConferencePlane::set_reports, behind its checks)
 		} else if (step.rfind("r/", 0) == 0 || step.rfind("a/", 0) == 0) {
 			const int s = atoi(arg);
 			if (s < 0 || s >= n) return 2;
-			printf("roster %d\n", (step[0] == 'r' ? roster.leave(s) : roster.join(s)) ? 0 : (int)MI_EINVAL);
+			printf("roster %d\n", step[0] == 'r' ? book.remove_member("remove_member", s) : book.add_member("add_member", s));
 		} else if (step.rfind("f/", 0) == 0 || step.rfind("g/", 0) == 0 || step.rfind("v/", 0) == 0) {
 			int s = 0;
 			float v = 0;
@@ -109,15 +102,15 @@ int main(int argc, char **argv) {
 			if (step[0] == 'f') { // mi_*_set_controls(h_flags): the whole array
 				std::vector<uint8_t> f = roster.flags;
 				f[(size_t)s] = (uint8_t)v;
-				roster.set_flags(f.data());
+				book.set_controls(f.data(), nullptr);
 			} else if (step[0] == 'g') { // mi_*_set_controls(h_gain)
 				std::vector<float> g = ctl.gain;
 				g[(size_t)s] = v;
-				ctl.set_gains(g.data());
+				book.set_controls(nullptr, g.data());
 			} else { // mi_bridge_set_volume_params
 				mi_volume_params p = dp;
 				p.static_gain = v;
-				ctl.set_params(s, 1, &p);
+				book.set_params(s, 1, &p);
 			}
 		} else if (step.rfind("m/", 0) == 0) {
 			std::vector<Change> list;
@@ -129,12 +122,7 @@ int main(int argc, char **argv) {
 				p += used;
 				if (*p == ',') ++p;
 			}
-			const int rc = mi::check_uniform_changes("mi_session_change_members", "JOIN or LEAVE", n, roster.flags.data(), list.data(), (int)list.size());
-			for (size_t j = 0; rc == MI_OK && j < list.size(); ++j) { // session.hip's loop
-				const bool was = roster.leave(list[j].stream);
-				seats.note(list[j].stream, (uint8_t)list[j].op, was);
-				if (list[j].op == MI_SEAT_JOIN) roster.join(list[j].stream);
-			}
+			const int rc = book.change_uniform_members("mi_session_change_members", "JOIN or LEAVE", list.data(), (int)list.size(), 160);
 			printf("call %d %s\n", rc, g_error);
 		} else if (step.rfind("c/", 0) == 0 || step.rfind("n/", 0) == 0) {
 			std::vector<Control> list;
@@ -155,13 +143,7 @@ int main(int argc, char **argv) {
 				}
 				count = (int)list.size();
 			}
-			const unsigned allowed = MI_CTL_FLAGS | MI_CTL_GAIN | (bridge ? MI_CTL_VOLUME : 0u);
-			int rc = mi::check_controls(fn, n, roster.flags.data(), allowed, list.empty() ? nullptr : list.data(), count, ctl.scratch);
-			if (rc == MI_OK && bridge) rc = mi::check_control_params(fn, list.data(), count);
-			for (int j = 0; rc == MI_OK && j < count; ++j) { // bridge.hip's / session.hip's loop
-				ctl.apply(list[(size_t)j], roster.flags.data());
-				if (bridge) ctl.apply_params(list[(size_t)j]);
-			}
+			const int rc = book.change_controls(fn, list.empty() ? nullptr : list.data(), count);
 			printf("call %d %s\n", rc, g_error);
 		} else {
 			return 2;

@@ -1,5 +1,6 @@
-// session_open_check.cpp -- csrc/seat_changes.hpp, the host's bookkeeping of membership changes that mi_bridge_change_members and
-// mi_session_change_members share, run alone with mi::Roster (csrc/conference.hpp), without a GPU or the library
+// session_open_check.cpp -- mi::ConferenceBook (csrc/conference_book.hpp), the host's bookkeeping under mi_bridge and mi_session,
+// driven through its membership half (csrc/seat_changes.hpp, mi::Roster of csrc/conference.hpp) by the very calls
+// mi_session's entry points make, without a GPU or the library
 // (tests/test_session_open_cpu.py builds this with the address and undefined-behaviour sanitizers and reads its lines):
 //   session_open_check NSEATS MEMBERS SLOTS STEP...
 //     c/STREAM:OP,STREAM:OP,...   a call, as mi_session_change_members makes it: checked, then merged per seat (c/ alone: count 0)
@@ -14,8 +15,7 @@
 #include <cstring>
 #include <string>
 
-#include "../../mediastreamer2_amd/csrc/conference.hpp"
-#include "../../mediastreamer2_amd/csrc/seat_changes.hpp"
+#include "../../mediastreamer2_amd/csrc/conference_book.hpp"
 
 static char g_error[1024];
 void mi::set_error(const char *fmt, ...) {
@@ -31,25 +31,27 @@ int main(int argc, char **argv) {
 	if (argc < 4) return 2;
 	const int n = atoi(argv[1]), mm = atoi(argv[2]), slots = atoi(argv[3]);
 	if (n <= 0 || mm <= 0 || n % mm || slots < 1) return 2;
-	mi::Roster roster;
-	roster.init(n, mm);
-	mi::SeatChanges changes;
-	changes.init(n, slots);
+	mi::ConferenceBook book;
+	book.init(n, mm, slots, nullptr);
+	const mi::Roster &roster = book.roster;
+	const mi::SeatChanges &changes = book.seats;
 	std::vector<mi_seat_cmd> row((size_t)n);
+	std::vector<mi_ctl_cmd> ctl_row((size_t)n);
 	for (int i = 4; i < argc; ++i) {
 		const std::string step = argv[i];
 		g_error[0] = 0;
 		if (step == "s") {
-			const int k = changes.stage(row.data(), roster.flags.data());
-			if (k < 0 || k > n) return 3;
-			changes.submitted();
+			int k = -1, kc = -1;
+			book.stage(row.data(), ctl_row.data(), &k, &kc);
+			if (k < 0 || k > n || kc != 0) return 3;
+			book.submitted();
 			printf("row");
 			for (int j = 0; j < k; ++j) printf(" %d:%d:%d", row[(size_t)j].stream, row[(size_t)j].op, row[(size_t)j].flags);
 			printf("\n");
 		} else if (step.rfind("r/", 0) == 0 || step.rfind("a/", 0) == 0) {
 			const int s = atoi(step.c_str() + 2);
 			if (s < 0 || s >= n) return 2;
-			printf("roster %d\n", (step[0] == 'r' ? roster.leave(s) : roster.join(s)) ? 0 : (int)MI_EINVAL);
+			printf("roster %d\n", step[0] == 'r' ? book.remove_member("mi_session_remove_member", s) : book.add_member("mi_session_add_member", s));
 		} else if (step.rfind("c/", 0) == 0 || step.rfind("n/", 0) == 0) {
 			std::vector<Change> list;
 			int count = 0;
@@ -66,13 +68,8 @@ int main(int argc, char **argv) {
 				}
 				count = (int)list.size();
 			}
-			const int rc = mi::check_uniform_changes("mi_session_change_members", "MI_SESSION_JOIN (1) or MI_SESSION_LEAVE (2)", n,
-			                                         roster.flags.data(), list.empty() ? nullptr : list.data(), count);
-			for (int j = 0; rc == MI_OK && j < count; ++j) { // session.hip's loop
-				const bool was = roster.leave(list[(size_t)j].stream);
-				changes.note(list[(size_t)j].stream, (uint8_t)list[(size_t)j].op, was);
-				if (list[(size_t)j].op == MI_SEAT_JOIN) roster.join(list[(size_t)j].stream);
-			}
+			const int rc = book.change_uniform_members("mi_session_change_members", "MI_SESSION_JOIN (1) or MI_SESSION_LEAVE (2)",
+			                                           list.empty() ? nullptr : list.data(), count, 160);
 			printf("call %d %s\n", rc, g_error);
 		} else {
 			return 2;
