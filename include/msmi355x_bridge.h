@@ -84,15 +84,28 @@
  * from any older constructor the call is mi_bridge_add_member / _remove_member without the drain.  Bit for bit the parts called
  * one by one with batches for every admitted rate (tests/test_gpu_bridge_open.py).
  *
+ * Legs at 44.1 kHz (mi_bridge_create_offgrid): the static RTP payload types 10 and 11 are L16 at 44 100 Hz (l16.c), AAC-ELD runs
+ * there (aac-eld.c), and so does a local sound-card endpoint; plumb_to_conf resamples such a member without asking.  The
+ * constructor takes mi_bridge_create_open's arguments and rules, and a leg or admitted kind may also be at 44 100 Hz -- the one
+ * rate off the 800 Hz grid whose 10 ms tick is whole samples, 441 of them: 55 groups of eight and one sample, which the kernel
+ * reads, levels and stores alone, no byte of a row touched past the leg's 882 (PCM) or 441 (code words).  Against a mix at 8,
+ * 12, 16, 24, 32 or 48 kHz both its resamplers are interpolated designs of 48 to 264 taps whose per-phase tables (80 to 441
+ * rows, 28 to 92 KB) mi_resampler blends once; the tick runs mi_resampler's generic-order arithmetic on those tables, each lane
+ * reading its output's row from memory, bit for bit mi_resampler_process_masked.  One conference holds such legs beside
+ * legs of every older form, still one launch per tick (bridge_offgrid_kernel, csrc/bridge_offgrid.hip, run only by a bridge
+ * with such a leg or admitted kind; tests/test_gpu_bridge_offgrid.py); cfg.plc is served through the per-leg concealer, whose
+ * rate classes may include 44 100 Hz.  The host swaps an L16 member's bytes, as it decodes every codec but G.711.
+ *
  * Out of scope, on purpose:
  *   - per membership change: mi_volume_params and the pin's input gain (mi_bridge_set_volume_params and mi_bridge_set_controls,
  *     which wait, set them); growing nstreams; kinds outside mi_bridge_create_ratios' rules; mi_session, whose membership calls
  *     keep their waits;
- *   - rates off the 800 Hz grid (44.1 kHz: its tick is not whole groups of eight samples); whole ratios other than 2, 3, 4
- *     and 6 (5, 7, 8 and up: a down-sampler of 240 taps or more); a : b with a or b above 8 or a ratio above 8/3 (7 : 2,
- *     9 : 8: an interpolated table or more than 128 taps), in either direction: refused with MI_ENOTSUP -- mi_session and the
- *     MSFilter plugin resample those; 3/2 and 2/3 through the five oldest constructors and 4, 1/4 and a : b through the six
- *     older ones, which keep refusing them;
+ *   - rates off the 800 Hz grid other than 44.1 kHz (22.05 and 11.025 kHz: 220.5 and 110.25 samples are no 10 ms tick), and a
+ *     MIX at 44.1 kHz; whole ratios other than 2, 3, 4 and 6 (5, 7, 8 and up: a down-sampler of 240 taps or more); a : b on the
+ *     grid with a or b above 8 or a ratio above 8/3 (7 : 2, 9 : 8: an interpolated table or more than 128 taps), in either
+ *     direction: refused with MI_ENOTSUP -- mi_session and the MSFilter plugin resample those; 3/2 and 2/3 through the five
+ *     oldest constructors, 4, 1/4 and a : b through the six older ones and 44.1 kHz through all eight before
+ *     mi_bridge_create_offgrid, which keep refusing them;
  *   - jitter buffering and flow control: the host's, as with mi_session -- a leg whose packet is missing at the tick is
  *     flagged absent (or concealed, cfg.plc);
  *   - cfg.plc with legs that differ in rate or codec through the four older constructors: they keep refusing it with
@@ -202,6 +215,23 @@ int mi_bridge_create_ratios(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_b
  * the distinct rates of the union may be seven at most (the message names the count). */
 int mi_bridge_create_open(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */,
                           const mi_bridge_leg *h_admit /* [nadmit] */, int nadmit, mi_bridge **out);
+/* The same with legs and admitted kinds at 44 100 Hz as well.  The arguments and every rule are mi_bridge_create_open's, and a
+ * leg or an admitted kind may also be at 44 100 Hz wherever both its resamplers, by the resampler's own design rule at quality
+ * 3, have a per-phase table (up to 256 KB) of at most 264 taps: with cfg->rate at 8, 12, 16, 24, 32 or 48 kHz (264, 176, 136,
+ * 88, 72 and 48 taps leg -> mix; 48 taps mix -> leg, 56 from 48 kHz).  cfg->rate itself stays a multiple of 800.  Any codec of
+ * the three is legal on such a leg (code words are samples at the leg's rate): its tick is 882 bytes of PCM or 441 code words,
+ * and the rows' pitch is rounded up to 16 as ever (896 and 448).  With no such leg or kind: mi_bridge_create_open's bridge
+ * exactly, the same kernels, pitch and tick bytes.  mi_bridge_reset_streams, mi_bridge_add_member and a JOIN zero both its
+ * resamplers' histories (filter length - 1 samples, up to 263) and start its concealer over in the 44 100 Hz class; with
+ * cfg->plc and such a leg the concealer is the per-leg one whether the legs differ or not.  MI_ENOTSUP, the message naming the
+ * leg or admitted kind, both rates and the reason, before anything is allocated: what mi_bridge_create_open refuses on the grid
+ * (whole ratios 5, 7, 8 and up; 7 : 2, 9 : 8); 22 050 and 11 025 Hz, or any other rate off the grid; a mix at 44 100 Hz, or one
+ * against which the tables fail the rule (4 kHz: 536 taps); a conference whose rows -- 448 samples for a 441-sample tick --, sum
+ * row and resampler scratch do not fit the 64 KB of LDS the kernel allows itself.  44.1 kHz legs alone fit at the mixer's own
+ * limit of 50 members in every one of the six mixes (58 896 bytes in a 48 kHz one); in a 16 kHz room that also holds 48 kHz
+ * members: up to 45 members. */
+int mi_bridge_create_offgrid(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs /* [nstreams] */,
+                             const mi_bridge_leg *h_admit /* [nadmit] */, int nadmit, mi_bridge **out);
 void mi_bridge_destroy(mi_bridge *b);
 int mi_bridge_leg_rate(const mi_bridge *b, int stream); /* the leg's rate in Hz, or MI_EINVAL */
 /* the leg's codecs and its own tick in bytes (rate / 100 x 1 or 2), on any bridge; either pointer may be NULL.

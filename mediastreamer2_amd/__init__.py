@@ -937,7 +937,8 @@ class Bridge(_ConferenceBatch):
     _destroy, _prefix = "mi_bridge_destroy", "bridge"
 
     def __init__(self, ctx, nstreams, members=32, rate=8000, in_codec=MI_SESSION_PCMU, out_codec=MI_SESSION_PCMU, plc=False, device=0,
-                 leg_rates=None, legs=None, endpoints=None, concealed=None, rational=None, ratios=None, open=None, admit=None):
+                 leg_rates=None, legs=None, endpoints=None, concealed=None, rational=None, ratios=None, open=None, admit=None,
+                 offgrid=None):
         """leg_rates: the rate of every leg's code words or PCM [nstreams] (mi_bridge_create_rated: rate / leg rate in
         {1, 2, 3, 6}); None: every leg at `rate`.
         legs: every leg's (rate, in_codec, out_codec) [nstreams], a sequence of triples or a structured array with those
@@ -954,7 +955,10 @@ class Bridge(_ConferenceBatch):
         12 kHz member of a 16 kHz one); geometry and views are endpoints='.
         open: the same triples for mi_bridge_create_open: ratios= whose seats may change hands (change()); admit: the kinds
         (rate, in_codec, out_codec) that may ever take a seat besides those of open= themselves.  The bridge is planned for
-        the union, so the byte rows' pitch is the widest admitted kind's; admit=None or empty is ratios= exactly."""
+        the union, so the byte rows' pitch is the widest admitted kind's; admit=None or empty is ratios= exactly.
+        offgrid: the same triples for mi_bridge_create_offgrid: open= (admit= goes with it likewise) where a leg or admitted kind
+        may also be at 44 100 Hz, a tick of 441 samples -- 882 bytes of PCM or 441 code words, the pitch rounded up to 16 as
+        ever; without such a kind it is open= exactly."""
         self._own_ctx = ctx is None
         self.ctx = ctx = Context(device) if ctx is None else ctx
         cfg = BridgeConfig()
@@ -965,13 +969,15 @@ class Bridge(_ConferenceBatch):
         by_leg = {"mi_bridge_create_legs": legs, "mi_bridge_create_endpoints": endpoints, "mi_bridge_create_concealed": concealed,
                   "mi_bridge_create_rational": rational, "mi_bridge_create_ratios": ratios}
         given = [(getattr(ctx.L, entry), v) for entry, v in by_leg.items() if v is not None]
-        assert admit is None or open is not None, "admit= goes with open="
-        if open is not None:
-            assert not given, "one of legs=, endpoints=, concealed=, rational=, ratios= and open="
+        assert admit is None or open is not None or offgrid is not None, "admit= goes with open= or offgrid="
+        assert open is None or offgrid is None, "one of open= and offgrid="
+        if open is not None or offgrid is not None:
+            assert not given, "one of legs=, endpoints=, concealed=, rational=, ratios=, open= and offgrid="
             kinds = np.zeros((0, 3), np.int32) if admit is None or len(admit) == 0 else self._triples(admit)
-            given = [(lambda c, cf, lg, out: ctx.L.mi_bridge_create_open(c, cf, lg, kinds.ctypes.data, len(kinds), out), open)]
+            entry = ctx.L.mi_bridge_create_open if open is not None else ctx.L.mi_bridge_create_offgrid
+            given = [(lambda c, cf, lg, out: entry(c, cf, lg, kinds.ctypes.data, len(kinds), out), open if open is not None else offgrid)]
         if given:
-            assert len(given) == 1, "one of legs=, endpoints=, concealed=, rational=, ratios= and open="
+            assert len(given) == 1, "one of legs=, endpoints=, concealed=, rational=, ratios=, open= and offgrid="
             create, lg = given[0][0], self._triples(given[0][1])
             assert lg.shape == (nstreams, 3), "one (rate, in_codec, out_codec) per leg"
             check(create(ctx.h, C.byref(cfg), lg.ctypes.data, C.byref(h)))

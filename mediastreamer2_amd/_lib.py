@@ -69,6 +69,7 @@ BRIDGE_EXPORTS = [
     "mi_bridge_create_rational",
     "mi_bridge_create_ratios",
     "mi_bridge_create_open", "mi_bridge_change_members",
+    "mi_bridge_create_offgrid",
     "mi_bridge_change_controls", "mi_bridge_set_reports", "mi_bridge_collected_report",
 ]
 
@@ -309,6 +310,7 @@ def load():
     L.mi_bridge_create_rational.argtypes = [vp, vp, vp, pp]
     L.mi_bridge_create_ratios.argtypes = [vp, vp, vp, pp]
     L.mi_bridge_create_open.argtypes = [vp, vp, vp, vp, i32, pp]
+    L.mi_bridge_create_offgrid.argtypes = [vp, vp, vp, vp, i32, pp]
     L.mi_bridge_change_members.argtypes = [vp, vp, i32]
     L.mi_bridge_leg_codec.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.mi_bridge_leg_bytes.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]

@@ -31,7 +31,8 @@
 // LDS are as wide as the widest leg's tick; a narrower leg's tick sits at the head of its row until its up-sampler has run.
 // The five kernels below differ in which forms they are built for, so that a bridge pays only for what its legs need:
 // compile-time codecs or per-leg ones, no resamplers, those of legs below the mix, above it, at 3/2 and 2/3 of it.  A sixth,
-// for legs at 4, 1/4 and a : b of the mix (mi_bridge_create_ratios), is a unit of its own: bridge_ratios.hip.
+// for legs at 4, 1/4 and a : b of the mix (mi_bridge_create_ratios), is a unit of its own: bridge_ratios.hip; so is the seventh,
+// for legs at 44 100 Hz (mi_bridge_create_offgrid): bridge_offgrid.hip.
 //
 // Geometry: an 8 kHz conference of 32 is 5.4 KB of LDS and four waves, so eight such workgroups share a CU (32 waves);
 // 1000 conferences are 1000 workgroups dealt over the 256 CUs, about four per CU = one wave per SIMD and conference
@@ -51,6 +52,8 @@ static_assert(PLAN_MAX_RATE_CLASSES == PLC_MAX_CLASSES, "the plan refuses what t
 
 // bridge_ratios.hip: bridge_ratios_kernel on `nconf` workgroups; args: a RatiosArgs, as bytes
 int mi_bridge_ratios_launch(const void *args, size_t bytes, int nconf, size_t lds, hipStream_t stream);
+// bridge_offgrid.hip: bridge_offgrid_kernel likewise; args: an OffgridArgs
+int mi_bridge_offgrid_launch(const void *args, size_t bytes, int nconf, size_t lds, hipStream_t stream);
 
 namespace {
 
@@ -296,7 +299,7 @@ __global__ __launch_bounds__(BT) void bridge_rational_kernel(RationalArgs qa) {
 struct mi_bridge {
 	mi_ctx *ctx = nullptr;
 	Plan plan;              // what creation decided: geometry, family, the legs' rates, codecs and ratio bytes
-	RatiosArgs args = {};   // the widest kernel's arguments, filled at creation (fill_args, build_tables) but for in, present, out
+	OffgridArgs args = {};  // the widest kernel's arguments, filled at creation (fill_args, build_tables) but for in, present, out
 	mi_volume *vol = nullptr; // the meters: parameters, state, one-second windows
 	mi_mixer *mix = nullptr;  // the pins' controls
 	mi_plc *plc = nullptr;    // plan.leg_plc: mi_plc_create_legs', with the decoders; else mi_plc_create's at the legs' one rate
@@ -328,7 +331,7 @@ void (*const RATED_KERNELS[3][3])(RatedArgs) = CODEC_TABLE(bridge_rated_kernel);
 // mi_volume_create / mi_mixer_create allocate and only their destroy frees; no setter reallocates them.
 void fill_args(mi_bridge *b) {
 	const Plan &pl = b->plan;
-	LegsArgs &la = b->args.q.u.l;
+	LegsArgs &la = b->args.g.q.u.l;
 	RatedArgs &ra = la.r;
 	BridgeArgs &a = ra.b;
 	VolumeView vv;
@@ -342,10 +345,11 @@ void fill_args(mi_bridge *b) {
 	ra.pitch = pl.pitch, ra.hout_stride = pl.hout_stride, ra.scratch_off = pl.scratch_off, ra.scratch_per_wave = pl.scratch_per_wave;
 	if (b->d_codec) { // behind the concealer every leg's input is the PCM it worked on, at the pitch of its rows
 		la.codec = b->plc ? b->d_codec + pl.n : b->d_codec;
-		la.in_pitch = b->plc ? pl.pitch * 2 : (int)pl.in_bytes, la.out_pitch = (int)pl.out_bytes;
+		la.in_pitch = b->plc ? pl.pcm_pitch() * 2 : (int)pl.in_bytes, la.out_pitch = (int)pl.out_bytes;
 	}
-	b->args.q.u.wide = pl.wide, b->args.q.u.hin_stride = pl.hin_stride;
-	b->args.gen_tab = b->d_gen;
+	b->args.g.q.u.wide = pl.wide, b->args.g.q.u.hin_stride = pl.hin_stride;
+	b->args.g.gen_tab = b->d_gen;
+	b->args.num = pl.off_num, b->args.den = pl.off_den, b->args.filt_in = pl.off_fin, b->args.filt_out = pl.off_fout;
 }
 
 // a tick that carries membership changes: the bridge's own state in one launch (mi::ConferencePlane::apply's seat_launch)
@@ -367,12 +371,13 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 	const Plan &pl = b->plan;
 	const mi_bridge_config &cf = pl.cfg;
 	int rc, in_kind = cf.in_codec;
-	RatiosArgs ga = b->args; // each kernel is passed the part that is its own
+	OffgridArgs oa = b->args; // each kernel is passed the part that is its own
+	RatiosArgs &ga = oa.g;
 	RationalArgs &qa = ga.q;
 	BridgeArgs &a = qa.u.l.r.b;
 	a.in = b->d_in[slot], a.present = b->d_present[slot], a.out = b->d_out[slot];
 	if (pl.leg_plc) { // every leg's decoder and MSGenericPLC in the concealer's three launches: byte rows in, PCM rows out
-		if ((rc = mi_plc_process_legs(b->plc, b->d_in[slot], pl.in_bytes, b->d_pcm, (size_t)pl.pitch, b->d_ev[slot])) != MI_OK) return rc;
+		if ((rc = mi_plc_process_legs(b->plc, b->d_in[slot], pl.in_bytes, b->d_pcm, (size_t)pl.pcm_pitch(), b->d_ev[slot])) != MI_OK) return rc;
 		a.in = b->d_pcm, a.present = nullptr; // a concealed leg counts as present
 	} else if (b->plc) { // MSAlawDec / MSUlawDec as a launch of its own, then MSGenericPLC on the PCM rows, in place
 		int16_t *rows = reinterpret_cast<int16_t *>(b->d_in[slot]);
@@ -387,6 +392,7 @@ int run_tick_kernels(mi_bridge *b, int slot) { // everything on the context's st
 	}
 	auto launch = [&](auto kernel, const auto &args) { hipLaunchKernelGGL(kernel, dim3((unsigned)pl.nconf), dim3(BT), pl.lds, b->ctx->stream, args); };
 	switch (pl.family) {
+	case Plan::OFFGRID: return mi_bridge_offgrid_launch(&oa, sizeof(oa), pl.nconf, pl.lds, b->ctx->stream);
 	case Plan::RATIOS: return mi_bridge_ratios_launch(&ga, sizeof(ga), pl.nconf, pl.lds, b->ctx->stream);
 	case Plan::RATIONAL: launch(bridge_rational_kernel, qa); break;
 	case Plan::UPDOWN: launch(bridge_updown_kernel, qa.u); break;
@@ -435,8 +441,8 @@ struct Table { int in_rate, out_rate; size_t size; Layout layout; int *offset; i
 
 int build_tables(mi_bridge *b) {
 	const Plan &pl = b->plan;
-	UpdownArgs &ua = b->args.q.u;
-	RationalArgs &qa = b->args.q;
+	UpdownArgs &ua = b->args.g.q.u;
+	RationalArgs &qa = b->args.g.q;
 	RatedArgs &ra = ua.l.r;
 	const int conf = pl.cfg.rate;
 	std::vector<Table> want;
@@ -488,6 +494,29 @@ int build_tables(mi_bridge *b) {
 			for (int r = 0; r < L; ++r)
 				for (int pp = 0; pp < M; ++pp)
 					for (int k = 0; k < RQ_FT; ++k) all.push_back(t[(size_t)((r * M) % L) * RQ_FT * M + (size_t)k * M + pp]);
+	}
+	if (pl.offgrid) { // the 44 100 Hz legs' pair: the PER-PHASE tables mi_resampler's generic kernel reads, [rows][taps], on 16 bytes
+		const struct { int in_rate, out_rate, rows, taps, *offset; } pair[2] = {{OFFGRID_RATE, conf, pl.off_den, pl.off_fin, &b->args.tab_in},
+		                                                                        {conf, OFFGRID_RATE, pl.off_num, pl.off_fout, &b->args.tab_out}};
+		for (const auto &w : pair) {
+			mi_resampler *r = nullptr;
+			int rc = mi_resampler_create(b->ctx, 1, (uint32_t)w.in_rate, (uint32_t)w.out_rate, 3, &r), filt_len = 0;
+			if (rc != MI_OK) return rc;
+			t.resize((size_t)mi_resampler_get_phase_table(r, nullptr, 0));
+			mi_resampler_get_phase_table(r, t.data(), (int)t.size());
+			rc = mi_resampler_info(r, &filt_len, nullptr, nullptr, nullptr);
+			mi_resampler_destroy(r);
+			if (rc != MI_OK) return rc;
+			if (filt_len != w.taps || t.size() != (size_t)w.rows * w.taps) {
+				mi::set_error("mi_bridge: the plan's filter for %d -> %d Hz (%d rows of %d taps) is not mi_resampler's per-phase table (%zu floats, "
+				              "%d taps): filter_rule (bridge_plan.hpp) and design_filter (resample.hip) disagree",
+				              w.in_rate, w.out_rate, w.rows, w.taps, t.size(), filt_len);
+				return MI_ENOTSUP;
+			}
+			all.resize((all.size() + 3) & ~(size_t)3, 0.f);
+			*w.offset = (int)all.size();
+			all.insert(all.end(), t.begin(), t.end());
+		}
 	}
 	if (!(b->d_tab = (float *)mi_dev_alloc(b->ctx, all.size() * sizeof(float)))) return MI_ENOMEM;
 	MI_HIP(hipMemcpy(b->d_tab, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -582,10 +611,10 @@ static int build_bridge(mi_ctx *ctx, Plan &plan, mi_bridge **out) {
 			std::vector<int32_t> open; // an open bridge: a rate class for every kind that may come
 			for (const mi_bridge_leg &k : pl.kinds)
 				if (std::find(open.begin(), open.end(), k.rate) == open.end()) open.push_back(k.rate);
-			if ((rc = mi_plc_create_legs(ctx, pl.n, pl.leg_rate.data(), kind.data(), pl.pitch, &b->plc, open.data(), (int)open.size())) != MI_OK)
+			if ((rc = mi_plc_create_legs(ctx, pl.n, pl.leg_rate.data(), kind.data(), pl.pcm_pitch(), &b->plc, open.data(), (int)open.size())) != MI_OK)
 				return fail(rc);
-			if (!(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * pl.pitch * 2))) return fail(MI_ENOMEM);
-			if (hipMemsetAsync(b->d_pcm, 0, n * pl.pitch * 2, ctx->stream) != hipSuccess) return fail(MI_ENODEV);
+			if (!(b->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * pl.pcm_pitch() * 2))) return fail(MI_ENOMEM);
+			if (hipMemsetAsync(b->d_pcm, 0, n * pl.pcm_pitch() * 2, ctx->stream) != hipSuccess) return fail(MI_ENODEV);
 		} else { // at the legs' one rate, on rows of the host buffers' pitch
 			if ((rc = mi_plc_create(ctx, pl.n, pl.rated ? pl.common : pl.cfg.rate, pl.pitch, &b->plc)) != MI_OK) return fail(rc);
 			std::vector<int32_t> lens(n, pl.pitch);
@@ -638,6 +667,15 @@ int mi_bridge_create_open(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bri
 	*out = nullptr;
 	Plan plan;
 	const int rc = plan_open(RULES_RATIOS, cfg, h_legs, h_admit, nadmit, &plan);
+	return rc != MI_OK ? rc : build_bridge(ctx, plan, out);
+}
+
+int mi_bridge_create_offgrid(mi_ctx *ctx, const mi_bridge_config *cfg, const mi_bridge_leg *h_legs, const mi_bridge_leg *h_admit, int nadmit,
+                             mi_bridge **out) {
+	MI_CHECK_ARG(ctx && cfg && h_legs && out && nadmit >= 0 && (h_admit || nadmit == 0));
+	*out = nullptr;
+	Plan plan;
+	const int rc = plan_open(RULES_OFFGRID, cfg, h_legs, h_admit, nadmit, &plan);
 	return rc != MI_OK ? rc : build_bridge(ctx, plan, out);
 }
 

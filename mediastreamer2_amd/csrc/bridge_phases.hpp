@@ -1,6 +1,7 @@
 // bridge_phases.hpp -- the phases of a conference tick (the head of bridge.hip describes them), each written ONCE as a
-// __device__ __forceinline__ function; bridge.hip's five kernels and bridge_ratios.hip's one are compositions of them with
-// the barriers in between (bridge_tick_kernel keeps three of them written out, for its pinned register figures: see its head).
+// __device__ __forceinline__ function; bridge.hip's five kernels, bridge_ratios.hip's one and bridge_offgrid.hip's one are
+// compositions of them with the barriers in between (bridge_tick_kernel keeps three of them written out, for its pinned
+// register figures: see its head).
 // What differs between the kernels is a template parameter or data here:
 //   FORMS  which resamplers a kernel has (Forms below), and with it how a member's ratio byte is read (leg_span);
 //   SRC    where (A) takes a group from: FixedSrc<IN>, one compile-time codec on rows of samples, or LegSrc, every leg's own
@@ -21,7 +22,7 @@
 
 namespace {
 
-// ---- the kernels' arguments.  Each kernel's struct holds the one before it, so the host fills a RationalArgs once per bridge
+// ---- the kernels' arguments.  Each kernel's struct holds the one before it, so the host fills an OffgridArgs once per bridge
 // (mi_bridge::args, bridge.hip) and every kernel is passed its own part of it.
 struct BridgeArgs {
 	const void *in;         // [nconf * mm][ns] uint8 code words or int16
@@ -80,6 +81,14 @@ struct RatiosArgs {
 	const int2 *gen_tab;
 };
 
+struct OffgridArgs {
+	RatiosArgs g;
+	// the one pair of resamplers of the bridge's 44 100 Hz legs: leg : mix = num : den in lowest terms; the float offsets in
+	// `tab` (multiples of four: a lane reads its row in 16-byte loads) of the in_resampler's per-phase table [den][filt_in] and
+	// the out_resampler's [num][filt_out], as mi_resampler's generic kernel reads them
+	int num, den, filt_in, filt_out, tab_in, tab_out;
+};
+
 // ---- a member's ratio byte (bridge_plan.hpp writes it).  A kernel meets only the forms it was built for:
 enum Forms {
 	F_SAME,  // every leg at the conference's rate: no ratio byte, no resampler
@@ -87,13 +96,17 @@ enum Forms {
 	F_ABOVE, // and above it
 	F_R32,   // and at 3/2 or 2/3 of it
 	F_GEN,   // and at a : b of it in the generic order (UD_GEN); at 4 and 1/4 through the forms above
+	F_OFF,   // and at 44 100 Hz (UD_OFF): a tick of 441 samples, no whole groups of eight
 };
 
 // The one place where a ratio byte becomes a length or a rate: the leg's share of `conf` -- groups, words or samples of the
-// conference's tick, or its sample rate.  F_SAME folds to `conf` at compile time.
+// conference's tick, or its sample rate.  F_SAME folds to `conf` at compile time.  off: what a leg at 44 100 Hz has of that
+// unit, which is no share of the conference's -- OFFGRID_GROUPS, OFFGRID_WORDS (the tail group and word counted), OFFGRID_LEN or
+// OFFGRID_RATE; read by a kernel with F_OFF only.
 template <int FORMS>
-__device__ __forceinline__ int leg_span(int r, int conf) {
+__device__ __forceinline__ int leg_span(int r, int conf, int off = 0) {
 	if (FORMS == F_SAME) return conf;
+	if (FORMS >= F_OFF && is_offgrid(r)) return off;
 	if (FORMS >= F_GEN && (r & UD_GEN)) return conf / gen_b(r) * gen_a(r);
 	if (FORMS >= F_R32 && (r & UD_R32)) return (r & UD_ABOVE) ? conf / 2 * 3 : conf / 3 * 2;
 	if (FORMS >= F_ABOVE && (r & UD_ABOVE)) return conf * (r & 7);
@@ -158,7 +171,32 @@ struct LegSrc {
 	__device__ __forceinline__ int kind(int s) const { return codec[s] & 3; }
 	__device__ __forceinline__ uint4 fetch(int s, int kind, int g) const { return load_raw_leg(in + (size_t)s * pitch, kind, g); }
 	__device__ __forceinline__ uint4 decoded(uint4 v, int kind, int g) const { return decode_group_leg(v, kind, g); }
+	// the first REM < 8 code units of group g, one load each and not a byte past them, where fetch's 16 bytes have them
+	template <int REM>
+	__device__ __forceinline__ uint4 fetch_tail(int s, int kind, int g) const {
+		const uint8_t *row = in + (size_t)s * pitch;
+		uint32_t w[4] = {0, 0, 0, 0}, c[2] = {0, 0};
+		if (kind == MI_SESSION_PCM16) {
+			const uint16_t *p = reinterpret_cast<const uint16_t *>(row + 16 * g);
+#pragma unroll
+			for (int j = 0; j < REM; ++j) w[j >> 1] |= (uint32_t)p[j] << (16 * (j & 1));
+			return make_uint4(w[0], w[1], w[2], w[3]);
+		}
+#pragma unroll
+		for (int j = 0; j < REM; ++j) c[j >> 2] |= (uint32_t)row[8 * g + j] << (8 * (j & 3));
+		return (g & 1) ? make_uint4(0, 0, c[0], c[1]) : make_uint4(c[0], c[1], 0, 0);
+	}
 };
+
+// eight packed samples with all but the first REM zero: a tail group as it stands on a row (a code byte of zero is no silence)
+template <int REM>
+__device__ __forceinline__ uint4 keep_head(uint4 d) {
+	uint32_t w[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+	for (int i = 0; i < 4; ++i) w[i] &= 2 * i + 1 < REM ? 0xffffffffu : 2 * i < REM ? 0xffffu : 0u;
+	return make_uint4(w[0], w[1], w[2], w[3]);
+}
+constexpr int OFFGRID_TAIL = OFFGRID_LEN & 7; // samples in the tail group of a 441-sample tick: one
 
 // ---- where eight samples of a mix go: group g of the row that starts `at` code units into `out`, as 16 bytes of PCM or 8
 // code words.  OUT 0, 1, 2: the codec at compile time, a unit one sample of it; BY_KIND: the leg's own, `kind`, a unit one
@@ -237,19 +275,26 @@ __device__ __forceinline__ void stage_rows(const Conf &k, const uint8_t *present
 			const int s = k.s0 + m;
 			const bool on = !present || present[s] != 0;
 			const int kind = src.kind(s);
-			const int ngl = leg_span<FORMS>(FORMS == F_SAME ? 1 : ratio[s], k.ng), nz = FORMS >= F_ABOVE ? max(k.ng, ngl) : k.ng;
+			const int rb = FORMS == F_SAME ? 1 : ratio[s];
+			const int ngl = leg_span<FORMS>(rb, k.ng, OFFGRID_GROUPS), nz = FORMS >= F_ABOVE ? max(k.ng, ngl) : k.ng;
+			// a 441-sample tick's last group holds one sample: read alone, the group's other seven zeros on the row
+			const int tail = FORMS >= F_OFF && is_offgrid(rb) ? OFFGRID_GROUPS - 1 : -1;
 			for (int g0 = q; g0 < nz; g0 += 32) {
 				uint4 v[4];
 #pragma unroll
 				for (int i = 0; i < 4; ++i) { // straight-line loads: all in flight at once
 					v[i] = make_uint4(0, 0, 0, 0);
-					if (on && g0 + 8 * i < ngl) v[i] = src.fetch(s, kind, g0 + 8 * i);
+					if constexpr (FORMS >= F_OFF) {
+						if (on && g0 + 8 * i == tail) v[i] = src.template fetch_tail<OFFGRID_TAIL>(s, kind, tail);
+						else if (on && g0 + 8 * i < ngl) v[i] = src.fetch(s, kind, g0 + 8 * i);
+					} else if (on && g0 + 8 * i < ngl) v[i] = src.fetch(s, kind, g0 + 8 * i);
 				}
 #pragma unroll
 				for (int i = 0; i < 4; ++i) {
 					const int g = g0 + 8 * i;
 					if (g >= nz) continue;
-					const uint4 d = src.decoded(v[i], kind, g);
+					uint4 d = src.decoded(v[i], kind, g);
+					if (FORMS >= F_OFF && g == tail) d = keep_head<OFFGRID_TAIL>(d);
 					if (on && g < ngl) v[i] = d; // (code bytes of zero are not silence)
 					k.rows[m * k.row_w + 2 * g] = make_uint2(v[i].x, v[i].y);
 					k.rows[m * k.row_w + 2 * g + 1] = make_uint2(v[i].z, v[i].w);
@@ -281,7 +326,7 @@ __device__ __forceinline__ void meter(const Conf &k, const BridgeArgs &a, Member
 	if (k.t < k.mm) {
 		if (me.here) {
 			const uint2 *r = k.rows + k.t * k.row_w;
-			const int nwl = leg_span<FORMS>(me.rt, k.nw);
+			const int nwl = leg_span<FORMS>(me.rt, k.nw, OFFGRID_WORDS); // (a tail word's other samples are zeros: + 0.f)
 			float acc = 0;
 #pragma unroll 4
 			for (int i = 0; i < nwl; ++i) {
@@ -292,8 +337,8 @@ __device__ __forceinline__ void meter(const Conf &k, const BridgeArgs &a, Member
 				acc += (float)(x2 * x2);
 				acc += (float)(x3 * x3);
 			}
-			const VolCtl o = volume_control(p, st, 0.f, acc, leg_span<FORMS>(me.rt, k.ns), k.s_pk[k.t], k.s_dc[k.t],
-			                                leg_span<FORMS>(me.rt, a.sample_rate), me.win);
+			const VolCtl o = volume_control(p, st, 0.f, acc, leg_span<FORMS>(me.rt, k.ns, OFFGRID_LEN), k.s_pk[k.t], k.s_dc[k.t],
+			                                leg_span<FORMS>(me.rt, a.sample_rate, OFFGRID_RATE), me.win);
 			k.s_par[k.t] = make_int4((int)me.mflag | (o.mode << 8), o.intgain, o.dcoff, me.mgain_bits);
 			a.state[k.s0 + k.t] = st;
 			a.win[k.s0 + k.t] = me.win;
@@ -319,10 +364,14 @@ __device__ __forceinline__ void level_legs(const Conf &k, int nww) {
 	for (int item = k.t; item < k.mm * nww; item += BT) {
 		const int m = item / nww, j = item - m * nww;
 		const int4 par = k.s_par[m];
-		if ((par.x >> 8) == 0 || j >= leg_span<FORMS>(k.s_rt[m], k.nw)) continue;
+		if ((par.x >> 8) == 0 || j >= leg_span<FORMS>(k.s_rt[m], k.nw, OFFGRID_WORDS)) continue;
 		const uint2 cur = k.rows[m * k.row_w + j];
 		int x[4] = {lo16(cur.x), hi16(cur.x), lo16(cur.y), hi16(cur.y)};
 		apply_gain(x, par);
+		if (FORMS >= F_OFF && is_offgrid(k.s_rt[m]) && j == OFFGRID_WORDS - 1) { // the tail word: no sample past the tick's last
+#pragma unroll
+			for (int i = OFFGRID_LEN & 3; i < 4; ++i) x[i] = 0;
+		}
 		k.rows[m * k.row_w + j] = make_uint2(pack16(x[0], x[1]), pack16(x[2], x[3]));
 	}
 }
@@ -539,6 +588,43 @@ __device__ __forceinline__ void generic_run(float *x, int16_t *row, int16_t *his
 	wave_sync(); // x is read out before the wave's next member stages over it
 }
 
+// One member's resampler at num : den (in : out, lowest terms) in mi_resampler's generic order on the PER-PHASE table, which
+// stays in memory: the 44 100 Hz legs' (mi_bridge_create_offgrid).  generic_run's arithmetic to the bit -- output k is ONE
+// __builtin_fmaf chain from 0.f over taps j = 0 .. filt - 1 of table row (k * num) % den against x[(k * num) / den + j], then
+// rs_word2int; the last filt - 1 samples of history ++ tick are the new history -- but nothing of the table is staged: it is 28
+// to 92 KB, no wavefront's scratch holds it, and a tick uses every row of it about once (441 rows for 441 outputs, 160 for
+// 160), so a staged copy would be read once as well.  Each lane reads ITS output's row, filt floats (a multiple of eight, the
+// row 16-byte aligned), in 16-byte loads, two in flight per step; the rows are the same for every such leg of the launch and
+// stay in L2.  x: [generic_xlen(filt, in_len)] floats.  A tick is whole periods of `num` samples: no position state.
+__device__ __forceinline__ void offgrid_run(float *x, int16_t *row, int16_t *hist, const float *tab, int num, int den, int filt, int in_len,
+                                            int lane) {
+	const int hl = filt - 1, out_len = in_len / num * den;
+	for (int i = lane; i < hl; i += 64) x[i] = (float)hist[i];
+	for (int i = lane; i < in_len; i += 64) x[hl + i] = (float)row[i];
+	wave_sync(); // the whole tick is staged before the first output lands on the row
+	for (int k = lane; k < out_len; k += 64) {
+		const int t = k * num, last = t / den, frac = t - last * den;
+		const float4 *sc = reinterpret_cast<const float4 *>(tab + (size_t)frac * filt);
+		const float *ip = x + last;
+		float sum = 0.f;
+		for (int j = 0; j < (filt >> 3); ++j) {
+			const float4 a = sc[2 * j], b = sc[2 * j + 1];
+			const float *w = ip + 8 * j;
+			sum = __builtin_fmaf(a.x, w[0], sum);
+			sum = __builtin_fmaf(a.y, w[1], sum);
+			sum = __builtin_fmaf(a.z, w[2], sum);
+			sum = __builtin_fmaf(a.w, w[3], sum);
+			sum = __builtin_fmaf(b.x, w[4], sum);
+			sum = __builtin_fmaf(b.y, w[5], sum);
+			sum = __builtin_fmaf(b.z, w[6], sum);
+			sum = __builtin_fmaf(b.w, w[7], sum);
+		}
+		row[k] = rs_word2int(sum);
+	}
+	for (int i = lane; i < hl; i += 64) hist[i] = (int16_t)x[in_len + i];
+	wave_sync(); // x is read out before the wave's next member stages over it
+}
+
 // what an up-sampler behind a pin left on the member's row -- its out_resampler's `len` leg-rate samples -- through the leg's
 // store or encoder, 16 bytes of PCM or 8 code words per lane
 __device__ __forceinline__ void store_row(const int16_t *row, uint8_t *out, int kind, int len, int lane) {
@@ -548,6 +634,16 @@ __device__ __forceinline__ void store_row(const int16_t *row, uint8_t *out, int 
 		const int o[8] = {lo16(w0.x), hi16(w0.x), lo16(w0.y), hi16(w0.y), lo16(w1.x), hi16(w1.x), lo16(w1.y), hi16(w1.y)};
 		store_group<BY_KIND>(out, 0, g, o, kind);
 	}
+}
+
+// the REM < 8 samples behind the `groups` whole groups store_row has stored, one store each and not a byte past them: the
+// row's tail in the host buffers stays as it is
+template <int REM>
+__device__ __forceinline__ void store_tail(const int16_t *row, uint8_t *out, int kind, int groups, int lane) {
+	if (lane >= REM) return;
+	const int i = 8 * groups + lane, x = row[i];
+	if (kind == MI_SESSION_PCM16) reinterpret_cast<int16_t *>(out)[i] = (int16_t)x;
+	else out[i] = (uint8_t)(kind == MI_SESSION_PCMU ? lin2ulaw(x) : lin2alaw(x));
 }
 
 // a wavefront's resampler scratch in the dynamic LDS
@@ -566,17 +662,19 @@ __device__ __forceinline__ int wave_ratio(const Conf &k, int m) {
 // ---- (U) one wavefront per member, the four waves taking members in turn: the in_resampler of a present, plumbed leg (the
 // run mask present & linked of mi_resampler_process_masked; any other keeps its history), from the head of the row back over
 // it -- rated_up for a leg below the mix, resample_down for one above it, rational_run (x 3/2 below, x 2/3 above) for
-// UD_R32, generic_run for UD_GEN (a loop of its own as well).  ua, qa, ga: null in a kernel without those forms.
+// UD_R32, generic_run for UD_GEN, offgrid_run for UD_OFF (loops of their own as well).  ua, qa, ga, oa: null in a kernel without
+// those forms.
 // The legs at 3/2 and 2/3 have a loop of their own, here and in (W): what a helper keeps per lane stays live over its own
 // loop only, and one loop over all forms is how a kernel goes past 128 VGPRs.
 template <int FORMS>
 __device__ __forceinline__ void resample_in(const Conf &k, const RatedArgs &ra, const UpdownArgs *ua, const RationalArgs *qa, float *scr,
-                                            const RatiosArgs *ga = nullptr) {
+                                            const RatiosArgs *ga = nullptr, const OffgridArgs *oa = nullptr) {
 	const int wave = k.t >> 6, lane = k.t & 63, ns = k.ns;
 	const int hin = FORMS >= F_ABOVE ? ua->hin_stride : RS_FILT;
 	for (int m = wave; m < k.mm; m += BT / 64) {
 		const int r = wave_ratio<FORMS>(k, m), n = FORMS >= F_ABOVE ? r & 7 : r;
-		if (r == 1 || (FORMS >= F_R32 && (r & UD_R32)) || (FORMS >= F_GEN && (r & UD_GEN)) || !k.s_on[m] || !((unsigned)k.s_par[m].x & MI_MIX_LINKED))
+		if (r == 1 || (FORMS >= F_R32 && (r & UD_R32)) || (FORMS >= F_GEN && (r & UD_GEN)) || (FORMS >= F_OFF && (r & UD_OFF)) || !k.s_on[m] ||
+		    !((unsigned)k.s_par[m].x & MI_MIX_LINKED))
 			continue;
 		int16_t *row = reinterpret_cast<int16_t *>(k.rows + m * k.row_w), *hist = ra.hist_in + (size_t)(k.s0 + m) * hin;
 		if (FORMS >= F_ABOVE && (r & UD_ABOVE))
@@ -599,19 +697,28 @@ __device__ __forceinline__ void resample_in(const Conf &k, const RatedArgs &ra, 
 		const int la = gen_a(r), cb = gen_b(r);
 		generic_run(scr, row, hist, ra.tab + ga->gen_tab[gen_code(r)].x, la, cb, filter_rule(la, cb).filt_len, ns / cb * la, lane);
 	}
+	if (FORMS < F_OFF) return;
+	for (int m = wave; m < k.mm; m += BT / 64) { // (44 100 Hz: leg -> conference is num : den, 441 samples in)
+		const int r = __builtin_amdgcn_readfirstlane(k.s_rt[m]);
+		if (!is_offgrid(r) || !k.s_on[m] || !((unsigned)k.s_par[m].x & MI_MIX_LINKED)) continue;
+		int16_t *row = reinterpret_cast<int16_t *>(k.rows + m * k.row_w), *hist = ra.hist_in + (size_t)(k.s0 + m) * hin;
+		offgrid_run(scr, row, hist, ra.tab + oa->tab_in, oa->num, oa->den, oa->filt_in, OFFGRID_LEN, lane);
+	}
 }
 
 // ---- (W) one wavefront per member: the out_resampler of a pin with its output on, then the leg's store or encoder --
 // resample_down for a leg below the mix; for one above it rated_up, for UD_R32 rational_run the other way, from the head of
-// the row back over the row (which held the leg's input, so it is wide enough), for UD_GEN generic_run likewise, then
-// store_row.  OUT as in (D).
+// the row back over the row (which held the leg's input, so it is wide enough), for UD_GEN generic_run and for UD_OFF
+// offgrid_run likewise, then store_row (and store_tail for the 441st sample).  OUT as in (D).
 template <int FORMS, int OUT>
 __device__ __forceinline__ void resample_out(const Conf &k, const RatedArgs &ra, const UpdownArgs *ua, const RationalArgs *qa, float *scr,
-                                             uint8_t *out, int pitch, const RatiosArgs *ga = nullptr) {
+                                             uint8_t *out, int pitch, const RatiosArgs *ga = nullptr, const OffgridArgs *oa = nullptr) {
 	const int wave = k.t >> 6, lane = k.t & 63, ns = k.ns;
 	for (int m = wave; m < k.mm; m += BT / 64) {
 		const int r = wave_ratio<FORMS>(k, m), n = FORMS >= F_ABOVE ? r & 7 : r;
-		if (r == 1 || (FORMS >= F_R32 && (r & UD_R32)) || (FORMS >= F_GEN && (r & UD_GEN)) || !((unsigned)k.s_par[m].x & MI_MIX_OUTPUT)) continue;
+		if (r == 1 || (FORMS >= F_R32 && (r & UD_R32)) || (FORMS >= F_GEN && (r & UD_GEN)) || (FORMS >= F_OFF && (r & UD_OFF)) ||
+		    !((unsigned)k.s_par[m].x & MI_MIX_OUTPUT))
+			continue;
 		int16_t *row = reinterpret_cast<int16_t *>(k.rows + m * k.row_w), *hist = ra.hist_out + (size_t)(k.s0 + m) * ra.hout_stride;
 		const int kind = OUT == BY_KIND ? __builtin_amdgcn_readfirstlane(k.s_cd[m] >> 2) : OUT;
 		const size_t at = (size_t)(k.s0 + m) * pitch;
@@ -639,6 +746,17 @@ __device__ __forceinline__ void resample_out(const Conf &k, const RatedArgs &ra,
 		const int la = gen_a(r), cb = gen_b(r);
 		generic_run(scr, row, hist, ra.tab + ga->gen_tab[gen_code(r)].y, cb, la, filter_rule(cb, la).filt_len, ns, lane);
 		store_row(row, out + (size_t)(k.s0 + m) * pitch, __builtin_amdgcn_readfirstlane(k.s_cd[m] >> 2), leg_span<FORMS>(r, ns), lane);
+	}
+	if (FORMS < F_OFF) return;
+	for (int m = wave; m < k.mm; m += BT / 64) { // (conference -> 44 100 Hz is den : num, 441 samples out: 55 groups and the tail)
+		const int r = __builtin_amdgcn_readfirstlane(k.s_rt[m]);
+		if (!is_offgrid(r) || !((unsigned)k.s_par[m].x & MI_MIX_OUTPUT)) continue;
+		int16_t *row = reinterpret_cast<int16_t *>(k.rows + m * k.row_w), *hist = ra.hist_out + (size_t)(k.s0 + m) * ra.hout_stride;
+		uint8_t *dst = out + (size_t)(k.s0 + m) * pitch;
+		const int kind = __builtin_amdgcn_readfirstlane(k.s_cd[m] >> 2);
+		offgrid_run(scr, row, hist, ra.tab + oa->tab_out, oa->den, oa->num, oa->filt_out, ns, lane);
+		store_row(row, dst, kind, OFFGRID_LEN, lane);
+		store_tail<OFFGRID_TAIL>(row, dst, kind, OFFGRID_LEN >> 3, lane);
 	}
 }
 

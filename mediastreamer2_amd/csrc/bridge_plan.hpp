@@ -53,12 +53,30 @@ MI_PLAN_HD inline FilterRule filter_rule(int num, int den) {
 }
 constexpr int GENERIC_MAX_FILT = 128, GENERIC_MAX_TERM = 8; // the longest filter generic_run takes; a and b of a : b in the byte
 
+// ---- the one rate off the 800 Hz grid (mi_bridge_create_offgrid): 44 100 Hz, a tick of 441 samples = 55 groups of eight and
+// one sample.  Against a mix at 100 n Hz that is 441 / g : n / g with g = gcd(441, n) -- whole periods either way, so
+// mi_resampler's position state is (0, 0) at every tick.  Its resamplers run in the generic order on the PER-PHASE table
+// (design_filter blends an interpolated design once per phase, up to 256 KB), read from memory by offgrid_run
+// (bridge_phases.hpp): the tables are 28 to 92 KB, more than a wavefront's scratch.
+constexpr int OFFGRID_RATE = 44100, OFFGRID_LEN = OFFGRID_RATE / 100;
+constexpr int OFFGRID_GROUPS = (OFFGRID_LEN + 7) / 8, OFFGRID_WORDS = (OFFGRID_LEN + 3) / 4; // the tail group holds one sample
+constexpr int OFFGRID_MAX_FILT = 264;                 // 44.1 -> 8 kHz
+constexpr size_t PHASE_TABLE_MAX = 256 * 1024;        // bytes: design_filter's bound on a per-phase table
+// whether design_filter has a per-phase table for in : out = num : den, direct or blended
+MI_PLAN_HD inline bool has_phase_table(int num, int den) {
+	const FilterRule f = filter_rule(num, den);
+	return f.direct || (size_t)den * f.filt_len * sizeof(float) <= PHASE_TABLE_MAX;
+}
+
 // ---- a member's ratio byte.  Conference rate / leg rate (1, 2, 3 or 6; 4 under mi_bridge_create_ratios) for a leg at or
 // below the mix; with UD_ABOVE the leg is above it and the low three bits are leg rate / conference rate; with UD_R32 the
 // ratio is 3/2 (the whole part: 1), UD_ABOVE still giving the direction.  With UD_GEN the leg stands a : b to the mix, any
 // other non-whole ratio of mi_bridge_create_ratios: a - 1 in bits 0-2, b - 1 in bits 3, 4 and 6, UD_ABOVE where a > b.  The
 // kernels read it through leg_span (bridge_phases.hpp).
-constexpr unsigned UD_ABOVE = 0x80, UD_R32 = 0x40, UD_GEN = 0x20;
+// With UD_OFF, and neither UD_GEN nor UD_R32, the leg is at 44 100 Hz (mi_bridge_create_offgrid): the byte says no more than
+// that and UD_ABOVE -- the one pair num : den, its filters and tables are the bridge's, not the leg's (OffgridArgs).
+constexpr unsigned UD_ABOVE = 0x80, UD_R32 = 0x40, UD_GEN = 0x20, UD_OFF = 0x10;
+MI_PLAN_HD inline bool is_offgrid(int rb) { return (rb & (int)(UD_GEN | UD_R32 | UD_OFF)) == (int)UD_OFF; }
 constexpr int NO_WHOLE_RATIO = -1, RATIO_NOT_SERVED = -2;
 MI_PLAN_HD inline int gen_a(int rb) { return (rb & 7) + 1; }
 MI_PLAN_HD inline int gen_b(int rb) { return ((rb >> 3) & 3) + ((rb >> 4) & 4) + 1; }
@@ -88,7 +106,8 @@ struct Rules {
 	// rate or codec is served by the per-leg concealer, not refused; rational: a leg may be at 3/2 or 2/3 of the mix
 	// ratios: a leg may be at 4 or 1/4 of the mix, or stand a : b to it wherever both its resamplers have a direct table of at
 	// most 128 taps
-	bool above, leg_plc, rational, ratios;
+	// offgrid: a leg may be at 44 100 Hz wherever both its resamplers have a per-phase table of at most 264 taps
+	bool above, leg_plc, rational, ratios, offgrid = false;
 };
 constexpr Rules RULES_RATED = {"mi_bridge_create_rated", "mi_bridge_create_rated", false, false, false};
 constexpr Rules RULES_LEGS = {"mi_bridge_create_legs", "mi_bridge_create_rated", false, false, false};
@@ -96,11 +115,12 @@ constexpr Rules RULES_ENDPOINTS = {"mi_bridge_create_endpoints", "mi_bridge_crea
 constexpr Rules RULES_CONCEALED = {"mi_bridge_create_concealed", "mi_bridge_create_endpoints", true, true, false};
 constexpr Rules RULES_RATIONAL = {"mi_bridge_create_rational", "mi_bridge_create_rational", true, true, true};
 constexpr Rules RULES_RATIOS = {"mi_bridge_create_ratios", "mi_bridge_create_ratios", true, true, true, true};
+constexpr Rules RULES_OFFGRID = {"mi_bridge_create_offgrid", "mi_bridge_create_offgrid", true, true, true, true, true};
 
 struct Plan {
 	// which kernel a tick launches, chosen once: compile-time codecs without and with resamplers, per-leg codecs without and
-	// with them, a leg above the mix, a leg at 3/2 or 2/3 of it, a leg at 4, 1/4 or a : b
-	enum Family { TICK, RATED, LEGS, LEGS_RATED, UPDOWN, RATIONAL, RATIOS } family = TICK;
+	// with them, a leg above the mix, a leg at 3/2 or 2/3 of it, a leg at 4, 1/4 or a : b, a leg at 44 100 Hz
+	enum Family { TICK, RATED, LEGS, LEGS_RATED, UPDOWN, RATIONAL, RATIOS, OFFGRID } family = TICK;
 	mi_bridge_config cfg = {}; // in_codec, out_codec: leg 0's where the legs were given
 	int n = 0, nconf = 0, mm = 0, len = 0;
 	// a leg not at the conference's rate (ratio bytes, resamplers, tables); one above the mix by a whole ratio; one at 3/2 or 2/3 of
@@ -108,6 +128,10 @@ struct Plan {
 	bool rated = false, updown = false, rational = false, leg_plc = false;
 	bool ratios = false;          // a leg at 4 or 1/4 of the mix, or at a : b: only mi_bridge_create_ratios plans one
 	std::vector<uint8_t> generic; // the distinct UD_GEN ratio bytes of the legs: a pair of tables each (gen_code)
+	// a leg at 44 100 Hz: only mi_bridge_create_offgrid plans one.  off_num : off_den is leg : mix in lowest terms, off_fin and
+	// off_fout the taps of its in_resampler (leg -> mix, off_den rows) and its out_resampler (mix -> leg, off_num rows)
+	bool offgrid = false;
+	int off_num = 0, off_den = 0, off_fin = 0, off_fout = 0;
 	bool used[7] = {}, above[7] = {};         // the whole ratios of legs below the mix, and of legs above it
 	bool r32_above = false, r32_below = false; // a leg at 3/2 of the mix, a leg at 2/3
 	int max_ratio = 1, common = 0; // common: the first leg's rate, the one concealer batch's
@@ -116,6 +140,8 @@ struct Plan {
 	size_t lds = 0;                         // dynamic LDS of a launch
 	int scratch_off = 0, scratch_per_wave = 0; // bytes: each wavefront's resampler scratch in it
 	int pitch = 0;                          // samples per row of the host buffers: the widest leg's tick
+	// samples per row of the PCM the per-leg concealer hands the kernel: whole groups of eight (448 for a 441-sample tick)
+	int pcm_pitch() const { return (pitch + 7) & ~7; }
 	size_t in_bytes = 0, out_bytes = 0;     // per stream and tick, on the host side; byte rows' pitch where the codecs are data
 	int hin_stride = RS_FILT, hout_stride = 0; // samples per member of the in_resamplers' and out_resamplers' histories
 	std::vector<int32_t> leg_rate;  // [n], empty: every leg at cfg.rate
@@ -155,6 +181,8 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 	const auto idx = [&](int s) { return own >= 0 && s >= own ? (s - own) / mm : s; };
 	bool mixed = false, differ = false; // the legs' pairs differ: the codecs are the kernel's data; they or the rates do
 	for (int s = 1; codec && s < n; ++s) mixed |= codec[s] != codec[0], differ |= codec[s] != codec[0] || (rates && rates[s] != rates[0]);
+	// (a 44 100 Hz leg's tick is no whole groups of eight: only the per-leg concealer, behind the legs' decoders, takes it)
+	for (int s = 0; rules.offgrid && rates && s < n; ++s) differ |= rates[s] == OFFGRID_RATE;
 	p->leg_plc = rules.leg_plc && cfg->plc && differ;
 	const char *fn = p->leg_plc ? rules.fn : rules.rates_fn;
 	// ---- the legs' rates
@@ -164,6 +192,30 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 		const int lr = rates[s];
 		MI_PLAN_ARG(lr > 0);
 		const bool up = lr > cfg->rate;
+		if (rules.offgrid && lr % 800 != 0) { // the one rate off the grid that is a whole tick and has its tables, or the reason
+			if (lr % 100 != 0)
+				MI_REFUSE("%s: %s %d at %d Hz in a %d Hz conference: %d.%02d samples are no 10 ms tick; off the 800 Hz grid only %d Hz is served",
+				          fn, who(s), idx(s), lr, cfg->rate, lr / 100, lr % 100, OFFGRID_RATE);
+			if (lr != OFFGRID_RATE)
+				MI_REFUSE("%s: %s %d at %d Hz in a %d Hz conference: the rate is no multiple of 800 (a 10 ms tick must be whole groups of 8 "
+				          "samples); off that grid only %d Hz is served", fn, who(s), idx(s), lr, cfg->rate, OFFGRID_RATE);
+			int g = OFFGRID_LEN, h = len;
+			while (h) { const int t = g % h; g = h, h = t; }
+			const int la = OFFGRID_LEN / g, cb = len / g; // leg : mix
+			const FilterRule in = filter_rule(la, cb), out = filter_rule(cb, la);
+			if (!has_phase_table(la, cb) || !has_phase_table(cb, la) || in.filt_len > OFFGRID_MAX_FILT || out.filt_len > OFFGRID_MAX_FILT)
+				MI_REFUSE("%s: %s %d at %d Hz in a %d Hz conference is %d : %d, a ratio whose resamplers have no per-phase table of at most "
+				          "%zu KB and %d taps (%d taps in %d rows one way, %d in %d the other)", fn, who(s), idx(s), lr, cfg->rate, la, cb,
+				          PHASE_TABLE_MAX / 1024, OFFGRID_MAX_FILT, in.filt_len, cb, out.filt_len, la);
+			if (cfg->plc && !p->leg_plc && p->common && lr != p->common)
+				MI_REFUSE("%s: plc with legs at %d Hz and %d Hz: the concealer batch has one rate", fn, p->common, lr);
+			if (!p->common) p->common = lr;
+			widest = std::max(widest, lr);
+			p->offgrid = true, p->off_num = la, p->off_den = cb, p->off_fin = in.filt_len, p->off_fout = out.filt_len;
+			data |= codec != nullptr; // (such a leg brings the codecs as data, whether they differ or not)
+			p->ratio.push_back((uint8_t)(UD_OFF | (up ? UD_ABOVE : 0u)));
+			continue;
+		}
 		int rb = ratio_byte(lr, cfg->rate);
 		if (rb >= 0 && (rb & UD_R32) && !rules.rational) rb = NO_WHOLE_RATIO;
 		bool added = false; // a form only mi_bridge_create_ratios plans
@@ -214,10 +266,12 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 		p->ratio.push_back((uint8_t)rb);
 	}
 	p->rational = p->r32_above || p->r32_below; // without such a leg: mi_bridge_create_concealed's bridge exactly
-	p->rated = p->max_ratio > 1 || p->rational || !p->generic.empty();
+	p->rated = p->max_ratio > 1 || p->rational || !p->generic.empty() || p->offgrid;
 	if (!p->rated) p->ratio.clear();
 	// ---- the LDS of a launch.  Samples per row: the widest leg's tick where one is above the mix
 	p->wide = p->updown ? widest / 100 : p->rational || !p->generic.empty() ? std::max(len, widest / 100) : len;
+	// a 441-sample tick is staged, levelled and stored in whole groups of eight, the tail group's other seven zero: 448 samples
+	if (p->offgrid) p->wide = std::max(len, (widest / 100 + 7) & ~7);
 	p->row_w = (p->wide >> 2) | 1;
 	p->sum_off = (int)up16((size_t)mm * p->row_w * 8);
 	p->nslice = std::max(1, std::min(mm, BT / (len >> 2)));
@@ -250,13 +304,18 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 			scratch = std::max(scratch, up16(std::max(generic_scratch(fin, cb, len / cb * la), generic_scratch(fout, la, len))));
 			generic_hist = std::max(generic_hist, (std::max(fin, fout) - 1 + 7) & ~7);
 		}
+		// a leg at 44 100 Hz: history ++ tick as floats either way, nothing else -- the tables stay in memory (offgrid_run)
+		if (p->offgrid) {
+			scratch = std::max(scratch, up16(sizeof(float) * (size_t)std::max(generic_xlen(p->off_fin, OFFGRID_LEN), generic_xlen(p->off_fout, len))));
+			generic_hist = std::max(generic_hist, (std::max(p->off_fin, p->off_fout) - 1 + 7) & ~7); // up to 263 samples
+		}
 		const size_t scratch_off = up16(lds);
 		lds = scratch_off + (BT / 64) * scratch;
 		if (lds + RATED_STATIC_LDS > BRIDGE_LDS_MAX)
 			MI_REFUSE("%s: a conference's tick and its resamplers' scratch must fit %zu bytes of LDS (%d members x %d samples "
 			          "= %zu, + %d wavefronts x %zu for ratio %d%s, + %zu of the kernel's own: %zu)",
 			          fn, BRIDGE_LDS_MAX, mm, p->wide, scratch_off, BT / 64, scratch, p->max_ratio,
-			          !p->generic.empty() ? " and a : b" : p->rational ? " and 3/2" : "", RATED_STATIC_LDS,
+			          p->offgrid ? " and 44100 Hz" : !p->generic.empty() ? " and a : b" : p->rational ? " and 3/2" : "", RATED_STATIC_LDS,
 			          lds + RATED_STATIC_LDS);
 		p->scratch_off = (int)scratch_off, p->scratch_per_wave = (int)scratch;
 		p->hout_stride = p->max_ratio * RS_FILT; // mi_resampler's round_up(filt_len - 1, 8) of the longest filter
@@ -282,7 +341,7 @@ inline int plan_bridge(const Rules &rules, const mi_bridge_config *cfg, const in
 	}
 	if (rates) p->leg_rate.assign(rates, rates + n);
 	// the widest form a leg needs: the order matters
-	p->family = p->ratios ? Plan::RATIOS : p->rational ? Plan::RATIONAL : p->updown ? Plan::UPDOWN : data ? (p->rated ? Plan::LEGS_RATED : Plan::LEGS)
+	p->family = p->offgrid ? Plan::OFFGRID : p->ratios ? Plan::RATIOS : p->rational ? Plan::RATIONAL : p->updown ? Plan::UPDOWN : data ? (p->rated ? Plan::LEGS_RATED : Plan::LEGS)
 	            : p->rated  ? Plan::RATED : Plan::TICK;
 	return MI_OK;
 }

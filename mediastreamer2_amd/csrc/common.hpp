@@ -110,6 +110,10 @@ struct ResamplerView {
 };
 struct mi_resampler;
 void mi_resampler_view(mi_resampler *r, ResamplerView *v);
+// The table mi_resampler's generic kernel runs as a direct one, [den][filt_len] floats: the direct design, or an interpolated
+// design blended once per phase (resample.hip's Design::phase_table, which mi_resampler_get_table does not hand out).  Returns
+// its length, copying where cap allows; 0 for a design that has neither.  For the bridge's 44 100 Hz legs (bridge.hip).
+int mi_resampler_get_phase_table(const mi_resampler *r, float *h_dst, int cap);
 
 // What the fused volume + conference mix kernel (volume.hip) needs of an mi_mixer: its per-pin controls
 struct MixerView {

@@ -429,8 +429,16 @@ struct LegBlock {
 	const uint8_t *in;
 	int kind;
 	__device__ __forceinline__ void operator()(int16_t *blk, const int16_t *, int n, int lane) const {
-		for (int g = lane; g < (n >> 3); g += 64) // (a leg's tick is whole groups of eight: its rate is a multiple of 800)
+		for (int g = lane; g < (n >> 3); g += 64) // (a leg's tick is whole groups of eight where its rate is a multiple of 800)
 			*reinterpret_cast<uint4 *>(blk + 8 * g) = decode_group_leg(load_raw_leg(in, kind, g), kind, g);
+		// a 441-sample tick (44 100 Hz, the bridge's one rate off that grid) ends in one sample: the tail one unit per lane, not
+		// a byte read past the leg's own
+		const int i = (n & ~7) + lane;
+		if (i < n) {
+			const uint32_t c = in[i];
+			blk[i] = kind == MI_SESSION_PCM16 ? reinterpret_cast<const int16_t *>(in)[i]
+			                                  : (int16_t)((kind == MI_SESSION_PCMU ? ulaw2lin_x2(c) : alaw2lin_x2(c)) & 0xffffu);
+		}
 	}
 };
 
@@ -762,12 +770,12 @@ int mi_plc_create_legs(mi_ctx *c, int nstreams, const int32_t *h_rate, const uin
 	int rc;
 	for (int k = 0; k < nopen; ++k) {
 		if ((rc = mi_plc_check_rate("mi_plc_create", "admitted rate", k, h_open_rate[k])) != MI_OK) return rc;
-		MI_CHECK_ARG(h_open_rate[k] % 800 == 0 && h_open_rate[k] / 100 <= pitch);
+		MI_CHECK_ARG((h_open_rate[k] % 800 == 0 || h_open_rate[k] == 44100) && h_open_rate[k] / 100 <= pitch);
 	}
 	for (int s = 0; s < nstreams; ++s) {
 		if ((rc = mi_plc_check_rate("mi_plc_create", "stream", s, h_rate[s])) != MI_OK) return rc;
-		// a tick is whole 16-byte groups of PCM inside the row, and the row holds one of the three kinds
-		MI_CHECK_ARG(h_rate[s] % 800 == 0 && h_rate[s] / 100 <= pitch && h_kind[s] <= MI_SESSION_PCMU);
+		// a tick is whole 16-byte groups of PCM inside the row (and, at 44 100 Hz, one sample), and the row holds one of the three kinds
+		MI_CHECK_ARG((h_rate[s] % 800 == 0 || h_rate[s] == 44100) && h_rate[s] / 100 <= pitch && h_kind[s] <= MI_SESSION_PCMU);
 	}
 	if ((rc = c->activate()) != MI_OK) return rc;
 	mi_plc *p = new mi_plc();

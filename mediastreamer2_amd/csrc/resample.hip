@@ -793,5 +793,14 @@ int mi_resampler_process_host(mi_resampler *r, const int16_t *h_in, int in_len, 
 
 } // extern "C"
 
+// (common.hpp) what resample_generic_kernel reads as a direct table: [den][filt_len], the direct design itself or the
+// per-phase blend of an interpolated one; 0 floats where the design has neither
+int mi_resampler_get_phase_table(const mi_resampler *r, float *h_dst, int cap) {
+	if (!r) return MI_EINVAL;
+	const int n = r->dev_direct() ? (int)r->dev_table().size() : 0;
+	if (h_dst && n > 0 && cap >= n) memcpy(h_dst, r->dev_table().data(), sizeof(float) * (size_t)n);
+	return n;
+}
+
 // (mi_warmup, ctx.hip: this unit's code object is loaded when the library is, not under a tick's first launch)
 static const mi::WarmEntry g_warm_resample(reinterpret_cast<const void *>(&fill_pos_kernel));
