@@ -869,7 +869,12 @@ class Session(_ConferenceBatch):
     _destroy, _prefix = "mi_session_destroy", "session"
 
     def __init__(self, ctx, nstreams, members=32, in_rate=16000, rate=48000, tail_ms=128, agc=True, use_graphs=True,
-                 mic_codec=0, out_rate=0, out_codec=0, ref_loopback=False, ref_delay_ms=0, plc=False, stagger=False):
+                 mic_codec=0, out_rate=0, out_codec=0, ref_loopback=False, ref_delay_ms=0, plc=False, stagger=False, legs=None):
+        """legs: every leg's (rate, mic_codec, out_codec) [nstreams], a sequence of triples (mi_session_create_legs,
+        include/msmi355x_session.h): `rate` is the canceller's and the mixer's, every leg at rate / 1, 2, 3 or 6 with its own
+        codecs; in_rate, out_rate, mic_codec and out_codec are not read.  With legs that differ the staging views are byte rows,
+        uint8 [n, pitch] at tick_bytes' pitches, and a leg fills / receives the first leg_bytes(stream) of its row; legs of one
+        kind give mi_session_create's session and its views."""
         self.ctx = ctx
         cfg = SessionConfig()
         ctx.L.mi_session_default_config(C.byref(cfg))
@@ -879,7 +884,16 @@ class Session(_ConferenceBatch):
         cfg.ref_loopback, cfg.ref_delay_ms, cfg.plc = int(ref_loopback), ref_delay_ms, int(plc)
         cfg.stagger = int(stagger)  # (the C default is 1; the wrapper's tests compare with hand-made chains that start empty)
         h = C.c_void_p()
-        check(ctx.L.mi_session_create(ctx.h, C.byref(cfg), C.byref(h)))
+        if legs is None:
+            check(ctx.L.mi_session_create(ctx.h, C.byref(cfg), C.byref(h)))
+        else:
+            lg = np.ascontiguousarray(legs, np.int32)
+            assert lg.shape == (nstreams, 3), "one (rate, mic_codec, out_codec) per leg"
+            check(ctx.L.mi_legs_session_create(ctx.h, C.byref(cfg), lg.ctypes.data, C.byref(h)))
+            if len({tuple(k) for k in lg.tolist()}) == 1:  # one kind: mi_session_create's session
+                in_rate = out_rate = int(lg[0, 0])
+                mic_codec, out_codec = int(lg[0, 1]), int(lg[0, 2])
+                legs = None
         self.h = h
         self.n, self.in_len, self.len = nstreams, in_rate // 100, rate // 100
         self.members = members
@@ -887,6 +901,9 @@ class Session(_ConferenceBatch):
         self.mic_dtype = C.c_uint8 if mic_codec else C.c_int16
         self.out_dtype = C.c_uint8 if out_codec else C.c_int16
         self.loopback = bool(ref_loopback)
+        if legs is not None:  # byte rows at mi_session_tick_bytes' pitches
+            self.mic_dtype = self.out_dtype = C.c_uint8
+            self.in_len, _, self.out_len = self.tick_bytes()
 
     def _view(self, ptr, cols, ctype=C.c_int16):
         return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(self.n, cols))
@@ -895,6 +912,23 @@ class Session(_ConferenceBatch):
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
         check(self.ctx.L.mi_session_tick_bytes(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def leg_rate(self, stream):
+        r = self.ctx.L.mi_legs_session_rate(self.h, int(stream))
+        check(min(r, 0))
+        return r
+
+    def leg_codec(self, stream):
+        """(mic_codec, out_codec) of the leg"""
+        a, b = C.c_int32(), C.c_int32()
+        check(self.ctx.L.mi_legs_session_codec(self.h, int(stream), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def leg_bytes(self, stream):
+        """(mic bytes, out bytes) of the leg's tick: what it fills and receives of its rows"""
+        a, b = C.c_int32(), C.c_int32()
+        check(self.ctx.L.mi_legs_session_bytes(self.h, int(stream), C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def acquire(self):
         """numpy views of the pinned staging of the next tick: (mic [n, in_len], ref [n, len] or None with loopback)."""

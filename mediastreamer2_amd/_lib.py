@@ -73,9 +73,15 @@ BRIDGE_EXPORTS = [
     "mi_bridge_change_controls", "mi_bridge_set_reports", "mi_bridge_collected_report",
 ]
 
-# every symbol include/msmi355x_session.h declares: mi_session's membership without a drain, in the same library
+# every mi_session_* symbol include/msmi355x_session.h declares: mi_session's membership without a drain, in the same library
 SESSION_EXPORTS = [
     "mi_session_change_members",
+]
+
+# the symbols behind that header's mi_session_create_legs, mi_session_leg_rate, _codec and _bytes (inline functions there): legs
+# at their own rate and codec
+SESSION_LEG_EXPORTS = [
+    "mi_legs_session_create", "mi_legs_session_rate", "mi_legs_session_codec", "mi_legs_session_bytes",
 ]
 
 # every symbol include/msmi355x_session_controls.h declares: mi_session's mute, gain and reports without a drain
@@ -318,6 +324,10 @@ def load():
     L.mi_bridge_get_volume_state.argtypes = [vp, i32, i32, C.POINTER(VolumeState)]
     L.mi_bridge_get_volume_max.argtypes = [vp, i32, i32, vp]
     L.mi_session_change_members.argtypes = [vp, vp, i32]
+    L.mi_legs_session_create.argtypes = [vp, vp, vp, pp]
+    L.mi_legs_session_rate.argtypes = [vp, i32]
+    L.mi_legs_session_codec.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.mi_legs_session_bytes.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     for p in ("session", "bridge"):
         getattr(L, f"mi_{p}_change_controls").argtypes = [vp, vp, i32]
         getattr(L, f"mi_{p}_set_reports").argtypes = [vp, u32]

@@ -45,6 +45,7 @@
 #include "bridge_phases.hpp"
 #include "bridge_roster.hpp"
 #include "controls.hpp"
+#include "resample_tables.hpp"
 
 #pragma clang fp contract(off)
 
@@ -416,19 +417,7 @@ int reset_resamplers(mi_bridge *b, int first, int count) {
 	return MI_OK;
 }
 
-// the polyphase table of mi_resampler's own design code (quality 3, what msresample.c uses) for in_rate -> out_rate
-// filt_len, direct: mi_resampler_info's verdict on that design
-int design_table(mi_ctx *ctx, int in_rate, int out_rate, std::vector<float> &table, int *filt_len = nullptr, int *direct = nullptr) {
-	mi_resampler *r = nullptr;
-	int rc = mi_resampler_create(ctx, 1, (uint32_t)in_rate, (uint32_t)out_rate, 3, &r);
-	if (rc != MI_OK) return rc;
-	table.resize((size_t)mi_resampler_get_table(r, nullptr, 0));
-	mi_resampler_get_table(r, table.data(), (int)table.size());
-	rc = mi_resampler_info(r, filt_len, nullptr, nullptr, direct);
-	mi_resampler_destroy(r);
-	return rc;
-}
-
+// (design_table, the polyphase table of mi_resampler's own design code: resample_tables.hpp)
 // one table per distinct ratio and direction, built once and back to back in d_tab, its float offset noted in b->args.  A table
 // is designed as [L][taps] polyphase rows for in_rate : out_rate = M : L and laid out as its reader wants it: AS_DESIGNED, an
 // up-sampler by r: [r][48]; PHASE_MAJOR, a down-sampler by r: tap r * i + p at [p][i]; REARRANGED, x 3/2 and x 2/3: [L][24 * M]
@@ -487,9 +476,7 @@ int build_tables(mi_bridge *b) {
 		const int g = std::min(w.in_rate, w.out_rate) / (w.layout == REARRANGED ? 2 : 1); // the rates are M * g and L * g
 		const int L = w.out_rate / g, M = w.in_rate / g;
 		if (w.layout == AS_DESIGNED) all.insert(all.end(), t.begin(), t.end());
-		else if (w.layout == PHASE_MAJOR)
-			for (int p = 0; p < M; ++p)
-				for (int i = 0; i < RS_FILT; ++i) all.push_back(t[(size_t)i * M + p]);
+		else if (w.layout == PHASE_MAJOR) append_phase_major(all, t, M, RS_FILT);
 		else
 			for (int r = 0; r < L; ++r)
 				for (int pp = 0; pp < M; ++pp)

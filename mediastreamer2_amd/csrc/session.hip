@@ -11,11 +11,15 @@
 // buffer slot) replay the kernel sequence.  Pinned host buffers belong to the session: the caller fills / reads them in place.
 // Membership, controls and reports -- waiting or carried by the ticks -- are mi::ConferencePlane's (controls.hpp); here is what
 // is the session's own: launch_seats, mi_session_reset_streams, the rows a departed leg leaves behind, two meter read-outs.
+// mi_session_create_legs: legs at their own rate and codec -- the plan is session_plan.hpp's, the two launches around the
+// canceller and the mixer session_legs.hip's (run_leg_tick).
 #include "common.hpp"
 
 #include "../../include/msmi355x_session.h"
 #include "../../include/msmi355x_session_controls.h"
 #include "controls.hpp"
+#include "session_legs.hpp"
+#include "session_plan.hpp"
 #include "session_roster.hpp"
 
 #include <cmath>
@@ -53,11 +57,58 @@ struct mi_session {
 	// conference membership, controls and reports (MSAudioConference), the waiting calls' and what travels with the ticks: controls.hpp
 	mi::ConferencePlane conf;
 	int lead_unit = 0, lead_phases = 0; // cfg.stagger: mi_aec_stagger_info's, what a fresh seat's queues lead with
+	// mi_session_create_legs: every leg's kind as it was given (empty: mi_session_create's session, cfg's one kind).  With legs
+	// that differ, `plan` is whole and `legs` holds their ingress and egress (session_legs.hip): `mic` and `out` are byte rows at
+	// mic_bytes / out_bytes, no mi_resampler and no encoder's launch, d_up the ingress' tick at `rate`, the mix always kept
+	std::vector<mi_session_leg> kinds;
+	SessionPlan plan;
+	SessionLegs *legs = nullptr;
 };
 
 namespace {
 
+// the mixer side of a tick, into `mix` [n][len]: what both kinds of session run behind the canceller
+int level_and_mix(mi_session *s, int16_t *mix) {
+	int rc;
+	// MSVolume on the tick the mixer side reads: popped from the canceller's output FIFO inside the kernel where the sizes
+	// allow 16-byte groups (every rate in use), else pop + process
+	// MSVolume + MSAudioMixer: one launch (every leg's tick popped from the canceller's output FIFO, levelled, the conference
+	// mixed from the levelled ticks on the chip) where the sizes allow 16-byte groups (every rate in use); else pop, level, mix
+	rc = s->fuse_mix ? mi_mixer_process_volume_fifo(s->mix, s->vol, 0, s->f_out, mix) : MI_ENOTSUP;
+	if (rc == MI_ENOTSUP) {
+		s->fuse_mix = false;
+		if ((s->len & 7) == 0) {
+			if ((rc = mi_volume_process_fifo(s->vol, s->f_out, s->d_tick, s->len, s->len)) != MI_OK) return rc;
+		} else {
+			if ((rc = mi_fifo_pop(s->f_out, s->len, s->d_tick, s->len, nullptr, nullptr, 1)) != MI_OK) return rc;
+			if ((rc = mi_volume_process(s->vol, s->d_tick, s->len, s->len, nullptr)) != MI_OK) return rc;
+		}
+		rc = mi_mixer_process(s->mix, s->d_tick, nullptr, 1, mix);
+	}
+	return rc;
+}
+
+// a tick of a session whose legs differ (mi_session_create_legs): the concealer with the decoders inside, the ingress, the
+// canceller on the ingress' tick, volume + mix into the kept mix, the egress
+int run_leg_tick(mi_session *s, int slot) {
+	int rc;
+	const uint8_t *in = reinterpret_cast<const uint8_t *>(s->d_mic[slot]);
+	size_t in_pitch = s->mic_bytes;
+	if (s->plc) { // every leg's decoder and MSGenericPLC at its own rate: byte rows in, PCM rows out
+		if ((rc = mi_plc_process_legs(s->plc, in, s->mic_bytes, s->d_pcm, (size_t)s->plan.pcm_pitch, s->d_ev[slot])) != MI_OK) return rc;
+		in = reinterpret_cast<const uint8_t *>(s->d_pcm), in_pitch = (size_t)s->plan.pcm_pitch * sizeof(int16_t);
+	}
+	if ((rc = mi_session_legs_ingress(s->legs, in, in_pitch, s->plc != nullptr, s->d_up, s->up_stride)) != MI_OK) return rc;
+	const int16_t *ref = s->cfg.ref_loopback ? s->d_mix[(slot + SLOTS - 1) % SLOTS] : s->d_ref[slot];
+	if ((rc = mi_aec_process_fifos(s->aec, s->f_mic, s->d_up, s->up_stride, s->f_ref, ref, s->len, nullptr, s->len, s->f_out, s->rounds,
+	                               MI_AEC_POSTFILTER, nullptr)) != MI_OK)
+		return rc;
+	if ((rc = level_and_mix(s, s->d_mix[slot])) != MI_OK) return rc;
+	return mi_session_legs_egress(s->legs, s->d_mix[slot], reinterpret_cast<uint8_t *>(s->d_out[slot]), s->out_bytes);
+}
+
 int run_tick_kernels(mi_session *s, int slot) { // everything on the context's stream
+	if (s->legs) return run_leg_tick(s, slot);
 	int rc;
 	const mi_session_config &cf = s->cfg;
 	const int16_t *mic = s->d_mic[slot];
@@ -94,23 +145,8 @@ int run_tick_kernels(mi_session *s, int slot) { // everything on the context's s
 		                          MI_AEC_POSTFILTER, nullptr);
 	}
 	if (rc != MI_OK) return rc;
-	// MSVolume on the tick the mixer side reads: popped from the canceller's output FIFO inside the kernel where the sizes
-	// allow 16-byte groups (every rate in use), else pop + process
 	int16_t *mix = s->d_mix[slot] ? s->d_mix[slot] : s->d_out[slot];
-	// MSVolume + MSAudioMixer: one launch (every leg's tick popped from the canceller's output FIFO, levelled, the conference
-	// mixed from the levelled ticks on the chip) where the sizes allow 16-byte groups (every rate in use); else pop, level, mix
-	rc = s->fuse_mix ? mi_mixer_process_volume_fifo(s->mix, s->vol, 0, s->f_out, mix) : MI_ENOTSUP;
-	if (rc == MI_ENOTSUP) {
-		s->fuse_mix = false;
-		if ((s->len & 7) == 0) {
-			if ((rc = mi_volume_process_fifo(s->vol, s->f_out, s->d_tick, s->len, s->len)) != MI_OK) return rc;
-		} else {
-			if ((rc = mi_fifo_pop(s->f_out, s->len, s->d_tick, s->len, nullptr, nullptr, 1)) != MI_OK) return rc;
-			if ((rc = mi_volume_process(s->vol, s->d_tick, s->len, s->len, nullptr)) != MI_OK) return rc;
-		}
-		rc = mi_mixer_process(s->mix, s->d_tick, nullptr, 1, mix);
-	}
-	if (rc != MI_OK) return rc;
+	if ((rc = level_and_mix(s, mix)) != MI_OK) return rc;
 	const int16_t *leaving = mix;
 	int pitch = s->len;
 	if (s->rs_out) { // MSResample rate -> out_rate
@@ -134,6 +170,11 @@ int launch_seats(mi_session *s, int slot, const mi_seat_cmd *d_cmd, int count) {
 	mi_aec_edit(s->aec, &ra.aec);
 	mi_resampler_edit(s->rs, &ra.rs_in);
 	mi_resampler_edit(s->rs_out, &ra.rs_out);
+	if (s->legs) { // the two per-leg history rows: a tick is whole periods, so these resamplers keep no position
+		ra.leg_rows = true;
+		ra.rs_in.hist = s->legs->d_hist_in, ra.rs_in.hist_stride = s->plan.hin_stride;
+		ra.rs_out.hist = s->legs->d_hist_out, ra.rs_out.hist_stride = s->plan.hout_stride;
+	}
 	mi_volume_edit(s->vol, &ra.vol);
 	MixerEdit me;
 	mi_mixer_edit(s->mix, &me);
@@ -188,6 +229,7 @@ void mi_session_destroy(mi_session *s) {
 	if (s->rs) mi_resampler_destroy(s->rs);
 	if (s->rs_out) mi_resampler_destroy(s->rs_out);
 	if (s->plc) mi_plc_destroy(s->plc);
+	if (s->legs) mi_session_legs_destroy(s->legs);
 	if (s->aec) mi_aec_destroy(s->aec);
 	if (s->vol) mi_volume_destroy(s->vol);
 	if (s->mix) mi_mixer_destroy(s->mix);
@@ -198,7 +240,9 @@ void mi_session_destroy(mi_session *s) {
 	delete s;
 }
 
-int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **out) {
+// lp: mi_session_create_legs' plan for legs that differ (cfg then names `rate` in and out and PCM, and the rows, the resamplers,
+// the codecs and the concealer are the plan's), or null: mi_session_create's session
+static int build_session(mi_ctx *ctx, const mi_session_config *cfg, const SessionPlan *lp, mi_session **out) {
 	MI_CHECK_ARG(ctx && cfg && out);
 	*out = nullptr;
 	MI_CHECK_ARG(cfg->nstreams > 0 && cfg->members_per_conference > 0 && cfg->nstreams % cfg->members_per_conference == 0);
@@ -218,6 +262,7 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 	s->mic_bytes = (size_t)s->in_len * (cfg->mic_codec ? 1 : 2);
 	s->ref_bytes = cfg->ref_loopback ? 0 : (size_t)s->len * 2;
 	s->out_bytes = (size_t)s->out_len * (cfg->out_codec ? 1 : 2);
+	if (lp) s->plan = *lp, s->mic_bytes = lp->mic_pitch, s->out_bytes = lp->out_pitch; // byte rows at one pitch
 	s->frame = mi_aec_framesize(64, cfg->rate); // speexec.c:41,171-180
 	int rc = MI_OK;
 	auto fail = [&](int code) {
@@ -263,25 +308,43 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 			s->d_ref[i] = (int16_t *)mi_dev_alloc(ctx, n * s->ref_bytes);
 			if (!s->h_ref[i] || !s->d_ref[i]) return fail(MI_ENOMEM);
 		}
-		if (cfg->ref_loopback || down || cfg->out_codec) { // the mix at `rate` is kept: next tick's reference and / or the encoder's input
+		if (lp) { // what lies in a row past its leg's bytes is never written: it reads as zeros
+			MI_HIP(hipMemsetAsync(s->d_out[i], 0, n * s->out_bytes, ctx->stream));
+			memset(s->h_out[i], 0, n * s->out_bytes);
+		}
+		if (cfg->ref_loopback || down || cfg->out_codec || lp) { // the mix at `rate` is kept: next tick's reference and / or the encoder's input
 			s->d_mix[i] = (int16_t *)mi_dev_alloc(ctx, n * s->len * 2);
 			if (!s->d_mix[i]) return fail(MI_ENOMEM);
 			MI_HIP(hipMemsetAsync(s->d_mix[i], 0, n * s->len * 2, ctx->stream));
 		}
 	}
-	if (s->rs) s->d_up = (int16_t *)mi_dev_alloc(ctx, n * s->up_stride * 2);
+	if (lp) { // the ingress writes the microphone tick at `rate` here
+		const SessionLegsSizes sizes = {s->n, s->len, cfg->rate, lp->hin_stride, lp->hout_stride, lp->in_row, lp->in_scratch, lp->out_scratch,
+		                                lp->used, lp->ratio.data(), lp->codec.data()};
+		if ((rc = mi_session_legs_create(ctx, sizes, &s->legs)) != MI_OK) return fail(rc);
+		s->up_stride = s->len;
+	}
+	if (s->rs || lp) s->d_up = (int16_t *)mi_dev_alloc(ctx, n * s->up_stride * 2);
 	s->rounds = (s->len + s->frame - 1) / s->frame;
 	if (s->rounds > MI_AEC_MAX_TICK_FRAMES) return fail(MI_ENOTSUP);
 	if (!(s->d_reset_gate = (uint8_t *)mi_dev_alloc(ctx, n))) return fail(MI_ENOMEM);
 	s->d_tick = (int16_t *)mi_dev_alloc(ctx, n * s->len * 2);
-	if ((s->rs && !s->d_up) || !s->d_tick) return fail(MI_ENOMEM);
+	if (((s->rs || lp) && !s->d_up) || !s->d_tick) return fail(MI_ENOMEM);
 	if (cfg->mic_codec && !(s->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * s->in_len * 2))) return fail(MI_ENOMEM);
 	if (s->rs_out && !(s->d_down = (int16_t *)mi_dev_alloc(ctx, n * s->down_stride * 2))) return fail(MI_ENOMEM);
 	if (cfg->plc) {
-		if ((rc = mi_plc_create(ctx, s->n, cfg->in_rate, s->in_len, &s->plc)) != MI_OK) return fail(rc);
-		std::vector<int32_t> lens(n, s->in_len);
-		if (!(s->d_evlen = (int32_t *)mi_dev_alloc(ctx, n * 4))) return fail(MI_ENOMEM);
-		MI_HIP(hipMemcpy(s->d_evlen, lens.data(), n * 4, hipMemcpyHostToDevice));
+		if (lp) { // at every leg's own rate behind its own decoder, into PCM rows of pcm_pitch samples
+			std::vector<uint8_t> kind(n);
+			for (size_t i = 0; i < n; ++i) kind[i] = lp->codec[i] & 3;
+			if ((rc = mi_plc_create_legs(ctx, s->n, lp->rate.data(), kind.data(), lp->pcm_pitch, &s->plc)) != MI_OK) return fail(rc);
+			if (!(s->d_pcm = (int16_t *)mi_dev_alloc(ctx, n * lp->pcm_pitch * 2))) return fail(MI_ENOMEM);
+			MI_HIP(hipMemsetAsync(s->d_pcm, 0, n * lp->pcm_pitch * 2, ctx->stream));
+		} else {
+			if ((rc = mi_plc_create(ctx, s->n, cfg->in_rate, s->in_len, &s->plc)) != MI_OK) return fail(rc);
+			std::vector<int32_t> lens(n, s->in_len);
+			if (!(s->d_evlen = (int32_t *)mi_dev_alloc(ctx, n * 4))) return fail(MI_ENOMEM);
+			MI_HIP(hipMemcpy(s->d_evlen, lens.data(), n * 4, hipMemcpyHostToDevice));
+		}
 		for (int i = 0; i < SLOTS; ++i) {
 			s->h_ev[i] = (uint8_t *)mi_host_alloc(ctx, n);
 			s->d_ev[i] = (uint8_t *)mi_dev_alloc(ctx, n);
@@ -299,6 +362,52 @@ int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **ou
 	if ((rc = s->conf.create(ctx, s->n, cfg->members_per_conference, SLOTS, nullptr, s->vol, s->mix, s->plc)) != MI_OK) return fail(rc);
 	MI_HIP(hipStreamSynchronize(ctx->stream));
 	*out = s;
+	return MI_OK;
+}
+
+int mi_session_create(mi_ctx *ctx, const mi_session_config *cfg, mi_session **out) { return build_session(ctx, cfg, nullptr, out); }
+
+int mi_legs_session_create(mi_ctx *ctx, const mi_session_config *cfg, const mi_session_leg *h_legs, mi_session **out) {
+	if (!h_legs) return mi_session_create(ctx, cfg, out);
+	MI_CHECK_ARG(cfg && out);
+	*out = nullptr;
+	SessionPlan plan; // every refusal comes from here, before the device is asked for anything
+	int rc = plan_session_legs(cfg, h_legs, &plan);
+	if (rc != MI_OK) return rc;
+	MI_CHECK_ARG(ctx != nullptr);
+	if (plan.uniform) rc = build_session(ctx, &plan.cfg, nullptr, out);
+	else { // the canceller's side of the session: `rate` in and out, 16-bit PCM; the legs' side is the plan's
+		mi_session_config c = *cfg;
+		c.in_rate = c.rate, c.out_rate = 0, c.mic_codec = c.out_codec = MI_SESSION_PCM16;
+		rc = build_session(ctx, &c, &plan, out);
+	}
+	if (rc == MI_OK) (*out)->kinds.assign(h_legs, h_legs + cfg->nstreams);
+	return rc;
+}
+
+// a leg's kind: as mi_session_create_legs was given it, else the one kind of mi_session_create's configuration (its in_rate)
+static mi_session_leg leg_kind(const mi_session *s, int stream) {
+	if (!s->kinds.empty()) return s->kinds[(size_t)stream];
+	return {s->cfg.in_rate, s->cfg.mic_codec, s->cfg.out_codec};
+}
+
+int mi_legs_session_rate(const mi_session *s, int stream) {
+	if (!s || stream < 0 || stream >= s->n) return mi::set_error("mi_session_leg_rate: %s", s ? "stream out of range" : "a null session"), (int)MI_EINVAL;
+	return leg_kind(s, stream).rate;
+}
+
+int mi_legs_session_codec(const mi_session *s, int stream, int *mic_codec, int *out_codec) {
+	if (!s || stream < 0 || stream >= s->n) return mi::set_error("mi_session_leg_codec: %s", s ? "stream out of range" : "a null session"), (int)MI_EINVAL;
+	const mi_session_leg k = leg_kind(s, stream);
+	if (mic_codec) *mic_codec = k.mic_codec;
+	if (out_codec) *out_codec = k.out_codec;
+	return MI_OK;
+}
+
+int mi_legs_session_bytes(const mi_session *s, int stream, int *mic_bytes, int *out_bytes) {
+	if (!s || stream < 0 || stream >= s->n) return mi::set_error("mi_session_leg_bytes: %s", s ? "stream out of range" : "a null session"), (int)MI_EINVAL;
+	if (mic_bytes) *mic_bytes = s->legs ? s->plan.mic_bytes(stream) : (int)s->mic_bytes;
+	if (out_bytes) *out_bytes = s->legs ? s->plan.out_bytes(stream) : (int)s->out_bytes;
 	return MI_OK;
 }
 
@@ -361,7 +470,8 @@ int mi_session_submit(mi_session *s) {
 		    int rc = s->conf.apply(slot, [&](const mi_seat_cmd *d_cmd, int count) { return launch_seats(s, slot, d_cmd, count); });
 		    if (rc != MI_OK) return rc;
 		    // the report's launch follows the tick's kernels -- behind the slot's graph, never inside it
-		    if (!s->cfg.use_graphs) return (rc = run_tick_kernels(s, slot)) != MI_OK ? rc : s->conf.report(slot);
+		    // (legs that differ with plc: the per-leg concealer's launches are not captured -- the tick is launched directly)
+		    if (!s->cfg.use_graphs || (s->legs && s->plc)) return (rc = run_tick_kernels(s, slot)) != MI_OK ? rc : s->conf.report(slot);
 		    if (!s->graph[slot]) {
 			    // first use of the slot: run eagerly once is not an option (state would advance twice), so capture directly
 			    if ((rc = mi_ctx_capture_begin(c)) != MI_OK) return rc;
@@ -424,7 +534,20 @@ int mi_session_change_members(mi_session *s, const mi_session_change *h_changes,
 	static_assert(MI_SESSION_JOIN == MI_SEAT_JOIN && MI_SESSION_LEAVE == MI_SEAT_LEAVE, "the public ops are the command's");
 	const char *fn = "mi_session_change_members";
 	if (!s) return mi::set_error("%s: a null session", fn), (int)MI_EINVAL;
-	return s->conf.book.change_uniform_members(fn, "MI_SESSION_JOIN (1) or MI_SESSION_LEAVE (2)", h_changes, count, s->in_len);
+	const char *names = "MI_SESSION_JOIN (1) or MI_SESSION_LEAVE (2)";
+	if (!s->legs) return s->conf.book.change_uniform_members(fn, names, h_changes, count, s->in_len);
+	// legs that differ: a JOIN re-seats the seat's own kind -- its tick's length, its class and decoder in the concealer
+	mi::ConferenceBook &book = s->conf.book;
+	const int rc = mi::check_uniform_changes(fn, names, book.n(), book.roster.flags.data(), h_changes, count, &book.controls.scratch);
+	for (int i = 0; rc == MI_OK && i < count; ++i) {
+		const mi_session_change &c = h_changes[i];
+		mi::SeatChanges::Pending &p = book.change_member(c.stream, (uint8_t)c.op);
+		if (c.op != MI_SEAT_JOIN) continue;
+		const mi_session_leg &k = s->kinds[(size_t)c.stream];
+		p.len = k.rate / 100, p.codec = s->plan.codec[(size_t)c.stream], p.ratio = s->plan.ratio[(size_t)c.stream];
+		if (s->plc) p.cls = (uint8_t)std::max(0, mi_plc_class_of(s->plc, c.stream, k.rate)), mi_plc_seat(s->plc, c.stream, p.cls, k.mic_codec);
+	}
+	return rc;
 }
 
 int mi_session_change_controls(mi_session *s, const mi_session_control *h_changes, int count) {
@@ -468,6 +591,7 @@ int mi_session_reset_streams(mi_session *s, int first, int count) {
 	    (rc = mi_fifo_reset_range(s->f_out, first, count)) != MI_OK)
 		return rc;
 	if (s->rs_out && (rc = mi_resampler_reset(s->rs_out, first, count)) != MI_OK) return rc;
+	if (s->legs && (rc = mi_session_legs_reset(s->legs, first, count)) != MI_OK) return rc;
 	if (s->plc && (rc = mi_plc_reset(s->plc, first, count)) != MI_OK) return rc;
 	if (s->cfg.ref_loopback) // the new leg was not sent anything yet
 		for (int i = 0; i < SLOTS; ++i)

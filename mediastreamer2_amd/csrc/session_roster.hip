@@ -42,7 +42,7 @@ __device__ __forceinline__ void fresh_fifo(const FifoView &f, int s, int silence
 __device__ __forceinline__ void fresh_resampler(const ResamplerEdit &r, int s, int t) { // speex_resampler_init
 	if (!r.hist) return;
 	zero_groups(r.hist + (size_t)s * r.hist_stride, (size_t)r.hist_stride * sizeof(int16_t), t);
-	if (t == 0) r.pos[s] = make_int2(0, 0);
+	if (t == 0 && r.pos) r.pos[s] = make_int2(0, 0); // (a per-leg history row of mi_session_create_legs has no position word)
 }
 
 __global__ __launch_bounds__(RT) void session_roster_kernel(SessionRosterArgs a) {
@@ -95,7 +95,10 @@ bool whole_groups(const AecEdit &e) {
 int mi_session_roster_launch(const SessionRosterArgs &a, hipStream_t stream) {
 	MI_CHECK_ARG(a.cmd && a.count > 0 && a.count <= a.nstreams && whole_groups(a.aec) && a.vol.state && a.vol.win && a.vol.energy[0] &&
 	             a.vol.energy[1] && a.flags && a.out && a.out_bytes > 0 && a.mix_len > 0);
-	MI_CHECK_ARG((!a.rs_in.hist || (a.rs_in.pos && a.rs_in.hist_stride % 8 == 0)) && (!a.rs_out.hist || (a.rs_out.pos && a.rs_out.hist_stride % 8 == 0)));
+	// an mi_resampler's history goes with its position word; the legs' own rows have none
+	MI_CHECK_ARG((!a.rs_in.hist || ((a.leg_rows || a.rs_in.pos) && a.rs_in.hist_stride % 8 == 0)) &&
+	             (!a.rs_out.hist || ((a.leg_rows || a.rs_out.pos) && a.rs_out.hist_stride % 8 == 0)));
+	MI_CHECK_ARG(!a.leg_rows || (a.rs_in.hist && a.rs_out.hist && !a.rs_in.pos && !a.rs_out.pos));
 	// every queue holds what a fresh seat is given
 	const int lead = a.lead_phases >= 2 ? a.lead_unit * (a.lead_phases - 1) : 0;
 	MI_CHECK_ARG(a.f_mic.ring && a.f_mic.pos && a.f_ref.ring && a.f_ref.pos && a.f_out.ring && a.f_out.pos && a.ref_delay >= 0 && a.lead_unit >= 0 &&

@@ -11,6 +11,7 @@ struct SessionRosterArgs {
 	int count, nstreams;
 	AecEdit aec;
 	ResamplerEdit rs_in, rs_out;
+	bool leg_rows; // rs_in, rs_out are the per-leg history rows of session_legs.hip (mi_session_create_legs): no position word
 	VolumeEdit vol;
 	uint8_t *flags; // the pins' MI_MIX_*
 	FifoView f_mic, f_ref, f_out;
